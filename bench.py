@@ -65,6 +65,11 @@ HUE_DELTA = 37
 NOISE_STD = 10.0
 LEVEL = 5
 
+# --dump-outputs: pixel positions sampled per image (fewer when the batch is large), all files together under 64 MB
+DUMP_SEED = 8191
+DUMP_PIXELS_PER_IMAGE = 8192
+DUMP_BUDGET_BYTES = 48 << 20
+
 
 def _noise_plane(args):
     seed, shape = args
@@ -118,6 +123,28 @@ def cpu_baseline(size, n_images):
                   f'the sample draws its noise plane from the numpy stream inside the timed region (since round 3; the round-2 figure '
                   f'of 17 Mpx/s took the planes as given), then grid->map, remap, blur, hue shift, noise add',
     }
+
+
+def dump_outputs(out_dir, batch, count):
+    """What a caller of the timed path holds after its last step -- ``count`` uint8 RGB images, each of its own result shape --
+    written so that two builds can be compared output for output: every image's shape and byte sum (float64, exact), and the
+    values of a fixed, seeded sample of pixel positions of every image (float32)."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_image = max(1, min(DUMP_PIXELS_PER_IMAGE, DUMP_BUDGET_BYTES // (count * 3 * 4)))
+    shapes = np.zeros((count, 2), np.float64)
+    sums = np.zeros(count, np.float64)
+    sample = np.zeros((count, per_image, 3), np.float32)
+    for j in range(count):
+        image = batch.result(j)
+        h, w = image.shape[:2]
+        shapes[j] = h, w
+        sums[j] = image.sum(dtype=np.uint64)
+        rng = np.random.default_rng([DUMP_SEED, j])
+        sample[j] = image[rng.integers(0, h, per_image), rng.integers(0, w, per_image)]
+    files = {'result_shapes': shapes, 'result_sums': sums, 'result_pixel_sample': sample}
+    for name, array in files.items():
+        np.save(os.path.join(out_dir, name + '.npy'), array)
+    return sorted(files)
 
 
 def host_cpu_facts():
@@ -535,7 +562,14 @@ def main():
                     help='rendezvous, barriers and the MAX reduction of the timing protocol only, over gloo, no GPU: the N > 1 path on '
                          'a box without GPUs (tests/test_bench_launch.py)')
     ap.add_argument('--noise-workers', type=int, default=0, help='unused since round 3 (the planes are drawn on the device); kept for old command lines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (rank 0\'s images) as DIR/<name>.npy: every '
+                         'image\'s shape and byte sum, and a fixed, seeded sample of its pixels; the default path (c3, resident) only')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.config != 'c3' or args.mode != 'resident' or args.dry_run):
+        ap.error('--dump-outputs covers the default path only (--config c3 --mode resident, no --dry-run)')
     if args.batch <= 0:
         args.batch = 64 if args.config == 'c4' else 256
 
@@ -644,6 +678,8 @@ def main():
     elapsed = shard.timed_steps(group, batch.run, steps=args.steps, warmup=0, device_sync=full_sync)
     major_times = batch.timings()
     batch.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, B)
     # what took part: the pixels every rank really processed (SUM all-reduce, not rank 0's count x world), the backend and world size
     # the process group reports, the PCI bus id of every rank's GPU
     total_px = group.sum_int(batch.source_pixels * args.steps)
@@ -832,11 +868,12 @@ def main():
             'poisson_noise_1024': _tool_json('poisson_probe.py', device_index, 180, ('1024',)),
             # the reference's own scaling model on one GPU: a pool of worker PROCESSES (vkit/utility/pool.py:153-243), each running whole
             # C4 pages through PageAssemblerStep -> PageDistortionStep -> PageResizingStep, host objects in and out (tools/pool_scale.py)
-            'C4_reference_api_worker_pool': _tool_json('pool_scale.py', device_index, 240, ('--workers', '1,8', '--seconds', '3', '--modes', 'pipeline')),
+            # at most 4 workers: with this process they are 5 holding the GPU, within the 6 a shared machine allows
+            'C4_reference_api_worker_pool': _tool_json('pool_scale.py', device_index, 240, ('--workers', '1,4', '--seconds', '3', '--modes', 'pipeline')),
             'note': 'BASELINE.json configs[1], [3], [4] on this box and clock, device resident (tools/c2.py, c4.py, c5.py): never '
                     'the headline value; poisson_noise_1024: rng.poisson(image) drawn on the device against numpy itself (values and stream '
                     'position, tools/poisson_probe.py), host arrays in and out; C4_reference_api_worker_pool: pages/s through the reference\'s '
-                    'step objects with 1 and 8 worker processes sharing this GPU (a worker is bound by its Python, a pool by the kernel time '
+                    'step objects with 1 and 4 worker processes sharing this GPU (a worker is bound by its Python, a pool by the kernel time '
                     'of a page: DESIGN.md section 5, round 6)',
         }
 
