@@ -423,6 +423,15 @@ int vkx_resize_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, 
 int vkx_resize_u8(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_t src_stride,
                   uint8_t *dst, int dh, int dw, ptrdiff_t dst_stride, int interpolation);
 
+/* jpeg_quality photometric/effect.py:41-42: cv.imdecode(cv.imencode('.jpeg', mat, [IMWRITE_JPEG_QUALITY, quality])) as
+ * libjpeg-turbo computes it (baseline tables scaled by jpeg_set_quality, 4:2:0, accurate integer DCT, fancy upsampling).
+ * cn 3: the mat is BGR to the codec (channel 2 carries the R weight); cn 1: a one-component (grayscale) JPEG.  quality
+ * 0 .. 100 (0 scales as 1).  Two launches; the decoded planes live in context scratch between them (cn 3 only). */
+int vkx_jpeg_roundtrip_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
+                              uint8_t *dst, ptrdiff_t dst_stride, int quality);
+int vkx_jpeg_roundtrip_u8(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
+                          uint8_t *dst, ptrdiff_t dst_stride, int quality);
+
 /* cv.filter2D(image, -1, kernel) on uint8 with a float32 kernel of up to 15 x 15 taps (HOST pointer, row-major):
  * defocus_blur / motion_blur  photometric/blur.py:85-192.  Correlation anchored at the kernel centre,
  * BORDER_REFLECT_101, the non-zero taps in row-major order accumulated in float32 (products and sums rounded

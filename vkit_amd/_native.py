@@ -302,6 +302,7 @@ for _sfx in ('', '_dev'):
     _SIGNATURES['vkx_fill_u8' + _sfx] = [c_void_p] + _PLANE_U8 + [ctypes.POINTER(VkxLayer), c_int]
     _SIGNATURES['vkx_fill_f32' + _sfx] = [c_void_p, c_void_p, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayerF32), c_int]
     _SIGNATURES['vkx_resize_u8' + _sfx] = [c_void_p] + _PLANE_U8 + [c_void_p, c_int, c_int, c_ssize, c_int]
+    _SIGNATURES['vkx_jpeg_roundtrip_u8' + _sfx] = [c_void_p] + _PLANE_U8 + [c_void_p, c_ssize, c_int]
     _SIGNATURES['vkx_zoom_in_blur_u8' + _sfx] = [c_void_p] + _PLANE_U8 + [c_void_p, c_int, c_double, c_void_p, c_ssize]
     _SIGNATURES['vkx_resize_cubic_u8' + _sfx] = [c_void_p] + _PLANE_U8 + [c_void_p, c_int, c_int, c_ssize]
     _SIGNATURES['vkx_resize_cubic_f32' + _sfx] = [c_void_p, c_void_p, c_int, c_int, c_ssize, c_void_p, c_int, c_int, c_ssize]
@@ -1805,6 +1806,20 @@ def resize(src, dsize_hw, interpolation, ctx=None):
     sh, sw, cn, stride = _shape_u8(src)
     dst, dptr = call.out((dh, dw) + tuple(src.shape[2:]), np.uint8)
     check(call.fn('vkx_resize_u8')(call.ctx.handle, call.src(src), sh, sw, cn, stride, dptr, dh, dw, dw * cn, int(interpolation)))
+    return dst
+
+
+def jpeg_roundtrip(img, quality, ctx=None):
+    """cv.imdecode(cv.imencode('.jpeg', img, [IMWRITE_JPEG_QUALITY, quality])) as libjpeg-turbo computes it
+    (include/vkx.h vkx_jpeg_roundtrip_u8) for uint8 HxW (grayscale) or HxWx3 (BGR to the codec) arrays."""
+    if not 0 <= int(quality) <= 100:
+        raise ValueError(f'quality={quality}: 0 .. 100')
+    call = _Call(ctx, img)
+    h, w, cn, stride = _shape_u8(img)
+    if cn not in (1, 3) or (img.ndim == 3 and cn == 1):
+        raise ValueError(f'jpeg_roundtrip takes HxW or HxWx3, got shape {img.shape}')
+    dst, dptr = call.out(img.shape, np.uint8)
+    check(call.fn('vkx_jpeg_roundtrip_u8')(call.ctx.handle, call.src(img), h, w, cn, stride, dptr, stride, int(quality)))
     return dst
 
 

@@ -74,6 +74,7 @@ struct vkx_ctx {
     vkx_scratch mls_work;                     // batched similarity_mls states (mls.hip): descriptors, handle tables, projected positions
     vkx_scratch camera_work;                  // camera states (camera.hip): descriptors, results, the depth values of the cubic curve
     vkx_scratch fog_work;                     // fog field (fog.hip): raw draws + the float64 centres of a level; a glass round's temporaries
+    vkx_scratch jpeg_planes;                  // jpeg round trip (jpeg.hip): the decoded Y, Cb, Cr planes at their padded sizes
     vkx_scratch glass_win;                    // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows
     bool pz_tabs_ready = false;

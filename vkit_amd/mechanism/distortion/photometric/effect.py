@@ -4,8 +4,9 @@ by level), with numpy itself otherwise (``generate_diamond_square_mask``, the st
 every pixel towards the fog colour with the field as float32 alpha, ``uint8(clip((1 - a) * px + a * fog))`` -- is the
 alpha composite ``vkx_fill_u8`` with one page-sized layer.  ``pixelation`` (:56-86) shrinks with ``cv.resize``
 INTER_LINEAR and grows back with INTER_NEAREST (``vkx_resize_u8``).  ``jpeg_quality`` (:25-53, an encoder round trip
-through ``cv.imencode`` / ``cv.imdecode``) is outside the path: the operator exists with the reference's config so that
-policies sample it draw for draw, the image passes through (``photometric/opt.py: pass_through_out_of_path``)."""
+through ``cv.imencode`` / ``cv.imdecode``) is outside the default path: the operator exists with the reference's config so that
+policies sample it draw for draw, and the image passes through (``photometric/opt.py: pass_through_out_of_path``) unless
+``out_of_path`` is 'device': then ``vkx_jpeg_roundtrip_u8`` computes libjpeg-turbo's round trip (csrc/jpeg.hip)."""
 from typing import Any, Mapping, Optional, Tuple
 
 import attrs
@@ -15,7 +16,7 @@ from numpy.random import Generator as RandomGenerator
 from vkit_amd import _native
 from vkit_amd.element import Image, ImageMode
 from ..interface import Distortion, DistortionConfig, DistortionNopState
-from .opt import pass_through_out_of_path
+from .opt import out_of_path_behaviour, pass_through_out_of_path, to_original_image, to_rgb_image
 
 
 @attrs.define
@@ -25,7 +26,12 @@ class JpegQualityConfig(DistortionConfig):
 
 def jpeg_quality_image(config: JpegQualityConfig, state, image: Image, rng: Optional[RandomGenerator]):
     assert 0 <= config.quality <= 100
-    return pass_through_out_of_path('jpeg_quality', image)
+    if out_of_path_behaviour() != 'device':
+        return pass_through_out_of_path('jpeg_quality', image)
+    mode = image.mode
+    image = to_rgb_image(image, mode)
+    image = attrs.evolve(image, mat=_native.jpeg_roundtrip(image.arr, config.quality))
+    return to_original_image(image, mode)
 
 
 jpeg_quality = Distortion(

@@ -34,10 +34,13 @@ def to_original_image(image: Image, mode: ImageMode):
 #                             through such an operator says so: ``DistortionResult.meta['out_of_path'] = ('jpeg_quality',)``
 #                             (RandomDistortion collects the names of all its stages there)
 #   'raise'                   NotImplementedError: for callers that must not miss a stage
+#   'device'                  the operators that have a device restatement run it (jpeg_quality: vkx_jpeg_roundtrip_u8, the
+#                             libjpeg-turbo round trip of cv.imencode / cv.imdecode); no warning, no ``out_of_path`` entry
 # chosen, in this order, by ``random_distortion_factory.create(config, out_of_path='raise')`` / ``RandomDistortion(...,
 # out_of_path='raise')`` (the object's own setting wins inside its ``distort``), by ``with out_of_path('raise'):`` around the call,
-# by the environment (VKX_OUT_OF_PATH=raise|pass_through; VKX_STRICT_UNSUPPORTED=1 is the older spelling of 'raise').
+# by the environment (VKX_OUT_OF_PATH=raise|pass_through|device; VKX_STRICT_UNSUPPORTED=1 is the older spelling of 'raise').
 OUT_OF_PATH_OPERATORS = ('jpeg_quality',)
+BEHAVIOURS = ('raise', 'pass_through', 'device')
 _warned = set()
 _choice = threading.local()
 
@@ -47,7 +50,7 @@ def out_of_path_behaviour() -> str:
     if chosen:
         return chosen
     env = os.environ.get('VKX_OUT_OF_PATH', '')
-    if env in ('raise', 'pass_through'):
+    if env in BEHAVIOURS:
         return env
     return 'raise' if os.environ.get('VKX_STRICT_UNSUPPORTED', '') == '1' else 'pass_through'
 
@@ -58,11 +61,11 @@ def out_of_path_context_choice():
 
 
 class out_of_path:
-    """``with out_of_path('raise'):`` / ``with out_of_path('pass_through'):`` -- the behaviour for the calls inside (this thread)."""
+    """``with out_of_path('raise'):`` / ``'pass_through'`` / ``'device'`` -- the behaviour for the calls inside (this thread)."""
 
     def __init__(self, behaviour):
-        if behaviour not in (None, 'raise', 'pass_through'):
-            raise ValueError(f"out_of_path={behaviour!r}: 'raise' or 'pass_through'")
+        if behaviour not in (None,) + BEHAVIOURS:
+            raise ValueError(f"out_of_path={behaviour!r}: 'raise', 'pass_through' or 'device'")
         self.behaviour = behaviour
 
     def __enter__(self):

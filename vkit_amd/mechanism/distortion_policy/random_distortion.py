@@ -148,8 +148,8 @@ class RandomDistortion:
     def __init__(self, configs: Sequence[RandomDistortionStageConfig], level_min: int, level_max: int,
                  out_of_path: Optional[str] = None):
         """``out_of_path``: what the operators outside the accelerated path (``UNSUPPORTED_POLICY_NAMES``) do with the image when
-        they are drawn -- 'pass_through' (config sampled, image unchanged, the result's ``meta['out_of_path']`` names them) or
-        'raise'; None leaves it to the surrounding ``out_of_path(...)`` context / the environment (photometric/opt.py)."""
+        they are drawn -- 'pass_through' (config sampled, image unchanged, the result's ``meta['out_of_path']`` names them),
+        'raise', or 'device' (their device restatement runs: jpeg_quality's libjpeg-turbo round trip); None leaves it to the surrounding ``out_of_path(...)`` context / the environment (photometric/opt.py)."""
         self.stages = [RandomDistortionStage(config) for config in configs]
         self.level_min = level_min
         self.level_max = level_max
@@ -321,7 +321,7 @@ class RandomDistortionFactory:
 
     def create(self, config: Optional[Union[Mapping[str, Any], PathType, RandomDistortionFactoryConfig]] = None,
                out_of_path: Optional[str] = None):
-        """``out_of_path``: 'raise' | 'pass_through' | None, see ``RandomDistortion`` (the reference's ``create(config)`` plus the
+        """``out_of_path``: 'raise' | 'pass_through' | 'device' | None, see ``RandomDistortion`` (the reference's ``create(config)`` plus the
         one switch this path needs: what a drawn ``jpeg_quality`` does)."""
         config = dyn_structure(config, RandomDistortionFactoryConfig, support_path_type=True, support_none_type=True)
 
