@@ -14,7 +14,12 @@
  *     pointers, stage through ctx scratch and are synchronous; the library never retains a
  *     host pointer past the call.
  *   - Images are row-major, channel-interleaved; `*_stride` is the row pitch in BYTES for
- *     uint8 planes and in ELEMENTS for float32 / int16 / int32 planes (`*_stride_el`).
+ *     uint8 planes and in ELEMENTS for float32 / int16 / int32 planes (`*_stride_el`).  A stride is at least
+ *     one row (width x channels); a shorter or negative one is VKX_ERR_INVALID before anything is launched, except
+ *     on a single-row plane, whose stride is never used.  This holds for stride arguments and for the planes of
+ *     vkx_elem, vkx_layer(_f32), vkx_paint_set and vkx_noise_plane; vkx_chain_item has limits of its own.  Entry points that cannot run in place (resize, remap, warps, blurs and
+ *     filter2d, gather, the JPEG round trip, zoom_in_blur, channel-count conversions, the channel permutation)
+ *     refuse a source and destination whose byte ranges overlap.
  *   - Integer and byte results are bit-exact with oracle/ (the CPU restatement of the
  *     reference's numpy/OpenCV arithmetic); float32 results (ScoreMap) are bit-exact too,
  *     the stated tolerance against cv2 itself is 2 ulp.

@@ -1,0 +1,105 @@
+"""The strided exports of include/vkx.h and where their pitch contract is tested.
+
+Every exported function with a `stride` or `pitch` parameter, or with a parameter whose struct type carries a `*_stride`
+field (vkx_elem, vkx_layer, vkx_paint_set, vkx_noise_plane, vkx_chain_item, ...), is either exercised by
+tests/test_gpu_strides.py (COVERED: its cases run the entry point on offset, padded and windowed planes) or listed in EXEMPT
+with the reason it is not.  tests/test_stride_coverage.py checks on the CPU that nothing falls between the two; the GPU module
+checks that every name in COVERED has a case.  An exemption is from the layout cases only: the refusal of short and negative
+strides is tested for every entry point named in REFUSAL_TESTED too.  Nothing here loads libvkx.so.
+"""
+import os
+import re
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'vkx.h')
+
+# device entry points with a case of their own in test_gpu_strides.py
+COVERED_DEV = {
+    'vkx_remap_u8_dev', 'vkx_remap_f32_dev',
+    'vkx_warp_affine_u8_dev', 'vkx_warp_affine_f32_dev', 'vkx_warp_perspective_u8_dev', 'vkx_warp_perspective_f32_dev',
+    'vkx_gaussian_blur_u8_dev', 'vkx_filter2d_u8_dev',
+    'vkx_color_shift_rgb_dev', 'vkx_cvt_rgb_hsv_u8_dev', 'vkx_mean_shift_u8_dev', 'vkx_add_noise_i16_dev',
+    'vkx_brightness_shift_rgb_dev', 'vkx_color_balance_rgb_dev', 'vkx_pointwise_u8_dev', 'vkx_apply_lut_u8_dev',
+    'vkx_impulse_noise_u8_dev', 'vkx_histogram_u8_dev',
+    'vkx_line_streak_u8_dev', 'vkx_ellipse_mask_u8_dev', 'vkx_ellipse_streak_u8_dev',
+    'vkx_cvt_color_u8_dev', 'vkx_blend_u8_dev', 'vkx_fog_f32_u8_dev', 'vkx_sum_f32_u8_dev', 'vkx_gather_u8_dev',
+    'vkx_speckle_noise_u8_dev', 'vkx_fill_u8_dev', 'vkx_fill_u8_batch_dev', 'vkx_fill_f32_dev',
+    'vkx_resize_cubic_u8_dev', 'vkx_resize_cubic_f32_dev', 'vkx_resize_u8_dev', 'vkx_resize_f32_dev',
+    'vkx_jpeg_roundtrip_u8_dev', 'vkx_zoom_in_blur_u8_dev', 'vkx_noise_normal_i16_dev',
+}
+
+# host entry points run on pitched host buffers with canaries (HostStage's pitched gather and copy-out)
+COVERED_HOST = {
+    'vkx_remap_u8', 'vkx_warp_affine_u8', 'vkx_gaussian_blur_u8', 'vkx_filter2d_u8', 'vkx_color_shift_rgb', 'vkx_blend_u8',
+    'vkx_fill_u8', 'vkx_resize_u8', 'vkx_resize_f32', 'vkx_line_streak_u8', 'vkx_speckle_noise_u8', 'vkx_fog_f32_u8',
+    'vkx_gather_u8', 'vkx_jpeg_roundtrip_u8', 'vkx_zoom_in_blur_u8', 'vkx_cvt_color_u8', 'vkx_noise_normal_i16',
+}
+
+_HOST_FORM = 'the host form stages through the same HostStage gather / copy-out as the host entry points of COVERED_HOST ' \
+             'and runs the _dev form this table covers'
+
+EXEMPT = {
+    'vkx_remap_f32': _HOST_FORM,
+    'vkx_warp_affine_f32': _HOST_FORM,
+    'vkx_warp_perspective_u8': _HOST_FORM,
+    'vkx_warp_perspective_f32': _HOST_FORM,
+    'vkx_cvt_rgb_hsv_u8': _HOST_FORM,
+    'vkx_mean_shift_u8': _HOST_FORM,
+    'vkx_add_noise_i16': _HOST_FORM,
+    'vkx_brightness_shift_rgb': _HOST_FORM,
+    'vkx_color_balance_rgb': _HOST_FORM,
+    'vkx_pointwise_u8': _HOST_FORM,
+    'vkx_histogram_u8': _HOST_FORM,
+    'vkx_sum_f32_u8': _HOST_FORM,
+    'vkx_apply_lut_u8': _HOST_FORM,
+    'vkx_impulse_noise_u8': _HOST_FORM,
+    'vkx_ellipse_mask_u8': _HOST_FORM,
+    'vkx_ellipse_streak_u8': _HOST_FORM,
+    'vkx_fill_f32': _HOST_FORM,
+    'vkx_resize_cubic_u8': _HOST_FORM,
+    'vkx_resize_cubic_f32': _HOST_FORM,
+    'vkx_grid_to_map_dev': 'grid raster: writes map planes only, every caller passes dense ones; no layout cases yet',
+    'vkx_grid_to_map': 'host form of vkx_grid_to_map_dev',
+    'vkx_remap_multi_dev': 'element descriptors carry their strides; the gather is the remap kernel of vkx_remap_*_dev',
+    'vkx_grid_remap_dev': 'element descriptors carry their strides; the lattice remap is pinned by test_gpu_parity',
+    'vkx_grid_remap': 'host form of vkx_grid_remap_dev',
+    'vkx_noise_normal_i16_batch_dev': 'the planes of vkx_noise_normal_i16_dev, which the table covers, in one launch',
+    'vkx_paint_poly_sets_fresh_dev': 'label paint (dense planes in every caller); no layout cases yet',
+    'vkx_chain_rgb_batch_dev': 'fused page chain: its items take the dense page planes of the batch; no layout cases yet',
+    'vkx_chain_rgb_batch_np_dev': 'fused page chain with its noise streams; as vkx_chain_rgb_batch_dev',
+    'vkx_remap_multi': 'host form of vkx_remap_multi_dev',
+    'vkx_fill_u8_dev_host_layers': 'layer planes are gathered densely in the page-locked ring; the composite is vkx_fill_u8_dev',
+    'vkx_fill_poly_mask_u8_dev': 'polygon raster (label planes, dense in every caller); no layout cases yet',
+    'vkx_fill_poly_mask_u8': 'host form of vkx_fill_poly_mask_u8_dev',
+    'vkx_paint_polys_dev': 'label paint (dense planes in every caller); no layout cases yet',
+    'vkx_paint_polys': 'host form of vkx_paint_polys_dev',
+    'vkx_paint_polys_fresh_dev': 'label paint (dense planes in every caller); no layout cases yet',
+    'vkx_glass_round_dev': '`pitch` is the spacing of the swap lattice, not a row pitch; the planes are dense',
+}
+
+COVERED = COVERED_DEV | COVERED_HOST
+
+# exempt entry points whose refusal of short and negative strides test_gpu_strides.py tests all the same
+REFUSAL_TESTED = {
+    'vkx_fill_poly_mask_u8_dev', 'vkx_fill_poly_mask_u8', 'vkx_paint_polys_dev', 'vkx_paint_polys', 'vkx_paint_polys_fresh_dev',
+    'vkx_paint_poly_sets_fresh_dev', 'vkx_grid_to_map_dev', 'vkx_remap_multi_dev', 'vkx_grid_remap_dev',
+}
+
+
+def strided_structs(text):
+    """The struct types of vkx.h with a field whose name contains `stride`."""
+    return {m.group(2) for m in re.finditer(r'typedef\s+struct\s+\w+\s*\{([^}]*)\}\s*(\w+)\s*;', text, flags=re.S)
+            if 'stride' in m.group(1)}
+
+
+def strided_exports(path=HEADER):
+    """Names of the functions declared in vkx.h with a parameter whose name contains `stride` or `pitch`, or whose type is
+    (a pointer to) a struct with a stride field."""
+    with open(path) as f:
+        text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    structs = strided_structs(text)
+    names = []
+    for m in re.finditer(r'\bint\s+(vkx_\w+)\s*\(([^;]*?)\)\s*;', text, flags=re.S):
+        params = [p.strip() for p in m.group(2).split(',') if p.strip()]
+        if any('stride' in p.split()[-1] or 'pitch' in p.split()[-1] or set(re.findall(r'\w+', p)) & structs for p in params):
+            names.append(m.group(1))
+    return names

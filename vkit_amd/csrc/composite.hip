@@ -452,11 +452,20 @@ int composite_launch(vkx_ctx *ctx, T *dst, int h, int w, ptrdiff_t dstride, cons
     return VKX_OK;
 }
 
+inline ptrdiff_t value_stride_of(const vkx_layer &l) { return l.value_stride; }
+inline ptrdiff_t value_stride_of(const vkx_layer_f32 &l) { return l.value_stride_el; }
+
 template <typename LAYER>
-int check_layers(const LAYER *layers, int n_layers, int h, int w)
+int check_layers(const LAYER *layers, int n_layers, int h, int w, int cn = 1)
 {
     for (int i = 0; i < n_layers; i++) {
         const LAYER &l = layers[i];
+        // the pitch contract of vkx.h for the layer planes ([height, width] mask / alpha, [height, width, cn] value)
+        if (l.height > 1 && ((l.mask && l.mask_stride < l.width) || (l.alpha && l.alpha_stride_el < l.width) ||
+                             (l.value && value_stride_of(l) < (ptrdiff_t)l.width * cn))) {
+            vkx_set_error("layer %d: a plane's row stride is shorter than its row, or negative", i);
+            return VKX_ERR_INVALID;
+        }
         if (l.height < 0 || l.width < 0 || l.up < 0 || l.left < 0 || l.up + l.height > h || l.left + l.width > w) {
             vkx_set_error("layer %d: box (up=%d left=%d h=%d w=%d) outside the %dx%d destination", i, l.up, l.left,
                           l.height, l.width, h, w);
@@ -493,10 +502,11 @@ bool to_layer_dev(const LAYER &l, LayerDev<T> *L)
 VKX_EXPORT int vkx_fill_u8_dev(vkx_ctx *ctx, uint8_t *dst, int h, int w, int cn, ptrdiff_t dst_stride,
                                const vkx_layer *layers, int n_layers)
 {
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     VKX_REQUIRE(ctx && dst, "NULL argument");
     VKX_REQUIRE(n_layers >= 0 && (n_layers == 0 || layers), "bad layer list");
     VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");
-    int rc = check_layers(layers, n_layers, h, w);
+    int rc = check_layers(layers, n_layers, h, w, cn);
     if (rc) return rc;
     std::vector<LayerDev<uint8_t>> devl;
     devl.reserve((size_t)n_layers);
@@ -532,6 +542,7 @@ VKX_EXPORT int vkx_fill_u8_dev(vkx_ctx *ctx, uint8_t *dst, int h, int w, int cn,
 VKX_EXPORT int vkx_fill_u8_batch_dev(vkx_ctx *ctx, uint8_t *const *dsts_host, int n_pages, int h, int w, int cn,
                                      ptrdiff_t dst_stride, const vkx_layer *layers, const int32_t *layer_begin_host)
 {
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     VKX_REQUIRE(ctx && dsts_host && layer_begin_host, "NULL argument");
     VKX_REQUIRE(n_pages >= 1 && cn >= 1, "bad batch");
     VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");
@@ -542,7 +553,7 @@ VKX_EXPORT int vkx_fill_u8_batch_dev(vkx_ctx *ctx, uint8_t *const *dsts_host, in
     }
     const int n_layers = layer_begin_host[n_pages];
     VKX_REQUIRE(n_layers == 0 || layers, "bad layer list");
-    int rc = check_layers(layers, n_layers, h, w);
+    int rc = check_layers(layers, n_layers, h, w, cn);
     if (rc) return rc;
     std::vector<LayerDev<uint8_t>> devl;
     std::vector<int> page_begin((size_t)n_pages + 1, 0);
@@ -568,6 +579,7 @@ VKX_EXPORT int vkx_fill_u8_batch_dev(vkx_ctx *ctx, uint8_t *const *dsts_host, in
 VKX_EXPORT int vkx_fill_f32_dev(vkx_ctx *ctx, float *dst, int h, int w, ptrdiff_t dst_stride_el,
                                 const vkx_layer_f32 *layers, int n_layers)
 {
+    VKX_REQUIRE_PITCH(dst_stride_el, w, h);
     VKX_REQUIRE(ctx && dst, "NULL argument");
     VKX_REQUIRE(n_layers >= 0 && (n_layers == 0 || layers), "bad layer list");
     int rc = check_layers(layers, n_layers, h, w);

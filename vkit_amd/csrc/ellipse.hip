@@ -249,6 +249,7 @@ void ellipse_segments(int cx, int cy, int ax, int ay, std::vector<Segment> &out)
 VKX_EXPORT int vkx_ellipse_mask_u8_dev(vkx_ctx *ctx, uint8_t *mask, ptrdiff_t stride, int h, int w, int cx, int cy,
                                        const int32_t *axes_host, int n_ellipses, int thickness)
 {
+    VKX_REQUIRE_PITCH(stride, w, h);
     VKX_REQUIRE(ctx && mask && (axes_host || n_ellipses == 0), "NULL argument");
     VKX_REQUIRE(h > 0 && w > 0 && n_ellipses >= 0, "bad shape");
     VKX_REQUIRE(thickness >= 1 && thickness <= 32767, "thickness must be in 1 .. 32767 (cv.ellipse's MAX_THICKNESS; filled ellipses are not on the path)");
@@ -303,6 +304,7 @@ VKX_EXPORT int vkx_ellipse_streak_u8_dev(vkx_ctx *ctx, uint8_t *img, int h, int 
                                          const int32_t *axes_host, int n_ellipses, int thickness, const uint8_t color[4],
                                          double alpha)
 {
+    VKX_REQUIRE_PITCH(stride, (ptrdiff_t)w * cn, h);
     VKX_REQUIRE(ctx && img && color, "NULL argument");
     VKX_REQUIRE(h > 0 && w > 0 && (cn == 1 || cn == 3 || cn == 4), "bad shape");
     VKX_REQUIRE(alpha >= 0.0 && alpha <= 1.0, "alpha must be in [0, 1]");

@@ -281,6 +281,7 @@ VKX_EXPORT int vkx_grid_to_map_dev(vkx_ctx *ctx, const int32_t *src_vertices, co
 {
     VKX_REQUIRE(ctx && map_x && map_y, "NULL argument");
     VKX_REQUIRE(dh > 0 && dw > 0, "bad destination shape");
+    VKX_REQUIRE_PITCH(map_stride_el, dw, dh);
     int32_t *own = owner;
     if (!own) {
         int rc = vkx_scratch_reserve(ctx, &ctx->owner, sizeof(int32_t) * (size_t)dh * dw);
@@ -311,6 +312,7 @@ VKX_EXPORT int vkx_grid_remap_dev(vkx_ctx *ctx, const vkx_elem *elems, int n_ele
         if (elems[i].is_f32) VKX_REQUIRE(elems[i].cn == 1, "float32 elements are single channel");
         else VKX_REQUIRE(elems[i].cn == 1 || elems[i].cn == 3 || elems[i].cn == 4, "uint8 elements need 1, 3 or 4 channels");
     }
+    if (int rc = vkx_check_elems(elems, n_elems, sh, sw, dh, dw)) return rc;
     // tile kernel first (ownership in LDS, one launch for all elements); the global-ownership-plane kernels below take
     // whatever it declines (VKX_GRID_GLOBAL=1 forces them: the two paths must agree bit for bit)
     static const bool force_global = getenv("VKX_GRID_GLOBAL") != nullptr;

@@ -19,6 +19,7 @@ public:
         Plane p;
         p.in = host_in; p.out = host_out; p.row_bytes = row_bytes; p.rows = rows; p.pitch = host_pitch;
         p.off = total_;
+        if (rows > 1 && (host_pitch < 0 || (size_t)host_pitch < row_bytes)) bad_pitch_ = true;   // vkx.h: a pitch of at least one row
         total_ += (row_bytes * (size_t)(rows > 0 ? rows : 0) + 255) & ~(size_t)255;
         planes_.push_back(p);
         return (int)planes_.size() - 1;
@@ -27,6 +28,10 @@ public:
     // copy_aside: the call is asynchronous (nothing is read back): its staging copy may go to the copy stream (see below)
     int commit(bool copy_aside = false)
     {
+        if (bad_pitch_) {
+            vkx_set_error("host plane with a row pitch shorter than its row, or negative");
+            return VKX_ERR_INVALID;
+        }
         int rc = vkx_scratch_reserve(ctx_, &ctx_->stage[0], total_ ? total_ : 256);
         if (rc) return rc;
         base_ = (uint8_t *)ctx_->stage[0].ptr;
@@ -100,7 +105,7 @@ public:
     // for pageable sources, the runtime's own staging pass.  false: too large for the ring or not mappable (use commit()).
     bool commit_mapped()
     {
-        if (total_ == 0 || total_ > ((size_t)48 << 20)) return false;
+        if (bad_pitch_ || total_ == 0 || total_ > ((size_t)48 << 20)) return false;   // commit() reports a bad pitch
         for (auto &p : planes_)
             if (p.out) return false;             // outputs need device memory + finish()
         void *r = nullptr;
@@ -147,6 +152,7 @@ private:
     vkx_ctx *ctx_;
     std::vector<Plane> planes_;
     size_t total_ = 0;
+    bool bad_pitch_ = false;
     uint8_t *base_ = nullptr;
 };
 

@@ -280,6 +280,9 @@ JpegTables jpeg_tables(int quality)
 VKX_EXPORT int vkx_jpeg_roundtrip_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                          uint8_t *dst, ptrdiff_t dst_stride, int quality)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_DISJOINT(src, h, src_stride, (ptrdiff_t)w * cn, dst, h, dst_stride, (ptrdiff_t)w * cn);
     VKX_REQUIRE(ctx && src && dst, "NULL argument");
     VKX_REQUIRE(h > 0 && w > 0 && h <= (1 << 28) / 8 && w <= (1 << 28) / 8, "bad shape");
     VKX_REQUIRE(cn == 1 || cn == 3, "1 or 3 channels");

@@ -1019,6 +1019,9 @@ int check_plane(vkx_ctx *ctx, const void *src, const void *dst, int h, int w)
 VKX_EXPORT int vkx_gaussian_blur_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                         int ksize, double sigma, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_DISJOINT(src, h, src_stride, (ptrdiff_t)w * cn, dst, h, dst_stride, (ptrdiff_t)w * cn);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(src != dst, "gaussian blur cannot run in place");
@@ -1065,6 +1068,9 @@ VKX_EXPORT int vkx_gaussian_blur_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h,
 VKX_EXPORT int vkx_filter2d_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                    const float *kernel_host, int kh, int kw, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_DISJOINT(src, h, src_stride, (ptrdiff_t)w * cn, dst, h, dst_stride, (ptrdiff_t)w * cn);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(kernel_host && kh >= 1 && kw >= 1 && kh <= kF2dMaxK && kw <= kF2dMaxK, "kernel of 1..15 rows and columns");
@@ -1130,12 +1136,16 @@ static int launch_hsv(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t 
 VKX_EXPORT int vkx_color_shift_rgb_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t src_stride, int delta,
                                        uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * 3, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * 3, h);
     return launch_hsv<0>(ctx, src, h, w, src_stride, delta, dst, dst_stride);
 }
 
 VKX_EXPORT int vkx_cvt_rgb_hsv_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t src_stride, int to_hsv,
                                       uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * 3, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * 3, h);
     return to_hsv ? launch_hsv<1>(ctx, src, h, w, src_stride, 0, dst, dst_stride)
                   : launch_hsv<2>(ctx, src, h, w, src_stride, 0, dst, dst_stride);
 }
@@ -1164,6 +1174,15 @@ static int launch_cvt(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t 
 VKX_EXPORT int vkx_cvt_color_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t src_stride, int code,
                                     uint8_t *dst, ptrdiff_t dst_stride)
 {
+    {
+        // channels in / out of each code (vkx.h VKX_CVT_*); the codes that change the channel count cannot run in place
+        static const int kIn[10] = {3, 3, 3, 3, 3, 1, 4, 3, 1, 4}, kOut[10] = {3, 3, 3, 3, 1, 3, 3, 4, 4, 1};
+        VKX_REQUIRE(code >= 0 && code < 10, "unknown conversion code");
+        const ptrdiff_t in_row = (ptrdiff_t)w * kIn[code], out_row = (ptrdiff_t)w * kOut[code];
+        VKX_REQUIRE_PITCH(src_stride, in_row, h);
+        VKX_REQUIRE_PITCH(dst_stride, out_row, h);
+        if (kIn[code] != kOut[code]) VKX_REQUIRE_DISJOINT(src, h, src_stride, (size_t)in_row, dst, h, dst_stride, (size_t)out_row);
+    }
     switch (code) {
     case VKX_CVT_RGB2HLS_FULL: return launch_cvt<1>(ctx, src, h, w, src_stride, 0, 0.f, 0.f, dst, dst_stride);
     case VKX_CVT_HLS2RGB_FULL: return launch_cvt<2>(ctx, src, h, w, src_stride, 0, 0.f, 0.f, dst, dst_stride);
@@ -1198,12 +1217,16 @@ VKX_EXPORT int vkx_cvt_color_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int
 VKX_EXPORT int vkx_brightness_shift_rgb_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t src_stride, int delta,
                                             uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * 3, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * 3, h);
     return launch_cvt<0>(ctx, src, h, w, src_stride, delta, 0.f, 0.f, dst, dst_stride);
 }
 
 VKX_EXPORT int vkx_color_balance_rgb_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t src_stride, double ratio,
                                          uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * 3, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * 3, h);
     if (!(ratio >= 0.0 && ratio <= 1.0)) {
         vkx_set_error("ratio=%g is invalid.", ratio);
         return VKX_ERR_INVALID;
@@ -1214,6 +1237,9 @@ VKX_EXPORT int vkx_color_balance_rgb_dev(vkx_ctx *ctx, const uint8_t *src, int h
 VKX_EXPORT int vkx_blend_u8_dev(vkx_ctx *ctx, const uint8_t *a, ptrdiff_t a_stride, const uint8_t *b, ptrdiff_t b_stride, int h,
                                 int w, int cn, double w0, double w1, unsigned channel_mask, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(a_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(b_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, a, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(b != nullptr && cn >= 1 && cn <= 4, "bad argument");
@@ -1228,6 +1254,9 @@ VKX_EXPORT int vkx_blend_u8_dev(vkx_ctx *ctx, const uint8_t *a, ptrdiff_t a_stri
 VKX_EXPORT int vkx_fog_f32_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride, const float *weight,
                                   ptrdiff_t weight_stride_el, const float *fog /* host, cn values */, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(weight_stride_el, w, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(weight && fog && cn >= 1 && cn <= 4, "bad argument");
@@ -1245,6 +1274,8 @@ VKX_EXPORT int vkx_mean_shift_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, in
                                      int delta, int has_threshold, int threshold, int cycle, unsigned channel_mask,
                                      uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
@@ -1266,6 +1297,9 @@ VKX_EXPORT int vkx_mean_shift_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, in
 VKX_EXPORT int vkx_pointwise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride, int op,
                                     int p0, int p1, unsigned channel_mask, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
+    if (op == VKX_POINT_PERMUTE) VKX_REQUIRE_DISJOINT(src, h, src_stride, (size_t)w * cn, dst, h, dst_stride, (size_t)w * cn);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
@@ -1293,6 +1327,9 @@ VKX_EXPORT int vkx_impulse_noise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h,
                                         const uint8_t *selector, ptrdiff_t selector_stride, uint8_t *dst,
                                         ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(selector_stride, w, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(selector != nullptr, "NULL selector plane");
@@ -1318,6 +1355,9 @@ VKX_EXPORT int vkx_impulse_noise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h,
 VKX_EXPORT int vkx_speckle_noise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                         const double *noise, ptrdiff_t noise_stride_el, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(noise_stride_el, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(noise != nullptr, "NULL noise plane");
@@ -1332,6 +1372,7 @@ VKX_EXPORT int vkx_speckle_noise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h,
 VKX_EXPORT int vkx_histogram_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                     int32_t *hist)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
     VKX_REQUIRE(ctx && src && hist, "NULL argument");
     VKX_REQUIRE(h >= 0 && w >= 0, "bad shape");
     VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
@@ -1353,6 +1394,8 @@ VKX_EXPORT int vkx_histogram_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int
 VKX_EXPORT int vkx_apply_lut_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                     const uint8_t *lut_host, unsigned channel_mask, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(lut_host != nullptr, "NULL table");
@@ -1421,6 +1464,10 @@ VKX_EXPORT int vkx_gather_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int s
                                  const int32_t *pos_y, const int32_t *pos_x, ptrdiff_t pos_stride_el, uint8_t *dst, int dh,
                                  int dw, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)sw * cn, sh);
+    VKX_REQUIRE_PITCH(pos_stride_el, dw, dh);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)dw * cn, dh);
+    VKX_REQUIRE_DISJOINT(src, sh, src_stride, (size_t)sw * cn, dst, dh, dst_stride, (size_t)dw * cn);
     VKX_REQUIRE(ctx && src && pos_y && pos_x && dst, "NULL argument");
     VKX_REQUIRE(sh >= 0 && sw >= 0 && dh >= 0 && dw >= 0, "bad shape");
     VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");
@@ -1462,6 +1509,9 @@ VKX_EXPORT int vkx_saturate_i64_u8_dev(vkx_ctx *ctx, const int64_t *src, size_t 
 VKX_EXPORT int vkx_add_noise_i16_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                      const int16_t *noise, ptrdiff_t noise_stride_el, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(noise_stride_el, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     VKX_REQUIRE(noise != nullptr, "NULL noise plane");
@@ -1484,6 +1534,7 @@ VKX_EXPORT int vkx_line_streak_u8_dev(vkx_ctx *ctx, uint8_t *img, int h, int w, 
                                       int gap, int dash_thickness, int dash_gap, const uint8_t color[4], double alpha,
                                       int enable_vert, int enable_hori)
 {
+    VKX_REQUIRE_PITCH(stride, (ptrdiff_t)w * cn, h);
     int rc = check_plane(ctx, img, img, h, w);
     if (rc) return rc;
     VKX_REQUIRE(color != nullptr, "NULL color");

@@ -246,6 +246,8 @@ static int paint_sets_dev(vkx_ctx *ctx, const vkx_paint_set *sets, int n_sets, i
         const vkx_paint_set &S = sets[k];
         VKX_REQUIRE(S.n_polys >= 0 && (S.n_polys == 0 || (S.pts_host && S.poly_offsets_host)), "bad polygon list");
         VKX_REQUIRE(S.mask || S.score, "no output plane");
+        VKX_REQUIRE_PITCH(S.mask_stride, w, S.mask ? h : 1);
+        VKX_REQUIRE_PITCH(S.score_stride_el, w, S.score ? h : 1);
         VKX_REQUIRE(!S.score || S.values_host || S.n_polys == 0, "score output needs per-polygon values");
         if (S.n_polys) {
             VKX_REQUIRE(S.poly_offsets_host[S.n_polys] >= 0, "bad polygon offsets");
@@ -392,6 +394,8 @@ VKX_EXPORT int vkx_paint_polys(vkx_ctx *ctx, const int32_t *pts_host, const int3
 {
     VKX_REQUIRE(ctx && (mask || score), "NULL argument");
     VKX_REQUIRE(h > 0 && w > 0, "bad shape");
+    VKX_REQUIRE_PITCH(mask_stride, w, mask ? h : 1);
+    VKX_REQUIRE_PITCH(score_stride_el, w, score ? h : 1);
     const size_t mbytes = mask ? (((size_t)h * w + 255) & ~(size_t)255) : 0;
     const size_t sbytes = score ? (size_t)h * w * 4 : 0;
     int rc = vkx_scratch_reserve(ctx, &ctx->stage[1], mbytes + sbytes);
@@ -417,6 +421,7 @@ VKX_EXPORT int vkx_fill_poly_mask_u8_dev(vkx_ctx *ctx, const int32_t *pts_host, 
 {
     VKX_REQUIRE(ctx && pts_host && mask, "NULL argument");
     VKX_REQUIRE(npts > 0 && h > 0 && w > 0, "bad shape");
+    VKX_REQUIRE_PITCH(stride, w, h);
     std::vector<PolyEdge> edges((size_t)npts);
     long long steps = 0;
     int ymin = INT_MAX, ymax = INT_MIN;
@@ -457,6 +462,7 @@ VKX_EXPORT int vkx_fill_poly_mask_u8(vkx_ctx *ctx, const int32_t *pts_host, int 
 {
     VKX_REQUIRE(ctx && pts_host && mask, "NULL argument");
     VKX_REQUIRE(npts > 0 && h > 0 && w > 0, "bad shape");
+    VKX_REQUIRE_PITCH(stride, w, h);
     const size_t bytes = (size_t)h * w;
     int rc = vkx_scratch_reserve(ctx, &ctx->stage[1], bytes);
     if (rc) return rc;

@@ -155,6 +155,7 @@ __global__ void k_sum_pieces_walk(const uint32_t *__restrict__ pieces, int n_pie
 VKX_EXPORT int vkx_sum_f32_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride, const int32_t *channels_host,
                                   int n_sel, int sequential, float *sums_host)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
     VKX_REQUIRE(ctx && src && channels_host && sums_host, "NULL argument");
     VKX_REQUIRE(h >= 1 && w >= 1 && cn >= 1 && cn <= 4 && n_sel >= 1 && n_sel <= 4, "bad shape");
     VKX_REQUIRE((long long)h * w <= (1ll << 22), "at most 2^22 pixels (sums below 2^30)");

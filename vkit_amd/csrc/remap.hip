@@ -295,6 +295,10 @@ int launch_u8(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_
     VKX_REQUIRE(sh > 0 && sw > 0 && dh >= 0 && dw >= 0, "bad shape");
     VKX_REQUIRE(sh <= 32767 && sw <= 32767, "source larger than 32767 px (cv.remap limit)");
     if (dh == 0 || dw == 0) return VKX_OK;
+    VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");
+    VKX_REQUIRE_PITCH(sstride, (ptrdiff_t)sw * cn, sh);
+    VKX_REQUIRE_PITCH(dstride, (ptrdiff_t)dw * cn, dh);
+    VKX_REQUIRE_DISJOINT(src, sh, sstride, (size_t)sw * cn, dst, dh, dstride, (size_t)dw * cn);
     dim3 block(64, 4), grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
     switch (cn) {
     case 1: { VKX_TIMED(ctx, "k_sample_u8"); k_sample_u8<1, Coord><<<grid, block, 0, ctx->stream>>>(src, sh, sw, sstride, dst, dh, dw, dstride, coord); } break;
@@ -321,6 +325,9 @@ int launch_f32(vkx_ctx *ctx, const float *src, int sh, int sw, ptrdiff_t sstride
     VKX_REQUIRE(sh > 0 && sw > 0 && dh >= 0 && dw >= 0, "bad shape");
     VKX_REQUIRE(sh <= 32767 && sw <= 32767, "source larger than 32767 px (cv.remap limit)");
     if (dh == 0 || dw == 0) return VKX_OK;
+    VKX_REQUIRE_PITCH(sstride, sw, sh);
+    VKX_REQUIRE_PITCH(dstride, dw, dh);
+    VKX_REQUIRE_DISJOINT(src, sh, sstride * 4, (size_t)sw * 4, dst, dh, dstride * 4, (size_t)dw * 4);
     dim3 block(64, 4), grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
     { VKX_TIMED(ctx, "k_sample_f32"); k_sample_f32<Coord><<<grid, block, 0, ctx->stream>>>(src, sh, sw, sstride, dst, dh, dw, dstride, coord); }
     VKX_LAUNCH_CHECK();
@@ -381,6 +388,7 @@ VKX_EXPORT int vkx_remap_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw
                                 int dh, int dw, ptrdiff_t dst_stride)
 {
     VKX_REQUIRE(map_x && map_y, "NULL map");
+    VKX_REQUIRE_PITCH(map_stride_el, dw, dh);
     return launch_u8(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride, CoordMap{map_x, map_y, map_stride_el});
 }
 
@@ -389,6 +397,7 @@ VKX_EXPORT int vkx_remap_f32_dev(vkx_ctx *ctx, const float *src, int sh, int sw,
                                  int dw, ptrdiff_t dst_stride_el)
 {
     VKX_REQUIRE(map_x && map_y, "NULL map");
+    VKX_REQUIRE_PITCH(map_stride_el, dw, dh);
     return launch_f32(ctx, src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el,
                       CoordMap{map_x, map_y, map_stride_el});
 }
@@ -398,6 +407,8 @@ VKX_EXPORT int vkx_remap_multi_dev(vkx_ctx *ctx, const vkx_elem *elems, int n_el
 {
     VKX_REQUIRE(ctx && elems && map_x && map_y, "NULL argument");
     VKX_REQUIRE(n_elems >= 1, "no elements");
+    VKX_REQUIRE_PITCH(map_stride_el, dw, dh);
+    if (int rc = vkx_check_elems(elems, n_elems, sh, sw, dh, dw)) return rc;
     const CoordMap map{map_x, map_y, map_stride_el};
     for (int i = 0; i < n_elems; i++) {
         const vkx_elem &e = elems[i];

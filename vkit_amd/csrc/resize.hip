@@ -943,6 +943,9 @@ int resize_tables(vkx_ctx *ctx, int taps, bool fixed, int sh, int sw, int dh, in
 VKX_EXPORT int vkx_resize_cubic_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_t src_stride,
                                        uint8_t *dst, int dh, int dw, ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)sw * cn, sh);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)dw * cn, dh);
+    VKX_REQUIRE_DISJOINT(src, sh, src_stride, (size_t)sw * cn, dst, dh, dst_stride, (size_t)dw * cn);
     VKX_REQUIRE(ctx && src && dst, "NULL argument");
     VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
     VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");
@@ -970,6 +973,9 @@ VKX_EXPORT int vkx_resize_cubic_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh,
 VKX_EXPORT int vkx_resize_cubic_f32_dev(vkx_ctx *ctx, const float *src, int sh, int sw, ptrdiff_t src_stride_el,
                                         float *dst, int dh, int dw, ptrdiff_t dst_stride_el)
 {
+    VKX_REQUIRE_PITCH(src_stride_el, sw, sh);
+    VKX_REQUIRE_PITCH(dst_stride_el, dw, dh);
+    VKX_REQUIRE_DISJOINT(src, sh, src_stride_el * 4, (size_t)sw * 4, dst, dh, dst_stride_el * 4, (size_t)dw * 4);
     VKX_REQUIRE(ctx && src && dst, "NULL argument");
     VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
     const int *xofs, *yofs;
@@ -995,6 +1001,9 @@ VKX_EXPORT int vkx_resize_cubic_f32_dev(vkx_ctx *ctx, const float *src, int sh, 
 VKX_EXPORT int vkx_resize_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_t src_stride, uint8_t *dst,
                                  int dh, int dw, ptrdiff_t dst_stride, int interpolation)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)sw * cn, sh);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)dw * cn, dh);
+    VKX_REQUIRE_DISJOINT(src, sh, src_stride, (size_t)sw * cn, dst, dh, dst_stride, (size_t)dw * cn);
     if (interpolation == VKX_INTER_CUBIC) return vkx_resize_cubic_u8_dev(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride);
     VKX_REQUIRE(ctx && src && dst, "NULL argument");
     VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
@@ -1097,6 +1106,9 @@ VKX_EXPORT int vkx_resize_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int s
 VKX_EXPORT int vkx_resize_f32_dev(vkx_ctx *ctx, const float *src, int sh, int sw, ptrdiff_t src_stride_el, float *dst, int dh,
                                   int dw, ptrdiff_t dst_stride_el, int interpolation)
 {
+    VKX_REQUIRE_PITCH(src_stride_el, sw, sh);
+    VKX_REQUIRE_PITCH(dst_stride_el, dw, dh);
+    VKX_REQUIRE_DISJOINT(src, sh, src_stride_el * 4, (size_t)sw * 4, dst, dh, dst_stride_el * 4, (size_t)dw * 4);
     if (interpolation == VKX_INTER_CUBIC) return vkx_resize_cubic_f32_dev(ctx, src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el);
     VKX_REQUIRE(ctx && src && dst, "NULL argument");
     VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
@@ -1152,6 +1164,9 @@ VKX_EXPORT int vkx_zoom_in_blur_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, 
                                        const int32_t *sizes_hw_host, int n_sizes, double alpha, uint8_t *dst,
                                        ptrdiff_t dst_stride)
 {
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
+    VKX_REQUIRE_DISJOINT(src, h, src_stride, (ptrdiff_t)w * cn, dst, h, dst_stride, (ptrdiff_t)w * cn);
     VKX_REQUIRE(ctx && src && dst && (n_sizes == 0 || sizes_hw_host), "NULL argument");
     VKX_REQUIRE(h > 0 && w > 0 && n_sizes >= 0, "bad shape");
     VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");

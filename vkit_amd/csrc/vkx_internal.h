@@ -31,7 +31,42 @@ void vkx_set_error(const char *fmt, ...);
         }                                                          \
     } while (0)
 
-#define VKX_LAUNCH_CHECK()                                                   \
+// The pitch contract of vkx.h: a plane of `rows` rows of `row` units (bytes or elements, the unit of its stride) takes a
+// stride of at least one row; with a single row the stride is never used.  A negative stride fails too.
+#define VKX_REQUIRE_PITCH(stride, row, rows)                                                     \
+    VKX_REQUIRE((rows) <= 1 || (ptrdiff_t)(stride) >= (ptrdiff_t)(row),                          \
+                "row stride " #stride " shorter than a row, or negative")
+
+// Do the byte ranges [p, p + (rows - 1) * pitch + row) of two planes overlap?  Pitches in bytes, already checked by
+// VKX_REQUIRE_PITCH.
+static inline bool vkx_planes_overlap(const void *a, int a_rows, ptrdiff_t a_pitch, size_t a_row, const void *b, int b_rows,
+                                      ptrdiff_t b_pitch, size_t b_row)
+{
+    if (a_rows <= 0 || b_rows <= 0 || !a_row || !b_row) return false;
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (size_t)(a_rows - 1) * (size_t)a_pitch + a_row;
+    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + (size_t)(b_rows - 1) * (size_t)b_pitch + b_row;
+    return a0 < b1 && b0 < a1;
+}
+// for the entry points that cannot run in place
+#define VKX_REQUIRE_DISJOINT(...) \
+    VKX_REQUIRE(!vkx_planes_overlap(__VA_ARGS__), "source and destination overlap (this operation cannot run in place)")
+
+// The strides of every element of a multi-element remap ([sh, sw] -> [dh, dw]) and their source / destination overlap,
+// all checked before the first launch.
+static inline int vkx_check_elems(const vkx_elem *elems, int n_elems, int sh, int sw, int dh, int dw)
+{
+    for (int i = 0; i < n_elems; i++) {
+        const vkx_elem &e = elems[i];
+        const size_t esz = e.is_f32 ? 4 : 1, cn = e.cn > 0 ? (size_t)e.cn : 1;
+        VKX_REQUIRE_PITCH(e.src_stride, (ptrdiff_t)(sw * cn), sh);
+        VKX_REQUIRE_PITCH(e.dst_stride, (ptrdiff_t)(dw * cn), dh);
+        VKX_REQUIRE_DISJOINT(e.src, sh, e.src_stride * (ptrdiff_t)esz, sw * cn * esz, e.dst, dh, e.dst_stride * (ptrdiff_t)esz,
+                             dw * cn * esz);
+    }
+    return VKX_OK;
+}
+
+#define VKX_LAUNCH_CHECK()                                                 \
     do {                                                                     \
         hipError_t e__ = hipGetLastError();                                  \
         if (e__ != hipSuccess) {                                             \
