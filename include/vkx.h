@@ -768,6 +768,55 @@ typedef struct vkx_mls_config {
 int vkx_mls_states_dev(vkx_ctx *ctx, const vkx_mls_config *configs_host, int n, int32_t *const *src_vertices,
                        int32_t *const *dst_vertices, vkx_grid_state *states_host, int stream);
 
+/* ---- page cropping ---------------------------------------------------------------------
+ * PageCroppingStep (pipeline/text_detection/page_cropping.py:243-290) and Cropper (mechanism/cropper.py:333-376) on
+ * device-resident planes.  Every plane is DENSE (rows follow each other without gaps; the pitch is width x channels), so
+ * none of these entry points takes a stride.  The window of one crop, in page coordinates: the part of the page a crop
+ * of crop_size = core_size + 2 pad_size covers (Cropper.original_box, clipped to the page by construction) and where it
+ * lands in the crop (target_box.up / .left, mechanism/cropper.py:106-160).  The core of the crop is the square
+ * [pad_size, pad_size + core_size) of crop coordinates (target_core_box, ibid.). */
+typedef struct vkx_crop_window {
+    int32_t up, left, height, width;   /* original_box: inside the page, height and width >= 1 */
+    int32_t target_up, target_left;    /* target_box origin: the window lies inside the crop */
+} vkx_crop_window;
+
+/* The counts behind PageCroppingStep's accept / reject loop for a batch of candidate windows, in one launch:
+ *   item 0: pixels of the page image with any channel > 0 (num_samples estimate, page_cropping.py:254-262), counted when
+ *           `image` is not NULL;
+ *   item 1 + i: slot 0 = char_mask pixels > 0 inside the core of window i (text ratio, page_cropping.py:142-146),
+ *               slot 1 = active_mask pixels > 0 inside window i (active ratio, page_cropping.py:148-152).
+ * Padding adds nothing to either count, so these equal the reference's counts on the padded crop.  The result is per
+ * workgroup partial sums: partials = int64 [1 + n_windows][n_parts][2] in DEVICE memory, the caller adds up the n_parts
+ * entries of every (item, slot) -- exact integers, no atomics, no clearing pass.  `windows_host` is a HOST table.
+ * image h x w x cn (cn 1, 3 or 4), the two masks uint8 h x w, all device, dense. */
+int vkx_crop_count_dev(vkx_ctx *ctx, const uint8_t *image, int h, int w, int cn, const uint8_t *active_mask,
+                       const uint8_t *char_mask, int core_size, int pad_size, const vkx_crop_window *windows_host,
+                       int n_windows, int n_parts, int64_t *partials);
+
+/* One plane of one crop for vkx_crop_planes_dev: Cropper.crop_image / crop_mask / crop_score_map (mechanism/cropper.py:
+ * 333-376) -- the window copied, the rest of the crop filled -- and, for a core-only plane, the INTER_AREA shrink by an
+ * integer factor that PageCroppingStep applies to its labels (page_cropping.py:154-230: Mask.to_resized_mask's
+ * x255 -> cv.resize -> > 0 for masks, ScoreMap.to_resized_score_map with its [0, 1] clip for probability maps).  The
+ * shrink is the arithmetic of vkx_resize_u8 / vkx_resize_f32's integer-factor INTER_AREA path, bit for bit. */
+typedef struct vkx_crop_plane {
+    const void *src;      /* device, the page plane h x w x cn, dense */
+    void *dst;            /* device, crop_size^2 (core_only 0) or core_size^2 (core_only 1) x cn, dense */
+    void *dst_down;       /* device, (core_size / factor)^2, or NULL; core-only planes only */
+    int32_t cn;           /* uint8: 1, 3 or 4; float32: 1 */
+    int32_t is_f32;       /* 0 uint8, 1 float32 */
+    int32_t core_only;    /* 1: only the core of the crop (crop_mask / crop_score_map with core_only=True) */
+    int32_t is_mask;      /* uint8 shrink as Mask.to_resized_mask (on (v > 0) * 255, then > 0); 0: plain INTER_AREA */
+    int32_t clip;         /* float32 shrink clipped to [0, 1] (ScoreMap.is_prob) */
+    int32_t fill;         /* the value of the padding in every channel: 0 .. 255 for uint8 planes, 0 for float32 */
+    int32_t window;       /* index into the window table */
+} vkx_crop_plane;
+/* All planes of all crops in one launch.  `windows_host` and `planes_host` are HOST tables; factor 0 = no shrink, else
+ * it divides core_size and pad_size.  Refused (VKX_ERR_INVALID, nothing written) for a NULL pointer, a window outside the
+ * page or the crop, a channel count other than 1 / 3 / 4, a factor that does not divide and a destination overlapping a
+ * source. */
+int vkx_crop_planes_dev(vkx_ctx *ctx, int h, int w, int core_size, int pad_size, int factor, const vkx_crop_window *windows_host,
+                        int n_windows, const vkx_crop_plane *planes_host, int n_planes);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

@@ -202,6 +202,15 @@ class VkxNpResult(ctypes.Structure):
     ]
 
 
+class VkxCropWindow(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in ('up', 'left', 'height', 'width', 'target_up', 'target_left')]
+
+
+class VkxCropPlane(ctypes.Structure):
+    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('dst_down', c_void_p)] + [
+        (name, ctypes.c_int32) for name in ('cn', 'is_f32', 'core_only', 'is_mask', 'clip', 'fill', 'window')]
+
+
 NP_NORMAL_I16, NP_NORMAL_ADD_U8, NP_SPECKLE_U8, NP_CHOICE3_U8, NP_IMPULSE_U8, NP_NORMAL_TILES = 0, 1, 2, 3, 4, 5
 NP_AMBIGUOUS, NP_SHORT = 1, 2
 
@@ -318,6 +327,10 @@ _SIGNATURES['vkx_paint_polys_fresh_dev'] = _SIGNATURES['vkx_paint_polys_dev']
 _SIGNATURES['vkx_apply_lut_u8_planes_dev'] = [c_void_p, ctypes.POINTER(VkxLutPlane), c_int]
 _SIGNATURES['vkx_paint_poly_sets_fresh_dev'] = [c_void_p, ctypes.POINTER(VkxPaintSet), c_int, c_int, c_int]
 _SIGNATURES['vkx_fill_u8_dev_host_layers'] = [c_void_p] + _PLANE_U8 + [ctypes.POINTER(VkxLayer), c_int]
+_SIGNATURES['vkx_crop_count_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                     ctypes.POINTER(VkxCropWindow), c_int, c_int, c_void_p]
+_SIGNATURES['vkx_crop_planes_dev'] = [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(VkxCropWindow), c_int,
+                                      ctypes.POINTER(VkxCropPlane), c_int]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
@@ -2093,3 +2106,70 @@ def fill(dst, layers, ctx=None):
     if dev:
         dst.invalidate_host()
     return dst
+
+
+def _crop_window_table(windows):
+    """(up, left, height, width, target_up, target_left) per window -> vkx_crop_window [n]."""
+    table = (VkxCropWindow * max(1, len(windows)))()
+    for rec, win in zip(table, windows):
+        rec.up, rec.left, rec.height, rec.width, rec.target_up, rec.target_left = (int(v) for v in win)
+    return table
+
+
+def crop_count(image, active_mask, char_mask, windows, core_size, pad_size):
+    """The counts of PageCroppingStep's accept / reject loop (vkx_crop_count_dev) over dense DevArrays of one context:
+    -> (pixels of ``image`` with any channel > 0, or None when ``image`` is None; int64 [n] char-mask pixels > 0 in the core of
+    every window; int64 [n] active-mask pixels > 0 in every window).  ONE launch, then ONE download of the partial sums."""
+    ctx = active_mask.ctx
+    planes = [p for p in (image, active_mask, char_mask) if p is not None]
+    if not all(isinstance(p, DevArray) and p.ctx is ctx and np.dtype(p.dtype) == np.uint8 for p in planes):
+        raise ValueError('crop_count takes uint8 DevArrays of one context')
+    h, w = active_mask.shape
+    cn = 1 if image is None or image.ndim == 2 else image.shape[2]
+    crop = core_size + 2 * pad_size
+    pixels = max(h * w if image is not None else 0, crop * crop)
+    n_parts = max(1, min(256, -(-pixels // (256 * 32))))     # ~32 pixels a lane on the largest item
+    n = len(windows)
+    partials = ctx.dev_empty((1 + n, n_parts, 2), np.int64)
+    check(lib().vkx_crop_count_dev(ctx.handle, c_void_p(image.ptr) if image is not None else None, h, w, cn,
+                                   c_void_p(active_mask.ptr), c_void_p(char_mask.ptr), int(core_size), int(pad_size),
+                                   _crop_window_table(windows), n, n_parts, c_void_p(partials.ptr)))
+    sums = partials.host().sum(axis=1)
+    return (int(sums[0, 0]) if image is not None else None), sums[1:, 0].copy(), sums[1:, 1].copy()
+
+
+def crop_planes(jobs, windows, page_shape, core_size, pad_size, factor=0):
+    """Cropper.crop_image / crop_mask / crop_score_map for many planes and windows in ONE launch (vkx_crop_planes_dev).
+    ``jobs``: dicts with ``src`` (a dense DevArray page plane; every source of one context), ``window`` (index into ``windows``),
+    and optionally ``core_only``, ``down`` (also the INTER_AREA shrink by ``factor``), ``is_mask``, ``clip``, ``fill``.
+    -> [(cropped DevArray, shrunk DevArray or None)] in the order of ``jobs``."""
+    n = len(jobs)
+    if n == 0:
+        return []
+    ctx = jobs[0]['src'].ctx
+    h, w = page_shape
+    crop = core_size + 2 * pad_size
+    table = (VkxCropPlane * n)()
+    outs = []
+    for rec, job in zip(table, jobs):
+        src = job['src']
+        if not isinstance(src, DevArray) or src.ctx is not ctx:
+            raise ValueError('crop_planes takes DevArrays of one context')
+        if tuple(src.shape[:2]) != (h, w):
+            raise ValueError(f'plane of shape {src.shape} on a page of shape {(h, w)}')
+        is_f32 = np.dtype(src.dtype) == np.float32
+        cn = src.shape[2] if src.ndim == 3 else 1
+        side = core_size if job.get('core_only') else crop
+        dst = ctx.dev_empty((side, side) + tuple(src.shape[2:]), src.dtype)
+        down = None
+        if job.get('down'):
+            small = core_size // factor
+            down = ctx.dev_empty((small, small) + tuple(src.shape[2:]), src.dtype)
+        rec.src, rec.dst, rec.dst_down = src.ptr, dst.ptr, (down.ptr if down is not None else None)
+        rec.cn, rec.is_f32, rec.core_only = cn, int(is_f32), int(bool(job.get('core_only')))
+        rec.is_mask, rec.clip, rec.fill = int(bool(job.get('is_mask'))), int(bool(job.get('clip'))), int(job.get('fill', 0))
+        rec.window = int(job['window'])
+        outs.append((dst, down))
+    check(lib().vkx_crop_planes_dev(ctx.handle, h, w, int(core_size), int(pad_size), int(factor), _crop_window_table(windows),
+                                    len(windows), table, n))
+    return outs

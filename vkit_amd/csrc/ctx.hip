@@ -98,6 +98,8 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->camera_work);
     scratch_release(&ctx->mls_work);
     scratch_release(&ctx->fog_work);
+    scratch_release(&ctx->crop_windows);
+    scratch_release(&ctx->crop_planes);
     scratch_release(&ctx->glass_win);
     scratch_release(&ctx->jpeg_planes);
     scratch_release(&ctx->pz_tabs);

@@ -436,7 +436,7 @@ __global__ void __launch_bounds__(256) k_resize_linear_f32(const float *__restri
     dst[(ptrdiff_t)dy * dstride + dx] = t0 + t1;
 }
 
-// INTER_AREA, integer scale factors (ResizeAreaFast): box sums, then * (1.f / area)
+// INTER_AREA, integer scale factors (ResizeAreaFast): box sums, then * (1.f / area) (vkd::area_fast_*)
 template <int CN, bool F32>
 __global__ void __launch_bounds__(256) k_resize_area_fast(const void *__restrict__ src_, ptrdiff_t sstride, void *__restrict__ dst_,
                                                           int dh, int dw, ptrdiff_t dstride, int isx, int isy)
@@ -444,39 +444,16 @@ __global__ void __launch_bounds__(256) k_resize_area_fast(const void *__restrict
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= dw || dy >= dh) return;
-    const int area = isx * isy;
-    const float scale = 1.f / area;
     if (F32) {
         const float *S = (const float *)src_ + (ptrdiff_t)(dy * isy) * sstride + (ptrdiff_t)(dx * isx);
-        if (isx == 2 && isy == 2) {          // the vector body of the 2 x 2 case pairs the rows
-            const float top = S[0] + S[1], bottom = S[sstride] + S[sstride + 1];
-            const float s4 = top + bottom;
-            ((float *)dst_)[(ptrdiff_t)dy * dstride + dx] = s4 * 0.25f;
-            return;
-        }
-        float sum = 0;
-        int k = 0;
-        for (; k <= area - 4; k += 4) {      // the reference sums the row-major box four samples at a time
-            const float a0 = S[(k / isx) * sstride + (k % isx)], a1 = S[((k + 1) / isx) * sstride + ((k + 1) % isx)];
-            const float a2 = S[((k + 2) / isx) * sstride + ((k + 2) % isx)], a3 = S[((k + 3) / isx) * sstride + ((k + 3) % isx)];
-            float g = a0 + a1;
-            g = g + a2;
-            g = g + a3;
-            sum = sum + g;
-        }
-        for (; k < area; k++) sum = sum + S[(k / isx) * sstride + (k % isx)];
-        ((float *)dst_)[(ptrdiff_t)dy * dstride + dx] = sum * scale;
+        ((float *)dst_)[(ptrdiff_t)dy * dstride + dx] =
+            vkd::area_fast_f32([&](int y, int x) { return S[(ptrdiff_t)y * sstride + x]; }, isx, isy);
     } else {
         const uint8_t *S = (const uint8_t *)src_ + (ptrdiff_t)(dy * isy) * sstride + (ptrdiff_t)(dx * isx) * CN;
         uint8_t *out = (uint8_t *)dst_ + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN;
 #pragma unroll
-        for (int c = 0; c < CN; c++) {
-            int sum = 0;
-            for (int y = 0; y < isy; y++)
-                for (int x = 0; x < isx; x++) sum += S[(ptrdiff_t)y * sstride + x * CN + c];
-            const int r = (isx == 2 && isy == 2) ? (sum + 2) >> 2 : vkd::cv_round((float)sum * scale);
-            out[c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-        }
+        for (int c = 0; c < CN; c++)
+            out[c] = vkd::area_fast_u8([&](int y, int x) { return (int)S[(ptrdiff_t)y * sstride + x * CN + c]; }, isx, isy);
     }
 }
 

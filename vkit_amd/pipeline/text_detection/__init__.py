@@ -15,3 +15,12 @@ from .page_resizing import (  # noqa: F401
     PageResizingStepOutput,
     page_resizing_step_factory,
 )
+from .page_cropping import (  # noqa: F401
+    CroppedPage,
+    DownsampledLabel,
+    PageCroppingStep,
+    PageCroppingStepConfig,
+    PageCroppingStepInput,
+    PageCroppingStepOutput,
+    page_cropping_step_factory,
+)
