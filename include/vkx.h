@@ -41,6 +41,7 @@ extern "C" {
 #define VKX_ERR_UNSUPPORTED (-4)
 #define VKX_ERR_OUT_OF_LATTICE (-5) /* a point falls outside the lattice cells (the reference raises IndexError there) */
 #define VKX_ERR_DIVIDE (-6)         /* a division by zero the reference raises FloatingPointError for */
+#define VKX_ERR_CHAR_MASK (-7)      /* a char the reference raises for (vkx_char_set.boxes_host has its status) */
 
 typedef struct vkx_ctx vkx_ctx;
 
@@ -816,6 +817,44 @@ typedef struct vkx_crop_plane {
  * source. */
 int vkx_crop_planes_dev(vkx_ctx *ctx, int h, int w, int core_size, int pad_size, int factor, const vkx_crop_window *windows_host,
                         int n_windows, const vkx_crop_plane *planes_host, int n_planes);
+
+/* ---- the external_ellipse char-mask engine (engine/char_mask/external_ellipse.py:104-220) ------------------------------
+ * Per char (4 points, smooth float64 (x, y)) and internal side length L (1 .. 2048): R = ceil(L / sqrt 2), E = 2 R + 1, the
+ * template build_np_distance(R) <= R (engine/char_heatmap/default.py:30-40); H1 = getPerspectiveTransform(char square
+ * [pad, pad + L - 1]^2, pad = (E - L) // 2 -> the polygon's float32 self-relative points) with the project's DECOMP_SVD
+ * definition (closed form, Jacobi SVD for degenerate quads); the 4 corners of [0, E - 1]^2 through H1 as affine_np_points
+ * computes them (numpy's matmul: fma(h2, 1, fma(h1, y, h0 x)), then / w); their min x / y subtracted, cast to float32;
+ * H2 = getPerspectiveTransform(external corners -> those); warpPerspective(template, H2, (ceil(x max), ceil(y max)))
+ * INTER_LINEAR, BORDER_CONSTANT 0 (a zero side: the template's size, as cv2); placed at round(min smooth y / x + offset)
+ * (halves to even) and trimmed against the page or the char's bounding box (:156-200).  A sample != 0 covers its pixel:
+ * mask = 1 there (:218), and score = the value of the LAST char of the set covering the pixel (PageDistortionStep's height
+ * map, pipeline/text_detection/page_distortion.py:276-287); every other pixel of both planes is 0.  char_masks, when given,
+ * receives every char's trimmed warped template (the reference's char_masks[i].mat), row-major, one after the other in
+ * char order.
+ * Status per char in boxes_host [n_chars, 5] = (up, down, left, right, status): 0 placed (the trimmed box); 1 the box and
+ * the trimmed template differ in shape (the reference raises RuntimeError: the disc lies outside the page / box); 2 an
+ * empty box (AssertionError in Box.extract_np_array: the quad collapses); 3 a NaN size (ValueError in math.ceil); 4 an
+ * infinite or larger than 2^30 size or position (OverflowError).  When any char has a non-zero status the call returns
+ * VKX_ERR_CHAR_MASK after filling boxes_host and writes no plane.
+ * One call: the sets of one page (up to 8), three launches and one synchronisation (the boxes).  Planes are dense.  Refused
+ * (VKX_ERR_INVALID, nothing written) before any launch for L outside 1 .. 2048, a polygon without exactly 4 points, a
+ * non-finite point, a bounding box outside the page, a score plane without values and overlapping output planes; a
+ * char_masks_cap below the packed size is refused after the boxes are known (boxes_host filled, no plane written). */
+typedef struct vkx_char_set {
+    const double *pts_host;           /* HOST float64 [total_pts, 2] (x, y) */
+    const int32_t *poly_offsets_host; /* HOST int32 [n_chars + 1]: 4 points each */
+    int32_t n_chars;
+    const int32_t *bounds_host;       /* HOST int32 [n_chars, 4] (up, down, left, right) inside the page, or NULL: the page */
+    const float *values_host;         /* HOST float32 [n_chars]; required with score */
+    uint8_t *mask;                    /* [h, w] or NULL */
+    float *score;                     /* [h, w] or NULL */
+    uint8_t *char_masks;              /* the packed per-char masks, or NULL */
+    int64_t char_masks_cap;           /* bytes of char_masks */
+    int32_t *boxes_host;              /* HOST int32 [n_chars, 5] out */
+} vkx_char_set;
+/* _dev: mask / score / char_masks in device memory.  The host form: in host memory, returns after the copies back. */
+int vkx_char_mask_ellipse_sets_fresh_dev(vkx_ctx *ctx, int internal_side_length, const vkx_char_set *sets, int n_sets, int h, int w);
+int vkx_char_mask_ellipse_sets_fresh(vkx_ctx *ctx, int internal_side_length, const vkx_char_set *sets, int n_sets, int h, int w);
 
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx

@@ -29,7 +29,7 @@ class VkxError(RuntimeError):
 
 
 # error codes of include/vkx.h
-ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_OUT_OF_LATTICE, ERR_DIVIDE = -1, -2, -3, -4, -5, -6
+ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_OUT_OF_LATTICE, ERR_DIVIDE, ERR_CHAR_MASK = -1, -2, -3, -4, -5, -6, -7
 
 
 class VkxElem(ctypes.Structure):
@@ -90,6 +90,21 @@ class VkxPaintSet(ctypes.Structure):
         ('mask_stride', c_ssize),
         ('score', c_void_p),
         ('score_stride_el', c_ssize),
+    ]
+
+
+class VkxCharSet(ctypes.Structure):
+    _fields_ = [
+        ('pts_host', c_void_p),
+        ('poly_offsets_host', c_void_p),
+        ('n_chars', ctypes.c_int32),
+        ('bounds_host', c_void_p),
+        ('values_host', c_void_p),
+        ('mask', c_void_p),
+        ('score', c_void_p),
+        ('char_masks', c_void_p),
+        ('char_masks_cap', ctypes.c_int64),
+        ('boxes_host', c_void_p),
     ]
 
 
@@ -331,6 +346,8 @@ _SIGNATURES['vkx_crop_count_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_
                                      ctypes.POINTER(VkxCropWindow), c_int, c_int, c_void_p]
 _SIGNATURES['vkx_crop_planes_dev'] = [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(VkxCropWindow), c_int,
                                       ctypes.POINTER(VkxCropPlane), c_int]
+_SIGNATURES['vkx_char_mask_ellipse_sets_fresh_dev'] = [c_void_p, c_int, ctypes.POINTER(VkxCharSet), c_int, c_int, c_int]
+_SIGNATURES['vkx_char_mask_ellipse_sets_fresh'] = [c_void_p, c_int, ctypes.POINTER(VkxCharSet), c_int, c_int, c_int]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
@@ -2173,3 +2190,96 @@ def crop_planes(jobs, windows, page_shape, core_size, pad_size, factor=0):
     check(lib().vkx_crop_planes_dev(ctx.handle, h, w, int(core_size), int(pad_size), int(factor), _crop_window_table(windows),
                                     len(windows), table, n))
     return outs
+
+
+class CharMaskSet:
+    """One char set of ``char_mask_ellipse_sets``: ``quads`` float64 (N, 4, 2) smooth (x, y) in paint order, optional
+    ``bounds`` int (N, 4) (up, down, left, right) and ``values`` float32 (N) (with a score plane), the fresh output planes
+    (``mask`` uint8 / ``score`` float32 of the page's shape, DevArrays or numpy arrays as the call's form) and
+    ``want_char_masks``.  After the call ``boxes`` holds int32 (N, 5) (up, down, left, right, status) and, when asked for,
+    ``char_masks`` the packed per-char masks (a uint8 numpy buffer, char i at the prefix sum of the box areas)."""
+
+    def __init__(self, quads, bounds=None, values=None, mask=None, score=None, want_char_masks=False):
+        self.quads = np.ascontiguousarray(np.asarray(quads, dtype=np.float64).reshape(-1, 2))
+        if self.quads.shape[0] % 4:
+            raise ValueError('four points per char')
+        self.n = self.quads.shape[0] // 4
+        self.offsets = np.arange(0, 4 * self.n + 1, 4, dtype=np.int32)
+        self.bounds = None if bounds is None else np.ascontiguousarray(np.asarray(bounds, dtype=np.int32).reshape(self.n, 4))
+        self.values = None if values is None else np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(self.n))
+        self.mask, self.score, self.want_char_masks = mask, score, want_char_masks
+        self.boxes = np.full((self.n, 5), -1, np.int32)
+        self.char_masks = None
+
+    def packed_size(self):
+        b = self.boxes.astype(np.int64)
+        return int(((b[:, 1] - b[:, 0] + 1) * (b[:, 3] - b[:, 2] + 1)).sum())
+
+
+def char_mask_ellipse_sets(internal_side_length, sets, shape, ctx=None):
+    """The external_ellipse char masks of several char sets of one page in ONE call (vkx_char_mask_ellipse_sets_fresh_dev
+    for DevArray planes, the host form for numpy planes).  Returns True when every char was placed; False when a char makes
+    the reference raise (``boxes[:, 4]`` says which and why) -- then no plane was written.  The packed per-char masks are
+    downloaded into ``CharMaskSet.char_masks``; their size is known once the boxes are, so the first call sizes the buffer by
+    an estimate and a call that finds it short is repeated once with the exact size."""
+    h, w = shape
+    planes = [p for s in sets for p in (s.mask, s.score) if p is not None]
+    on_device = bool(planes) and isinstance(planes[0], DevArray)
+    for p, dt in ((p, dt) for s in sets for p, dt in ((s.mask, np.uint8), (s.score, np.float32)) if p is not None):
+        if isinstance(p, DevArray) != on_device or np.dtype(p.dtype) != dt or tuple(p.shape) != (h, w):
+            raise ValueError(f'planes must be {(h, w)} arrays of one kind (uint8 mask, float32 score)')
+        if not on_device and not p.flags.c_contiguous:
+            raise ValueError('dense planes')
+    if on_device:
+        ctx = ctx or planes[0].ctx
+        if any(p.ctx is not ctx for p in planes):
+            raise ValueError('the planes of one call live on one context')
+    ctx = ctx or default_ctx()
+    # first guess of the packed size: the external disc's box is about 2x the quad's box; a short guess costs one more call
+    caps = []
+    for s in sets:
+        if s.want_char_masks and s.n:
+            q = s.quads.reshape(-1, 4, 2)
+            ext = (q.max(axis=1) - q.min(axis=1)) * 1.5 + 4
+            caps.append(int(np.minimum(ext[:, 0] * ext[:, 1], h * w).sum()) + 64)
+        else:
+            caps.append(0)
+    for attempt in range(2):
+        arr = (VkxCharSet * len(sets))()
+        bufs = []
+        for k, s in enumerate(sets):
+            rec = arr[k]
+            rec.pts_host, rec.poly_offsets_host, rec.n_chars = s.quads.ctypes.data, s.offsets.ctypes.data, s.n
+            rec.bounds_host = s.bounds.ctypes.data if s.bounds is not None else None
+            if s.score is not None:
+                if s.values is None or s.values.shape != (s.n,):
+                    raise ValueError('one value per char is required with a score plane')
+                rec.values_host = s.values.ctypes.data
+            rec.mask = (s.mask.ptr if on_device else s.mask.ctypes.data) if s.mask is not None else None
+            rec.score = (s.score.ptr if on_device else s.score.ctypes.data) if s.score is not None else None
+            buf = None
+            if s.want_char_masks:
+                buf = ctx.dev_empty((max(caps[k], 1),), np.uint8) if on_device else np.empty(max(caps[k], 1), np.uint8)
+                rec.char_masks = buf.ptr if on_device else buf.ctypes.data
+                rec.char_masks_cap = caps[k]
+            bufs.append(buf)
+            s.boxes[:] = -1
+            rec.boxes_host = s.boxes.ctypes.data
+        fn = lib().vkx_char_mask_ellipse_sets_fresh_dev if on_device else lib().vkx_char_mask_ellipse_sets_fresh
+        rc = fn(ctx.handle, int(internal_side_length), arr, len(sets), h, w)
+        if rc == ERR_CHAR_MASK:
+            return False
+        short = [k for k, s in enumerate(sets) if s.want_char_masks and (s.boxes[:, 4] == 0).all() and s.packed_size() > caps[k]]
+        if rc == ERR_INVALID and attempt == 0 and short and all((s.boxes[:, 4] == 0).all() for s in sets):
+            for k in short:
+                caps[k] = sets[k].packed_size()
+            continue
+        check(rc)
+        break
+    for s, buf in zip(sets, bufs):
+        for plane in (s.mask, s.score):
+            if on_device and plane is not None:
+                plane.invalidate_host()
+        if buf is not None:
+            s.char_masks = buf.host() if on_device else buf
+    return True

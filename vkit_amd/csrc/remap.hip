@@ -59,29 +59,7 @@ struct CoordAffine {   // warpAffine: inverse matrix, AB_BITS = 10 fixed point
     }
 };
 
-struct CoordPerspective { // warpPerspective: inverse matrix, per pixel in double, 32x32 blocks
-    static constexpr bool kTile2D = true;
-    double m[9];
-    int bw0;
-    struct Column {};
-    struct Rows {};
-    __device__ __forceinline__ Column column(int) const { return Column(); }
-    __device__ __forceinline__ Rows rows(int, int) const { return Rows(); }
-    __device__ __forceinline__ void at(const Column &, const Rows &, int, int x, int y, int &X, int &Y) const { (*this)(x, y, X, Y); }
-    __device__ __forceinline__ void operator()(int x, int y, int &X, int &Y) const
-    {
-        const int xb = (x / bw0) * bw0, x1 = x - xb;
-        const double X0 = m[0] * xb + m[1] * y + m[2];
-        const double Y0 = m[3] * xb + m[4] * y + m[5];
-        const double W0 = m[6] * xb + m[7] * y + m[8];
-        double W = W0 + m[6] * x1;
-        W = W ? 32 / W : 0;
-        const double fX = fmax((double)INT_MIN, fmin((double)INT_MAX, (X0 + m[0] * x1) * W));
-        const double fY = fmax((double)INT_MIN, fmin((double)INT_MAX, (Y0 + m[3] * x1) * W));
-        X = vkd::cv_round(fX);
-        Y = vkd::cv_round(fY);
-    }
-};
+using vkd::CoordPerspective;   // vkx_internal.h: shared with the char-mask raster (char_mask.hip)
 
 typedef unsigned long long u64_u1 __attribute__((aligned(1)));
 typedef uint32_t u32_u1 __attribute__((aligned(1)));
@@ -354,33 +332,6 @@ CoordAffine make_affine(const double Mf[6])
 
 // cv::invert of a 3x3 double matrix (cofactors times 1/det; zeros when singular) and the block width of
 // WarpPerspectiveInvoker.
-CoordPerspective make_perspective(const double S[9], int dh, int dw)
-{
-    CoordPerspective c;
-    auto at = [&](int r, int col) { return S[r * 3 + col]; };
-    double d = at(0, 0) * (at(1, 1) * at(2, 2) - at(1, 2) * at(2, 1)) -
-               at(0, 1) * (at(1, 0) * at(2, 2) - at(1, 2) * at(2, 0)) +
-               at(0, 2) * (at(1, 0) * at(2, 1) - at(1, 1) * at(2, 0));
-    if (d == 0.) {
-        for (int i = 0; i < 9; i++) c.m[i] = 0;
-    } else {
-        d = 1. / d;
-        c.m[0] = (at(1, 1) * at(2, 2) - at(1, 2) * at(2, 1)) * d;
-        c.m[1] = (at(0, 2) * at(2, 1) - at(0, 1) * at(2, 2)) * d;
-        c.m[2] = (at(0, 1) * at(1, 2) - at(0, 2) * at(1, 1)) * d;
-        c.m[3] = (at(1, 2) * at(2, 0) - at(1, 0) * at(2, 2)) * d;
-        c.m[4] = (at(0, 0) * at(2, 2) - at(0, 2) * at(2, 0)) * d;
-        c.m[5] = (at(0, 2) * at(1, 0) - at(0, 0) * at(1, 2)) * d;
-        c.m[6] = (at(1, 0) * at(2, 1) - at(1, 1) * at(2, 0)) * d;
-        c.m[7] = (at(0, 1) * at(2, 0) - at(0, 0) * at(2, 1)) * d;
-        c.m[8] = (at(0, 0) * at(1, 1) - at(0, 1) * at(1, 0)) * d;
-    }
-    const int BLOCK_SZ = 32;
-    const int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : (dh > 0 ? dh : 1);
-    c.bw0 = BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : (dw > 0 ? dw : 1);
-    return c;
-}
-
 } // namespace
 
 VKX_EXPORT int vkx_remap_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_t src_stride,
@@ -444,12 +395,12 @@ VKX_EXPORT int vkx_warp_perspective_u8_dev(vkx_ctx *ctx, const uint8_t *src, int
                                            ptrdiff_t dst_stride)
 {
     VKX_REQUIRE(M != nullptr, "NULL matrix");
-    return launch_u8(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride, make_perspective(M, dh, dw));
+    return launch_u8(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride, vkd::make_perspective(M, dh, dw));
 }
 
 VKX_EXPORT int vkx_warp_perspective_f32_dev(vkx_ctx *ctx, const float *src, int sh, int sw, ptrdiff_t src_stride_el,
                                             const double M[9], float *dst, int dh, int dw, ptrdiff_t dst_stride_el)
 {
     VKX_REQUIRE(M != nullptr, "NULL matrix");
-    return launch_f32(ctx, src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el, make_perspective(M, dh, dw));
+    return launch_f32(ctx, src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el, vkd::make_perspective(M, dh, dw));
 }

@@ -111,6 +111,10 @@ struct vkx_ctx {
     vkx_scratch fog_work;                     // fog field (fog.hip): raw draws + the float64 centres of a level; a glass round's temporaries
     vkx_scratch jpeg_planes;                  // jpeg round trip (jpeg.hip): the decoded Y, Cb, Cr planes at their padded sizes
     vkx_scratch crop_windows, crop_planes;      // page cropping (crop.hip): the window and plane tables of the last call
+    vkx_scratch char_table, char_geo, char_layout, char_host;   // char masks (char_mask.hip): chars, setup results, tile layout,
+                                                                // staging of the host form
+    vkx_scratch char_owner;                   // ... the ownership planes: all zero between calls (the resolve clears what it reads)
+    size_t char_owner_zeroed = 0;             // ... bytes of it known to be zero
     vkx_scratch glass_win;                    // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows
     bool pz_tabs_ready = false;
@@ -311,6 +315,62 @@ __device__ __forceinline__ float area_fast_f32(At at, int isx, int isy)
     }
     for (; k < area; k++) sum = sum + at(k / isx, k % isx);
     return sum * (1.f / area);
+}
+
+// cv.warpPerspective's source coordinate of destination pixel (x, y) in 1/32 px (imgwarp.cpp WarpPerspectiveInvoker): the
+// inverse matrix evaluated in double per pixel, with the x terms of a row restarted at the start of every bw0-wide block.
+// Shared by the warp kernels of remap.hip and the char-mask raster of char_mask.hip.
+struct CoordPerspective { // warpPerspective: inverse matrix, per pixel in double, 32x32 blocks
+    static constexpr bool kTile2D = true;
+    double m[9];
+    int bw0;
+    struct Column {};
+    struct Rows {};
+    __device__ __forceinline__ Column column(int) const { return Column(); }
+    __device__ __forceinline__ Rows rows(int, int) const { return Rows(); }
+    __device__ __forceinline__ void at(const Column &, const Rows &, int, int x, int y, int &X, int &Y) const { (*this)(x, y, X, Y); }
+    __device__ __forceinline__ void operator()(int x, int y, int &X, int &Y) const
+    {
+        const int xb = (x / bw0) * bw0, x1 = x - xb;
+        const double X0 = m[0] * xb + m[1] * y + m[2];
+        const double Y0 = m[3] * xb + m[4] * y + m[5];
+        const double W0 = m[6] * xb + m[7] * y + m[8];
+        double W = W0 + m[6] * x1;
+        W = W ? 32 / W : 0;
+        const double fX = fmax((double)INT_MIN, fmin((double)INT_MAX, (X0 + m[0] * x1) * W));
+        const double fY = fmax((double)INT_MIN, fmin((double)INT_MAX, (Y0 + m[3] * x1) * W));
+        X = vkd::cv_round(fX);
+        Y = vkd::cv_round(fY);
+    }
+};
+
+// The CoordPerspective of cv.warpPerspective(src, S, (dw, dh)) (no WARP_INVERSE_MAP: S inverted here, a singular S gives
+// the zero matrix as cv::invert does).
+__host__ __device__ inline CoordPerspective make_perspective(const double S[9], int dh, int dw)
+{
+    CoordPerspective c;
+    auto at = [&](int r, int col) { return S[r * 3 + col]; };
+    double d = at(0, 0) * (at(1, 1) * at(2, 2) - at(1, 2) * at(2, 1)) -
+               at(0, 1) * (at(1, 0) * at(2, 2) - at(1, 2) * at(2, 0)) +
+               at(0, 2) * (at(1, 0) * at(2, 1) - at(1, 1) * at(2, 0));
+    if (d == 0.) {
+        for (int i = 0; i < 9; i++) c.m[i] = 0;
+    } else {
+        d = 1. / d;
+        c.m[0] = (at(1, 1) * at(2, 2) - at(1, 2) * at(2, 1)) * d;
+        c.m[1] = (at(0, 2) * at(2, 1) - at(0, 1) * at(2, 2)) * d;
+        c.m[2] = (at(0, 1) * at(1, 2) - at(0, 2) * at(1, 1)) * d;
+        c.m[3] = (at(1, 2) * at(2, 0) - at(1, 0) * at(2, 2)) * d;
+        c.m[4] = (at(0, 0) * at(2, 2) - at(0, 2) * at(2, 0)) * d;
+        c.m[5] = (at(0, 2) * at(1, 0) - at(0, 0) * at(1, 2)) * d;
+        c.m[6] = (at(1, 0) * at(2, 1) - at(1, 1) * at(2, 0)) * d;
+        c.m[7] = (at(0, 1) * at(2, 0) - at(0, 0) * at(2, 1)) * d;
+        c.m[8] = (at(0, 0) * at(1, 1) - at(0, 1) * at(1, 0)) * d;
+    }
+    const int BLOCK_SZ = 32;
+    const int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : (dh > 0 ? dh : 1);
+    c.bw0 = BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : (dw > 0 ? dw : 1);
+    return c;
 }
 
 } // namespace vkd

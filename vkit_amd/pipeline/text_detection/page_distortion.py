@@ -8,8 +8,10 @@ layer image, unflatten, rasterise the labels.
 MI355X shape: the image / mask pair goes through the shared-grid device pass of each geometric operator; the
 labels (hundreds to thousands of polygons per page) are painted by ``vkx_paint_polys`` -- one ordered
 ownership raster per label plane pair instead of one fillPoly + boolean-index assignment per polygon.  The
-painter / debug image branches and the pluggable char-mask engines are outside the path (the default engine,
-"every char polygon, keep max", is what is implemented; reference engine/char_mask/default.py:44-53).
+painter / debug image branches are outside the path.  The char-mask engine comes from ``char_mask_engine_config``: the
+default engine ("every char polygon, keep max", reference engine/char_mask/default.py:44-53) is the polygon paint, and
+external_ellipse (vkit_amd/engine/char_mask/) paints the char mask, the seal-impression char mask and the char height map
+with one vkx_char_mask_ellipse_sets_fresh_dev call.
 """
 import itertools
 from typing import Any, Generic, List, Mapping, Optional, Sequence, Tuple, TypeVar, Union
@@ -19,6 +21,8 @@ import numpy as np
 from numpy.random import Generator as RandomGenerator
 
 from vkit_amd import _native
+from vkit_amd.engine.char_mask import CharMaskExternalEllipseEngine, char_mask_engine_executor_aggregator_factory
+from vkit_amd.engine.char_mask.external_ellipse import char_quads, new_planes, raise_for_statuses
 from vkit_amd.element import Image, Mask, Point, PointArray, PointList, Polygon, PolygonSoup, ScoreMap
 from vkit_amd.mechanism.distortion_policy import RandomDistortionDebug, random_distortion_factory
 from vkit_amd.utility import PathType
@@ -215,9 +219,8 @@ class PageDistortionStep(PipelineStep[PageDistortionStepConfig, PageDistortionSt
     def __init__(self, config: PageDistortionStepConfig):
         super().__init__(config)
         self.random_distortion = random_distortion_factory.create(self.config.random_distortion_factory_config)
-        engine_type = dict(self.config.char_mask_engine_config).get('type', 'default')
-        if engine_type != 'default':
-            raise NotImplementedError(f'char mask engine "{engine_type}" is outside the accelerated path')
+        self.char_mask_engine_executor = char_mask_engine_executor_aggregator_factory.create_engine_executor(
+            dict(self.config.char_mask_engine_config))
         for flag in ('enable_debug_distorted_char_heights', 'enable_debug_distorted_text_line_heights'):
             if getattr(self.config, flag):
                 raise NotImplementedError(f'{flag}: the painter is outside the accelerated path')
@@ -259,6 +262,9 @@ class PageDistortionStep(PipelineStep[PageDistortionStepConfig, PageDistortionSt
                                 seal_impression_char_polygons: Sequence[Polygon],
                                 char_height_points_up: PointList, char_height_points_down: PointList,
                                 _paint_queue: Optional[_PaintQueue] = None):
+        if isinstance(self.char_mask_engine_executor.engine, CharMaskExternalEllipseEngine):
+            return self._generate_ellipse_char_labelings(distorted_image, char_polygons, seal_impression_char_polygons,
+                                                         char_height_points_up, char_height_points_down, _paint_queue)
         char_mask: Optional[Mask] = None
         if self.config.enable_distorted_char_mask:
             # default engine: every polygon.fill_mask(mask, keep_max_value=True) with value 1 == union
@@ -280,6 +286,45 @@ class PageDistortionStep(PipelineStep[PageDistortionStepConfig, PageDistortionSt
                        else [char_polygons[idx] for idx in order])
             _, char_height_score_map = paint_polygons(
                 distorted_image.shape, ordered, values=[char_heights[idx] for idx in order], want_mask=False, queue=_paint_queue)
+        return char_mask, seal_impression_char_mask, char_height_score_map, char_heights, None
+
+    def _generate_ellipse_char_labelings(self, distorted_image: Image, char_polygons, seal_impression_char_polygons,
+                                         char_height_points_up: PointList, char_height_points_down: PointList,
+                                         _paint_queue: Optional[_PaintQueue]):
+        """generate_char_labelings with the external_ellipse engine (reference :225-300): the char mask, the seal-impression
+        char mask and -- when the char mask is on, since the reference fills the height map through the engine's char_masks
+        only then -- the char height map, as the sets of ONE vkx_char_mask_ellipse_sets_fresh_dev call."""
+        shape = distorted_image.shape
+        side = self.char_mask_engine_executor.engine.init_config.internal_side_length
+        sets, planes = [], {}
+        if self.config.enable_distorted_char_mask:
+            mask, _ = new_planes(shape, True, False)
+            sets.append(_native.CharMaskSet(char_quads(char_polygons), mask=mask))
+            planes['char'] = mask
+        if self.config.enable_distorted_seal_impression_char_mask:
+            mask, _ = new_planes(shape, True, False)
+            sets.append(_native.CharMaskSet(char_quads(seal_impression_char_polygons), mask=mask))
+            planes['seal'] = mask
+        char_height_score_map: Optional[ScoreMap] = None
+        char_heights: Optional[List[float]] = None
+        if self.config.enable_distorted_char_height_score_map:
+            np_heights = _heights(char_height_points_up, char_height_points_down)
+            # Large heights first, so that the small height survives where two char boxes overlap (reference :270-273)
+            order = np.asarray(tuple(reversed(np_heights.argsort())), dtype=np.int64)
+            char_heights = [float(v) for v in np_heights]
+            if self.config.enable_distorted_char_mask:
+                _, score = new_planes(shape, False, True)
+                sets.append(_native.CharMaskSet(char_quads(char_polygons)[order], values=np_heights[order], score=score))
+                char_height_score_map = ScoreMap(mat=score, is_prob=False)
+            else:
+                ordered = (char_polygons.reordered(order) if isinstance(char_polygons, PolygonSoup)
+                           else [char_polygons[idx] for idx in order])
+                _, char_height_score_map = paint_polygons(
+                    shape, ordered, values=[char_heights[idx] for idx in order], want_mask=False, queue=_paint_queue)
+        if sets and not _native.char_mask_ellipse_sets(side, sets, shape):
+            raise_for_statuses(sets)
+        char_mask = Mask(mat=planes['char']) if 'char' in planes else None
+        seal_impression_char_mask = Mask(mat=planes['seal']) if 'seal' in planes else None
         return char_mask, seal_impression_char_mask, char_height_score_map, char_heights, None
 
     def run(self, input: PageDistortionStepInput, rng: RandomGenerator):
