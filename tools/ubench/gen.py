@@ -106,6 +106,23 @@ T = [
     ('v_pk_lshrrev_b16', 'v_pk_lshrrev_b16 {d}, 3, {d}', '32'),
     ('v_fma_f32_x2_independent', 'v_fma_f32 {d}, {a}, {b}, {d}', '32'),
     ('v_permlane32_swap_b32', 'v_permlane32_swap_b32 {d}, {a}', '32'),
+    # the forms of the numpy-stream draw pass (k_np_draw_compact: profiles/np_draw_census.md)
+    ('v_lshrrev_b64', 'v_lshrrev_b64 {d}, 1, {d}', '64'),
+    ('v_lshrrev_b64_vshift', 'v_lshrrev_b64 {d}, {a32}, {d}', '64'),
+    ('v_lshlrev_b64_vshift', 'v_lshlrev_b64 {d}, {a32}, {d}', '64'),
+    ('v_cmp_ge_u64_e64_sgpr', 'v_cmp_ge_u64_e64 s[22:23], {d}, {a}', '64'),
+    ('v_mov_b64', 'v_mov_b64 {d}, {a}', '64'),
+    ('v_bitop3_b32_sgpr', 'v_bitop3_b32 {d}, {d}, s20, {a} bitop3:0xea', '32'),
+    ('v_alignbit_b32_vshift', 'v_alignbit_b32 {d}, {d}, {a}, {b}', '32'),
+    ('v_alignbit_b32_9', 'v_alignbit_b32 {d}, {d}, {a}, 9', '32'),
+    ('v_mbcnt_lo_u32_b32', 'v_mbcnt_lo_u32_b32 {d}, s20, {d}', '32'),
+    ('v_mbcnt_hi_u32_b32', 'v_mbcnt_hi_u32_b32 {d}, s21, {d}', '32'),
+    ('v_bfe_i32', 'v_bfe_i32 {d}, {d}, 0, 16', '32'),
+    ('v_addc_co_u32', 'v_addc_co_u32 {d}, vcc, {a}, {d}, vcc', '32'),
+    ('v_lshlrev_b32_sdwa_byte', 'v_lshlrev_b32_sdwa {d}, {a}, {d} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0', '32'),
+    ('ds_write_b16', 'ds_write_b16 {a}, {d}', '32lds'),
+    ('ds_write_b16_d16_hi', 'ds_write_b16_d16_hi {a}, {d}', '32lds'),
+    ('ds_write_b64', 'ds_write_b64 {a32}, {d}', '64lds'),
     ('ds_bpermute_b32', 'ds_bpermute_b32 {d}, {a}, {d}', '32lds'),
     ('ds_read_b32', 'ds_read_b32 {d}, {a}', '32lds'),
     ('ds_read_u16', 'ds_read_u16 {d}, {a}', '32lds'),

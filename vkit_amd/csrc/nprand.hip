@@ -132,6 +132,7 @@ struct TilePlan {
     uint32_t c_in, count;
 };
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u128 mk128(const uint64_t *w) { return ((u128)w[1] << 64) | (u128)w[0]; }
 
 __device__ __forceinline__ uint64_t pcg_out(u128 s)
@@ -206,8 +207,9 @@ __device__ __forceinline__ int rounded_step(const NpJob &job, double z, bool ine
         const double f = v - floor(v);
         if (fabs(f - 0.5) < 1e-9) flags |= VKX_NP_AMBIGUOUS;
     }
-    // |v| < 2^31: adding 1.5 * 2^52 leaves rint(v) (round half to even) in the low dword
-    return (int16_t)(int)__double_as_longlong(v + 6755399441055744.0);
+    // |v| < 2^31: adding 1.5 * 2^52 leaves rint(v) (round half to even) in the low dword; the int16 is its low half, taken where
+    // the step is stored (the draw pass packs two of them into a dword as they are)
+    return (int)(uint32_t)__double_as_longlong(v + 6755399441055744.0);
 }
 struct EmitNone {
     typedef int Val;
@@ -262,8 +264,8 @@ struct WaveWork {
     uint64_t slow[kRounds];      // per round: the lanes whose attempt is not a fast accept
     uint64_t semit[kRounds];     // per round: the events that emit a sample, as a lane mask
     uint64_t cov[kRounds];       // per round: the draws consumed by an attempt that started earlier
-    // kEmit / kCompact: what every draw would emit as a fast accept (int16 steps, or the float64 draw); kCompact squeezes the
-    // tile's samples together in place and sends them to the tile's slot as 16-byte groups
+    // kEmit / kCompact: what every draw would emit as a fast accept (int16 steps, or the float64 draw); kCompact parks two rounds
+    // per dword (park_index), squeezes the tile's samples together in place and sends them to the tile's slot as 16-byte groups
     __attribute__((aligned(16))) Val val[WITH_VAL ? kRounds : 1][64];
 };
 
@@ -296,25 +298,30 @@ __device__ __forceinline__ uint32_t lds_offset(const void *p)
     return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
 }
 
-// The samples of a tile parked in draw order (`flat[64 r + l]` = what draw l of round r emits), lane r < kRounds holding round
-// r's emit mask: squeezed together IN PLACE -- a sample's rank never exceeds its draw position, rounds are handled in order
-// and a round reads its 64 elements before it writes.  Per round two v_readlane, two v_mbcnt whose addend carries the running
-// count, one address op, a 2-byte LDS read and a write masked through exec.  Returns the number of samples.
+// The samples of a tile parked two rounds to a dword: element r of lane l (what draw 64 r + l emits) at park_index(64 r + l), so that
+// rounds 2 p and 2 p + 1 of a lane share one 4-byte LDS write in phase 1 and one read here.
+__device__ __forceinline__ uint32_t park_index(uint32_t pos) { return (pos & ~127u) | ((pos & 63u) << 1) | ((pos >> 6) & 1u); }
+
+// They are squeezed together IN PLACE into draw order, lane r < kRounds holding round r's emit mask: a sample's rank never exceeds
+// 64 (r + 1) -- the end of its pair of rounds --, pairs are handled in order and a pair reads its 128 elements before it writes.  Per round
+// two v_readlane, two v_mbcnt whose addend carries the running count, one address op and a 2-byte write masked through exec (the
+// high half of a dword through ds_write_b16_d16_hi); one 4-byte read per two rounds.  Returns the number of samples.
 __device__ __forceinline__ uint32_t compact_tile_lds(int16_t *flat, uint64_t m)
 {
     const uint32_t lane = (uint32_t)__lane_id();
     const uint32_t base = lds_offset(flat);
+    const uint32_t *pairs = (const uint32_t *)flat;
     uint32_t run = 0;
-    // eight rounds' reads are in flight before the first of their writes (a round's write lands at or below the round's own
-    // elements, never on a later round's): one LDS round trip per eight rounds instead of one per round
+    // eight rounds' reads are in flight before the first of their writes (a round's write lands below the end of its own pair,
+    // never on a later pair): one LDS round trip per eight rounds instead of one per round
     constexpr int kBatch = 8;
     static_assert(kRounds % kBatch == 0 || kRounds < kBatch, "rounds per compaction batch");
 #pragma unroll
     for (int r0 = 0; r0 < kRounds; r0 += kBatch) {
-        uint32_t v[kBatch];
+        uint32_t v[kBatch / 2];
 #pragma unroll
-        for (int j = 0; j < kBatch; j++)
-            if (r0 + j < kRounds) v[j] = (uint16_t)flat[64 * (r0 + j) + lane];
+        for (int j = 0; j < kBatch; j += 2)
+            if (r0 + j < kRounds) v[j / 2] = pairs[32 * (r0 + j) + lane];
 #pragma unroll
         for (int j = 0; j < kBatch; j++) {
             const int r = r0 + j;
@@ -324,8 +331,12 @@ __device__ __forceinline__ uint32_t compact_tile_lds(int16_t *flat, uint64_t m)
             const uint32_t addr = base + 2 * rank;
             const uint64_t mask = ((uint64_t)hi << 32) | lo;
             uint64_t saved;
-            asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\tds_write_b16 %[a], %[v]\n\ts_mov_b64 exec, %[sv]"
-                         : [sv] "=&s"(saved) : [m] "s"(mask), [a] "v"(addr), [v] "v"(v[j]) : "memory");
+            if (j & 1)
+                asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\tds_write_b16_d16_hi %[a], %[v]\n\ts_mov_b64 exec, %[sv]"
+                             : [sv] "=&s"(saved) : [m] "s"(mask), [a] "v"(addr), [v] "v"(v[j / 2]) : "memory");
+            else
+                asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\tds_write_b16 %[a], %[v]\n\ts_mov_b64 exec, %[sv]"
+                             : [sv] "=&s"(saved) : [m] "s"(mask), [a] "v"(addr), [v] "v"(v[j / 2]) : "memory");
             run += (uint32_t)__builtin_popcountll(mask);
         }
     }
@@ -350,29 +361,50 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
     // state after draw `lane` of the tile has been stepped
     u128 s = mk128(&g_jump.lane[lane][0]) * base + mk128(&g_jump.lane[lane][2]) * inc;
     uint32_t nev = 0;
-    if (lane < kRounds) ws.semit[lane] = 0;
+    if (lane < kRounds) {
+        ws.semit[lane] = 0;
+        ws.slow[lane] = 0;
+    }
     // two rounds per iteration from two independent generator states (draws 64 r + l and 64 (r + 1) + l, both striding
-    // 128): twice the instruction-level parallelism for the long dependent chain state -> draw -> table -> compare
-    auto round = [&](int r, const u128 &st) {
+    // 128): both table look-ups are issued first and the two stride steps run while they are in flight, so that the LDS latency of
+    // the chain state -> draw -> table -> compare is covered by the wavefront's own multiplies instead of by other wavefronts
+    // the fields phase 1 needs, on 32-bit words: idx = bits 0-7, the sign = bit 8, rabs = bits 9-60 of the rotated XSL-RR word
+    struct Draw {
+        uint32_t lo, dlo, dhi;   // low word of the draw; 2^52 + rabs as float64 bits
+        u32x4 e;                 // ki | 2^52 (as dlo, dhi), wi: one 16-byte LDS read
+    };
+    // the constants of the field extraction and of the sign, held in VGPRs: v_bitop3_b32 issues at about half the cycles of a VOP3
+    // when all three operands are VGPRs (4.46 with an SGPR constant, 2.46 without: profiles/np_instruction_rates.md)
+    uint32_t k_m20 = 0x000fffffu, k_exp = 0x43300000u, k_sgn = 0x80000000u;
+    asm volatile("" : "+v"(k_m20), "+v"(k_exp), "+v"(k_sgn));
+    auto lookup = [&](const u128 &st) {
         const uint64_t u = pcg_out(st);
-        const int idx = (int)(u & 0xff);
-        const uint64_t rabs = (u >> 9) & 0x000fffffffffffffull;
-        const uint4 e = zig[idx];
-        const uint64_t ki = ((uint64_t)e.y << 32) | e.x;
+        Draw d;
+        d.lo = (uint32_t)u;
+        d.e = ((const u32x4 *)zig)[d.lo & 0xff];
+        d.dlo = __builtin_amdgcn_alignbit((uint32_t)(u >> 32), d.lo, 9);
+        d.dhi = __builtin_amdgcn_bitop3_b32((uint32_t)(u >> 41), k_m20, k_exp, 0xea /* (a & b) | c */);
+        return d;
+    };
+    // what draw `lane` of round r would emit as a fast accept; the event push of the draws that are not one
+    auto finish = [&](int r, const u128 &st, const Draw &d) -> typename Emit::Val {
+        typename Emit::Val v = 0;
         if (MODE != kCount) {
-            const double wi = __longlong_as_double(((long long)e.w << 32) | e.z);
-            // rabs < 2^52: exact conversion through the exponent trick
-            double x = (__longlong_as_double((long long)(0x4330000000000000ull | rabs)) - 4503599627370496.0) * wi;
-            // x >= 0: the sign (bit 8 of the draw) is or-ed into the float64 sign bit
-            x = __longlong_as_double(__double_as_longlong(x) | ((long long)((uint32_t)u << 23 & 0x80000000u) << 32));
-            const typename Emit::Store v = (typename Emit::Store)Emit::make(job, x, false, flags);
-            if (MODE == kRecord) rec_val[64 * r + lane] = v;
-            else if (MODE == kEmit || MODE == kCompact) ws.val[r][lane] = v;
+            // x = rabs * wi, the sign (bit 8 of the draw, rotated to bit 31) or-ed into wi: rabs < 2^52 converts exactly through
+            // the exponent trick and the product of a signed factor is the signed product
+            const uint32_t wsgn = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_alignbit(d.lo, d.lo, 9), k_sgn, d.e[3], 0xea);
+            const double wi = __longlong_as_double(((long long)wsgn << 32) | d.e[2]);
+            const double x = (__longlong_as_double((long long)(((uint64_t)d.dhi << 32) | d.dlo)) - 4503599627370496.0) * wi;
+            v = Emit::make(job, x, false, flags);
+            if (MODE == kRecord) rec_val[64 * r + lane] = (typename Emit::Store)v;
+            else if (MODE == kEmit) ws.val[r][lane] = (typename Emit::Store)v;
         }
-        const uint64_t slow = __ballot(rabs >= ki);
-        if (lane == 0) ws.slow[r] = slow;
+        // rabs >= ki as 2^52 + rabs >= 2^52 + ki
+        const bool slow_me = (((uint64_t)d.dhi << 32) | d.dlo) >= (((uint64_t)d.e[1] << 32) | d.e[0]);
+        // (the round's mask of slow lanes is or-ed together from the event list in phase 2: no per-round store)
+        const uint64_t slow = __ballot(slow_me);
         if (slow) {
-            if (rabs >= ki) {
+            if (slow_me) {
                 const uint32_t slot = nev + (uint32_t)mbcnt64(slow);
                 if (slot < (uint32_t)kEvCap) {
                     ws.ev_s[slot][0] = (uint64_t)st;
@@ -382,15 +414,23 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
             }
             nev += (uint32_t)__builtin_popcountll(slow);
         }
+        return v;
     };
     const LcgStride stride128 = lcg_stride(mk128(g_jump.a128), mk128(job.c128));
     u128 s2 = a64 * s + c64;
-#pragma unroll 1
+    // (two iterations per trip of the loop: they share the address increments and the loop's own instructions, 1 - 2 % of the draw pass)
+#pragma unroll 2
     for (int r = 0; r < kRounds; r += 2) {
-        round(r, s);
-        round(r + 1, s2);
+        const u128 sa = s, sb = s2;
+        const Draw da = lookup(sa), db = lookup(sb);
         s = lcg_step(s, stride128);
         s2 = lcg_step(s2, stride128);
+        const typename Emit::Val va = finish(r, sa, da);
+        const typename Emit::Val vb = finish(r + 1, sb, db);
+        // kCompact parks rounds r and r + 1 of a lane side by side (park_index): one v_perm_b32 and one 4-byte LDS write per two
+        // rounds (two 2-byte writes without the perm measured 1 % slower: a 2-byte write costs the LDS pipe what a 4-byte one does)
+        if constexpr (MODE == kCompact)
+            ((uint32_t *)&ws.val[0][0])[32 * r + lane] = __builtin_amdgcn_perm((uint32_t)vb, (uint32_t)va, 0x05040100u);
     }
     if (nev > (uint32_t)kEvCap) {   // never observed; the job is redrawn on the host
         flags |= VKX_NP_SHORT;
@@ -452,7 +492,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                 if (MODE == kRecord) {
                     rec_val[pos] = (typename Emit::Store)Emit::make(job, z, true, flags);
                 } else if (MODE == kCompact) {
-                    (&ws.val[0][0])[pos] = (typename Emit::Store)Emit::make(job, z, true, flags);
+                    (&ws.val[0][0])[park_index(pos)] = (typename Emit::Store)Emit::make(job, z, true, flags);
                 } else if (MODE == kEmit) {
                     const typename Emit::Val v = Emit::make(job, z, true, flags);
                     uint64_t bits = 0;
@@ -463,6 +503,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                 info = len | 0x300u;
             }
             ws.ev_info[ev] = (uint16_t)info;
+            atomicOr((unsigned long long *)&ws.slow[pos >> 6], 1ull << (pos & 63));
             if (info & 0x100u) atomicOr((unsigned long long *)&ws.semit[pos >> 6], 1ull << (pos & 63));
         }
     }
@@ -592,7 +633,6 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
         int16_t *flat = (int16_t *)&ws.val[0][0];
         const uint32_t total = compact_tile_lds(flat, my_mask);        // == count
         const uint32_t groups = (total + 7) >> 3;                      // the last group's surplus elements are never read
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const u32x4 *f16 = (const u32x4 *)flat;
         u32x4 VKX_GLOBAL *s16 = (u32x4 VKX_GLOBAL *)rec_val;
 #pragma unroll
@@ -610,7 +650,8 @@ __device__ __forceinline__ void load_tables(uint4 *zig, double *fi, const NpTabs
 {
     for (int i = threadIdx.x; i < 256; i += blockDim.x) {
         const uint64_t k = tabs->ki[i], w = tabs->wi[i];
-        zig[i] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), (uint32_t)w, (uint32_t)(w >> 32));
+        // ki with the exponent of 2^52 (ki < 2^52): the walk compares it with 2^52 + rabs, the float64 it builds anyway
+        zig[i] = make_uint4((uint32_t)k, (uint32_t)(k >> 32) | 0x43300000u, (uint32_t)w, (uint32_t)(w >> 32));
         fi[i] = __longlong_as_double((long long)tabs->fi[i]);
     }
     __syncthreads();
@@ -728,9 +769,17 @@ __global__ void __launch_bounds__(64 * kDrawWaves) k_np_draw_compact(const NpJob
                                                                     const uint64_t *__restrict__ states, TileInfo *__restrict__ info,
                                                                     vkx_np_result *__restrict__ results, const NpTabs *__restrict__ tabs)
 {
-    __shared__ uint4 zig[256];
-    __shared__ double fi[256];
-    __shared__ WaveWork<int16_t, true> work[kDrawWaves];
+    // one LDS block with the table first: a table entry's address is 16 idx, one shift of the draw (at the table's own LDS offset,
+    // above the 64 KB a ds_read offset field reaches, it took one more instruction per round)
+    struct Lds {
+        uint4 zig[256];
+        double fi[256];
+        WaveWork<int16_t, true> work[kDrawWaves];
+    };
+    __shared__ Lds lds;
+    uint4 *zig = lds.zig;
+    double *fi = lds.fi;
+    WaveWork<int16_t, true> *work = lds.work;
     load_tables(zig, fi, tabs);
     const JumpTabs &g_jump = tabs->jump;
     const long long n_waves = (long long)gridDim.x * kDrawWaves;
