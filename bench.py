@@ -17,12 +17,17 @@ slots), run the chain (k_chain_fused adds the noise, the chain's last member, fr
 ``python bench.py --gpus N`` from a plain shell launches its own ranks (torch.distributed.run on 127.0.0.1, the way the
 reference's pool forks its own workers, vkit/utility/pool.py:153-243); under torch.distributed.run it is one of the ranks.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line.  Everything else the
+bench measures or checks runs only with ``--full``, after the timed steps: the per-kernel breakdown pass and the roofline, the
+device-built lattices against the host operator's, the oracle check of the batch, the legs of other modes and configurations
+and the CPU baselines.
+
 Prints ONE JSON line on rank 0 (see the driver contract in the task description):
   value      = source megapixels (H*W per image) processed per second by all ranks together
-  roofline   = the kernel with the largest share of the step, algorithmic bytes / HIP-event duration against the 8 TB/s HBM
-               peak; roofline.step prices the whole step (every kernel of it) against the same 3S + 3D, roofline.kernels
+  roofline   = (--full) the kernel with the largest share of the step, algorithmic bytes / HIP-event duration against the 8 TB/s
+               HBM peak; roofline.step prices the whole step (every kernel of it) against the same 3S + 3D, roofline.kernels
                lists every kernel of the step
-  cpu_baseline = the CPU oracle (port of the reference arithmetic, 1 thread) on a bounded sample, rank 0, N=1 only
+  cpu_baseline = (--full) the CPU oracle (port of the reference arithmetic, 1 thread) on a bounded sample, rank 0, N=1 only
 """
 import argparse
 import json
@@ -526,14 +531,19 @@ def main():
     ap.add_argument('--batch', type=int, default=0, help='images (pages) per GPU; 0 = the config\'s own: 256 for c3, 64 for c4')
     ap.add_argument('--seed', type=int, default=0, help='--config c4: rng_seed of the worker pool (SeedSequence(seed).spawn(world)[rank])')
     ap.add_argument('--size', type=int, default=2048)
-    ap.add_argument('--cpu-sample', type=int, default=40, help='images timed on the CPU oracle (rank 0, N=1)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps of the default path (c3, resident) also run what the headline does not need: the '
+                         'per-kernel breakdown pass and roofline, the lattice and oracle checks, the legs of --extra-legs and the '
+                         'CPU baselines.  Off: setup, warm-up, the timed steps, --dump-outputs and the line, nothing else')
+    ap.add_argument('--cpu-sample', type=int, default=40, help='--full: images timed on the CPU oracle (rank 0, N=1)')
     ap.add_argument('--cpu-procs', type=int, default=-1,
-                    help='largest process count of the all-cores CPU sweep (-1 = one per CPU of the affinity mask, 0 = skip)')
+                    help='--full: largest process count of the all-cores CPU sweep (-1 = one per CPU of the affinity mask, 0 = skip)')
     ap.add_argument('--verify', type=int, default=4,
-                    help='images of the batch checked against the oracle (spread over the batch, the last one included)')
+                    help='images of the batch checked against the oracle (spread over the batch, the last one included); c3 with '
+                         '--full, c4 always')
     ap.add_argument('--extra-legs', type=int, default=1,
-                    help='at N=1 also measure the other BASELINE configs (C2, C4, C5), the other noise modes and the drop-in paths '
-                         '(reported beside, never as value)')
+                    help='--full: at N=1 also measure the other BASELINE configs (C2, C4, C5), the other noise modes and the drop-in '
+                         'paths (reported beside, never as value)')
     ap.add_argument('--noise-planes', type=int, default=0,
                     help='how the device-drawn numpy stream reaches the chain: 0 = the generator\'s tile slots, read by k_chain_fused '
                          '(default); 1 = an int16 plane per image in HBM, added inside k_chain_fused (rounds 1 - 2); 2 = added to the '
@@ -685,6 +695,51 @@ def main():
     total_px = group.sum_int(batch.source_pixels * args.steps)
     dist_evidence = group.evidence(device_index=device_index, pci_bus_id=(affinity or {}).get('pci_bus_id'), first_image=first, images=B)
     group.close()  # every rank is past the closing barrier and the MAX reduction: nothing collective is left
+
+    value = total_px / elapsed / 1e6         # total_px: summed over the ranks before the group closed
+    ms_per_step = elapsed / args.steps * 1e3
+    result = {
+        'metric': 'Mpixels/s (2048^2 RGB, geo+photo chain)',
+        'value': value,
+        'unit': 'Mpixels/s',
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': ms_per_step,
+        'higher_is_better': True,
+        'scaling': 'weak',
+        'vs_baseline': None,
+        'dtype': 'u8',
+        'data': 'synthetic',
+        'config': {
+            'workload': f'C3 fused chain: camera_cubic_curve remap (level {LEVEL}) + gaussian_blur(sigma={BLUR_SIGMA}) + '
+                        f'color_shift({HUE_DELTA}) + gaussion_noise(std={NOISE_STD}, the numpy stream default_rng(5000 + i) drawn on '
+                        f'the device inside every step), ' + ('states built from the configs inside every step, ' if from_configs else '') +
+                        f'{size}x{size}x3 uint8, batch {B} per GPU',
+            'batch_per_gpu': B,
+            'image': f'{size}x{size}x3',
+            'mean_result_pixels': batch.result_pixels / B,
+            'noise_mode': noise_mode,
+            'states': ('built on the device from the configs inside every step (vkx_camera_states_dev)' if from_configs
+                       else 'host-built, lattices resident before the timed region'),
+            'lanes': args.lanes,
+            'sharding': f'{world} process(es), one per GPU, independent images, no collective' +
+                        (f' (ranks share {n_dev} GPU(s): rendezvous over {backend})' if shared_devices else ''),
+            'verified_against_oracle': 0,       # the checks run with --full, which fills in both; None: nothing was checked
+            'verified': None,
+            'affinity': affinity,
+            'distributed': dist_evidence,
+            'kernel_source_digest': kernel_source_digest(),
+            'setup_s': round(t_setup, 1),
+        },
+    }
+    if not args.full:
+        batch.close()
+        if rank == 0:
+            print(json.dumps(result))
+            sys.stdout.flush()
+        return
+
     breakdown_steps = max(1, min(args.steps, 20))
     kernel_times = {}
     if major_times:
@@ -877,9 +932,6 @@ def main():
                     'of a page: DESIGN.md section 5, round 6)',
         }
 
-    value = total_px / elapsed / 1e6         # total_px: summed over the ranks before the group closed
-    ms_per_step = elapsed / args.steps * 1e3
-
     # ---- roofline: every kernel of the step, the dominant one on top --------------------------------------------------
     S, D = src_px / B, dst_px / B           # mean source / result pixels per image
     chain_bytes = (3 * S + 3 * D) * B       # the fully fused geo + photo chain, per step
@@ -946,43 +998,12 @@ def main():
         'late': 'k_chain_fused ends with color_shift here: the noise member is added to its output by the generator (k_np_apply)',
     }[noise_mode]
     dom_traffic = dom.get('hbm_traffic_bytes_per_step')
-    result = {
-        'metric': 'Mpixels/s (2048^2 RGB, geo+photo chain)',
-        'value': value,
-        'unit': 'Mpixels/s',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': ms_per_step,
-        'higher_is_better': True,
-        'scaling': 'weak',
-        'vs_baseline': None,
-        'dtype': 'u8',
-        'data': 'synthetic',
-        'config': {
-            'workload': f'C3 fused chain: camera_cubic_curve remap (level {LEVEL}) + gaussian_blur(sigma={BLUR_SIGMA}) + '
-                        f'color_shift({HUE_DELTA}) + gaussion_noise(std={NOISE_STD}, the numpy stream default_rng(5000 + i) drawn on '
-                        f'the device inside every step), ' + ('states built from the configs inside every step, ' if from_configs else '') +
-                        f'{size}x{size}x3 uint8, batch {B} per GPU',
-            'batch_per_gpu': B,
-            'image': f'{size}x{size}x3',
-            'mean_result_pixels': D,
-            'noise_mode': noise_mode,
-            'states': ('built on the device from the configs inside every step (vkx_camera_states_dev)' if from_configs
-                       else 'host-built, lattices resident before the timed region'),
-            'lanes': args.lanes,
-            'sharding': f'{world} process(es), one per GPU, independent images, no collective' +
-                        (f' (ranks share {n_dev} GPU(s): rendezvous over {backend})' if shared_devices else ''),
-            'verified_against_oracle': verified,
-            # one flag for "this number is a checked number": every picked image equals the oracle AND (from configs) the lattices the
-            # device built equal the host operator's on this box -- a lattice regression must not hide behind pixels checked on the
-            # lattices the device itself produced
-            'verified': bool(verified == len(picks) and verified > 0 and lattices_ok),
-            'affinity': affinity,
-            'distributed': dist_evidence,
-            'kernel_source_digest': kernel_source_digest(),
-            'setup_s': round(t_setup, 1),
-        },
+    result['config']['verified_against_oracle'] = verified
+    # one flag for "this number is a checked number": every picked image equals the oracle AND (from configs) the lattices the
+    # device built equal the host operator's on this box -- a lattice regression must not hide behind pixels checked on the
+    # lattices the device itself produced
+    result['config']['verified'] = bool(verified == len(picks) and verified > 0 and lattices_ok)
+    result.update({
         'roofline': {
             'bound': 'hbm',
             'bound_measured': 'valu',
@@ -1023,7 +1044,7 @@ def main():
                     'for value numpy\'s (checked against numpy on the verified images): 128-bit LCG + ziggurat, VALU bound, not an '
                     'HBM-bound kernel',
         },
-    }
+    })
     if state_build is not None:
         result['state_construction'] = state_build
     if lattices_resident is not None:

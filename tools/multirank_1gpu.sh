@@ -13,8 +13,8 @@ for l in sys.stdin:
     if d.get('reference_api'): keep['reference_api']={k:d['reference_api'][k] for k in ('pages_per_s','pages','workers')}
     print(json.dumps(keep))
 " >> $OUT; tail -3 /tmp/mr.err | cut -c1-300 >> $OUT; }
-run python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 2 --batch 64 --extra-legs 0 --cpu-sample 0
+run python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 2 --batch 64 --full --extra-legs 0 --cpu-sample 0
 run python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --config c4 --steps 5 --warmup 2 --api-seconds 2
-run python bench.py --gpus 2 --steps 5 --warmup 2 --batch 64 --extra-legs 0 --cpu-sample 0
+run python bench.py --gpus 2 --steps 5 --warmup 2 --batch 64 --full --extra-legs 0 --cpu-sample 0
 run python bench.py --gpus 2 --config c4 --steps 5 --warmup 2 --api-seconds 2
 cat $OUT | cut -c1-1500

@@ -11,7 +11,7 @@ $ROOT/tools/pmc.sh $TAG 32
 python $ROOT/tools/pmc_parse.py $TAG 32 0 > /dev/null          # writes profiles/current_traffic.json on this box for the bench below
 cd $ROOT
 unset VKX_CHAIN_CHUNKS
-timeout 900 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > profiles/${TAG}_bench_full_batch256.json; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/stats_$TAG -o stats -- \
     python $ROOT/bench.py --batch 64 --steps 3 --warmup 1 --cpu-sample 0 --verify 0 --extra-legs 0 \
