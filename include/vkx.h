@@ -856,6 +856,42 @@ typedef struct vkx_char_set {
 int vkx_char_mask_ellipse_sets_fresh_dev(vkx_ctx *ctx, int internal_side_length, const vkx_char_set *sets, int n_sets, int h, int w);
 int vkx_char_mask_ellipse_sets_fresh(vkx_ctx *ctx, int internal_side_length, const vkx_char_set *sets, int n_sets, int h, int w);
 
+/* ---- the default char-heatmap engine (engine/char_heatmap/default.py:93-180) ---------------------------------------------
+ * Per char (4 points, smooth float64 (x, y)), in list order: H = getPerspectiveTransform(template corners (0, 0), (2r, 0),
+ * (2r, 2r), (0, 2r) -> the polygon's float32 self-relative integer points round(smooth) - min) with the project's DECOMP_SVD
+ * definition; warpPerspective(template, H, (bbox.width, bbox.height)) float32, INTER_LINEAR, BORDER_CONSTANT 0; keep-max into
+ * score_map_max (0 at first) and keep-min into score_map_min (1 at first) at the pixels of the char's cv.fillPoly raster
+ * (Polygon.internals.np_mask).  Then per page pixel: overlapped = covered by the rasters of 2 or more chars; neutralized =
+ * overlapped && !(max >= preserving_score_min); delta = clip(max - min, 0, 1); nscore = neutralized ? delta : max;
+ * score = weight_max * max + weight_neutralized * nscore, each product and the sum rounded to float32.
+ * One call: one page, three launches, no synchronisation (_dev).  Planes are dense.  Refused (VKX_ERR_INVALID, nothing
+ * written) before any launch for a NULL pointer, a radius outside 1 .. 1024, h or w outside 1 .. 2^24 - 1 or h * w >= 2^31,
+ * n_chars outside 0 .. 2^24 - 1, a non-finite point, a char box outside the page, a debug record with a NULL plane and
+ * output planes that overlap one another. */
+typedef struct vkx_char_heatmap_config {
+    int32_t radius;                  /* r: the template is (2r + 1) x (2r + 1) */
+    int32_t reserved;                /* 0 */
+    const float *template_host;      /* HOST float32 [2r + 1][2r + 1]: build_np_distance's Gaussian map, values in [0, 1] */
+    float preserving_score_min;      /* float32(gaussian_map_preserving_score_min) */
+    float weight_max;                /* float32(1 - weight_neutralized_score_map), the difference taken in double */
+    float weight_neutralized;        /* float32(weight_neutralized_score_map) */
+    float reserved2;                 /* 0 */
+} vkx_char_heatmap_config;
+typedef struct vkx_char_heatmap_debug {   /* CharHeatmapDefaultDebug: all six planes [h, w] */
+    float *score_map_max;
+    float *score_map_min;
+    uint8_t *char_overlapped_mask;
+    float *char_neutralized_score_map;    /* delta */
+    uint8_t *neutralized_mask;
+    float *neutralized_score_map;
+} vkx_char_heatmap_debug;
+/* _dev: score and the debug planes in device memory; the host form: in host memory, returns after the copies back.
+ * quads_host: HOST float64 [n_chars][4][2] (x, y).  debug: NULL or a record of six planes. */
+int vkx_char_heatmap_fresh_dev(vkx_ctx *ctx, const vkx_char_heatmap_config *config, const double *quads_host, int n_chars,
+                               int h, int w, float *score, const vkx_char_heatmap_debug *debug);
+int vkx_char_heatmap_fresh(vkx_ctx *ctx, const vkx_char_heatmap_config *config, const double *quads_host, int n_chars,
+                           int h, int w, float *score, const vkx_char_heatmap_debug *debug);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

@@ -108,6 +108,29 @@ class VkxCharSet(ctypes.Structure):
     ]
 
 
+class VkxCharHeatmapConfig(ctypes.Structure):
+    _fields_ = [
+        ('radius', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+        ('template_host', c_void_p),
+        ('preserving_score_min', ctypes.c_float),
+        ('weight_max', ctypes.c_float),
+        ('weight_neutralized', ctypes.c_float),
+        ('reserved2', ctypes.c_float),
+    ]
+
+
+class VkxCharHeatmapDebug(ctypes.Structure):
+    _fields_ = [
+        ('score_map_max', c_void_p),
+        ('score_map_min', c_void_p),
+        ('char_overlapped_mask', c_void_p),
+        ('char_neutralized_score_map', c_void_p),
+        ('neutralized_mask', c_void_p),
+        ('neutralized_score_map', c_void_p),
+    ]
+
+
 class VkxLayer(ctypes.Structure):
     _fields_ = [
         ('up', ctypes.c_int32),
@@ -348,6 +371,9 @@ _SIGNATURES['vkx_crop_planes_dev'] = [c_void_p, c_int, c_int, c_int, c_int, c_in
                                       ctypes.POINTER(VkxCropPlane), c_int]
 _SIGNATURES['vkx_char_mask_ellipse_sets_fresh_dev'] = [c_void_p, c_int, ctypes.POINTER(VkxCharSet), c_int, c_int, c_int]
 _SIGNATURES['vkx_char_mask_ellipse_sets_fresh'] = [c_void_p, c_int, ctypes.POINTER(VkxCharSet), c_int, c_int, c_int]
+_SIGNATURES['vkx_char_heatmap_fresh_dev'] = [c_void_p, ctypes.POINTER(VkxCharHeatmapConfig), c_void_p, c_int, c_int, c_int,
+                                             c_void_p, ctypes.POINTER(VkxCharHeatmapDebug)]
+_SIGNATURES['vkx_char_heatmap_fresh'] = _SIGNATURES['vkx_char_heatmap_fresh_dev']
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
@@ -2283,3 +2309,47 @@ def char_mask_ellipse_sets(internal_side_length, sets, shape, ctx=None):
         if buf is not None:
             s.char_masks = buf.host() if on_device else buf
     return True
+
+
+CHAR_HEATMAP_DEBUG_PLANES = (('score_map_max', np.float32), ('score_map_min', np.float32), ('char_overlapped_mask', np.uint8),
+                             ('char_neutralized_score_map', np.float32), ('neutralized_mask', np.uint8),
+                             ('neutralized_score_map', np.float32))
+
+
+def char_heatmap(radius, template, preserving_score_min, weight_max, weight_neutralized, quads, shape, score, debug=None,
+                 ctx=None):
+    """The default char heatmap of one page in ONE call (vkx_char_heatmap_fresh_dev for DevArray planes, the host form for
+    numpy planes).  ``template`` float32 (2r + 1, 2r + 1); the three scalars are float32 already; ``quads`` float64 (N, 4, 2)
+    smooth (x, y), every char box inside the page; ``score`` a float32 plane of ``shape``; ``debug`` None or a dict of the six
+    planes of CHAR_HEATMAP_DEBUG_PLANES.  Asynchronous on the context's stream for device planes."""
+    h, w = shape
+    planes = [(score, np.float32)] + ([(debug[name], dt) for name, dt in CHAR_HEATMAP_DEBUG_PLANES] if debug is not None else [])
+    on_device = isinstance(score, DevArray)
+    for p, dt in planes:
+        if isinstance(p, DevArray) != on_device or np.dtype(p.dtype) != dt or tuple(p.shape) != (h, w):
+            raise ValueError(f'planes must be {(h, w)} arrays of one kind')
+        if not on_device and not p.flags.c_contiguous:
+            raise ValueError('dense planes')
+    if on_device:
+        ctx = ctx or score.ctx
+        if any(p.ctx is not ctx for p, _ in planes):
+            raise ValueError('the planes of one call live on one context')
+    ctx = ctx or default_ctx()
+    template = np.ascontiguousarray(template, dtype=np.float32)
+    if template.shape != (2 * radius + 1, 2 * radius + 1):
+        raise ValueError('the template is (2r + 1) x (2r + 1)')
+    quads = np.ascontiguousarray(np.asarray(quads, dtype=np.float64).reshape(-1, 4, 2))
+    config = VkxCharHeatmapConfig()
+    config.radius, config.template_host = int(radius), template.ctypes.data
+    config.preserving_score_min, config.weight_max, config.weight_neutralized = (
+        float(preserving_score_min), float(weight_max), float(weight_neutralized))
+    ptr = (lambda p: p.ptr) if on_device else (lambda p: p.ctypes.data)
+    rec = None
+    if debug is not None:
+        rec = VkxCharHeatmapDebug(*[ptr(debug[name]) for name, _ in CHAR_HEATMAP_DEBUG_PLANES])
+    fn = lib().vkx_char_heatmap_fresh_dev if on_device else lib().vkx_char_heatmap_fresh
+    check(fn(ctx.handle, ctypes.byref(config), quads.ctypes.data, quads.shape[0], h, w, ptr(score),
+             ctypes.byref(rec) if rec is not None else None))
+    if on_device:
+        for p, _ in planes:
+            p.invalidate_host()

@@ -84,14 +84,6 @@ __device__ inline float nan_max4f(const float v[4])
     return r;
 }
 
-// getPerspectiveTransform(DECOMP_SVD) as the project defines it: closed form, Jacobi SVD for degenerate quads
-__device__ inline void perspective(const float from[8], const float to[8], double H[9])
-{
-    double qf[8], qt[8];
-    for (int i = 0; i < 8; i++) { qf[i] = from[i]; qt[i] = to[i]; }
-    if (!vkc::homography_direct(qf, qt, H)) vkc::homography_jacobi(from, to, H);
-}
-
 // len(range(n)[a:b]) for a >= 0 (Python slice semantics: a negative b counts from the end)
 __device__ inline long long slice_len(long long n, long long a, long long b)
 {
@@ -132,7 +124,7 @@ __global__ void __launch_bounds__(256) k_char_mask_setup(const CharIn *__restric
     for (int k = 1; k < 4; k++) { mx = fminf(mx, ip[2 * k]); my = fminf(my, ip[2 * k + 1]); }
     for (int k = 0; k < 4; k++) { rel[2 * k] = ip[2 * k] - mx; rel[2 * k + 1] = ip[2 * k + 1] - my; }
     double H[9];
-    perspective(char_pts, rel, H);
+    vkc::perspective_transform(char_pts, rel, H);
 
     // affine_np_points: float64 H times the float32 (x, y, 1) columns -- numpy's matmul sums as fma(a2, x2, fma(a1, x1, a0 x0))
     double px[4], py[4];
@@ -154,7 +146,7 @@ __global__ void __launch_bounds__(256) k_char_mask_setup(const CharIn *__restric
     }
     // 2. H2: external points -> those; the warp's size is (ceil(x max), ceil(y max))
     double H2[9];
-    perspective(ext_pts, tp, H2);
+    vkc::perspective_transform(ext_pts, tp, H2);
     long long th = 0, tw = 0;
     if (ceil_to_int(nan_max4f(ty), th, status) && ceil_to_int(nan_max4f(tx), tw, status)) {
         // 3. placement: round(min smooth + offset), Python's round (halves to even)

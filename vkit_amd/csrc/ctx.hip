@@ -105,6 +105,10 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->char_layout);
     scratch_release(&ctx->char_host);
     scratch_release(&ctx->char_owner);
+    scratch_release(&ctx->heat_table);
+    scratch_release(&ctx->heat_geo);
+    scratch_release(&ctx->heat_host);
+    scratch_release(&ctx->heat_planes);
     scratch_release(&ctx->glass_win);
     scratch_release(&ctx->jpeg_planes);
     scratch_release(&ctx->pz_tabs);

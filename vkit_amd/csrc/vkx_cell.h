@@ -286,6 +286,15 @@ __device__ __noinline__ void homography_jacobi(const float from[8], const float 
     homography_jacobi_ws(from, to, H, ws);
 }
 
+// getPerspectiveTransform(DECOMP_SVD) as the project defines it: closed form, Jacobi SVD for degenerate quads.  Shared by
+// the char-mask (char_mask.hip) and char-heatmap (char_heatmap.hip) setup passes.
+__device__ inline void perspective_transform(const float from[8], const float to[8], double H[9])
+{
+    double qf[8], qt[8];
+    for (int i = 0; i < 8; i++) { qf[i] = from[i]; qt[i] = to[i]; }
+    if (!homography_direct(qf, qt, H)) homography_jacobi(from, to, H);
+}
+
 // Number of minor-axis steps an 8-connected Bresenham line (cv::LineIterator, walked from its left end) has
 // taken after k major steps: ceil((2 k dmin - dmaj) / (2 dmaj)), never negative.
 __device__ __forceinline__ int bres_minor(int k, int dmaj, int dmin)

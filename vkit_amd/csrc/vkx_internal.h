@@ -115,6 +115,10 @@ struct vkx_ctx {
                                                                 // staging of the host form
     vkx_scratch char_owner;                   // ... the ownership planes: all zero between calls (the resolve clears what it reads)
     size_t char_owner_zeroed = 0;             // ... bytes of it known to be zero
+    vkx_scratch heat_table, heat_geo, heat_host;   // char heatmap (char_heatmap.hip): template + quads + boxes + tile starts,
+                                                   // setup results, staging of the host form
+    vkx_scratch heat_planes;                  // ... the max / min / count planes (int [3][h * w])
+    size_t heat_clean_page = 0;               // ... the page size they hold their initial values for (0: none)
     vkx_scratch glass_win;                    // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows
     bool pz_tabs_ready = false;
