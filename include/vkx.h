@@ -892,6 +892,38 @@ int vkx_char_heatmap_fresh_dev(vkx_ctx *ctx, const vkx_char_heatmap_config *conf
 int vkx_char_heatmap_fresh(vkx_ctx *ctx, const vkx_char_heatmap_config *config, const double *quads_host, int n_chars,
                            int h, int w, float *score, const vkx_char_heatmap_debug *debug);
 
+/* ---- PageTextRegionLabelStep (pipeline/text_detection/page_text_region_label.py) ----------------------------------------
+ * vkx_region_label_deviate_dev replaces the deviate-candidate loop of generate_page_char_regression_labels (:498-575): per
+ * char g < n_chars (4 points, smooth float64 (x, y)) and per candidate j < m, with the box (up, left, bh, bw) of the rounded
+ * points (Polygon.bounding_box) and H = getPerspectiveTransform((0, 0), (bw - 1, 0), (bw - 1, bh - 1), (0, bh - 1) -> the
+ * float32 self-relative integer points) with the project's DECOMP_SVD definition, the drawn point (x, y) maps as affine_points
+ * does (float64 H times the float32 (x, y, 1) in numpy's matmul order, a single column (m == 1) in its matrix-vector
+ * order, then the two divisions) to (px, py); out = (up + py,
+ * left + px), their rint, a status (0 in the page, 1 dropped: the last of m > 2 points equals the first as integers, as
+ * PointTuple.from_np_array drops it; 2 outside [0, h) x [0, w); 3 non-finite) and, for status 0, the nearest-centre class
+ * that replaces KDTree(centres).query (:468, :541): 0 the char's own centre strictly nearest, 1 another strictly nearer, 2 a
+ * tie at the minimum (the host resolves it).  Squared distances of integer points, exact.  One launch, no synchronisation.
+ * Refused (VKX_ERR_INVALID, nothing launched) for a NULL pointer, n_centres outside 1 .. 2^24 - 1, n_chars outside
+ * 1 .. n_centres, m outside 1 .. 4096, h or w outside 1 .. 32768, a centre or a point outside +-2^30, a non-finite point, a
+ * box narrower or lower than 3 and a draw outside [1, bw - 2] x [1, bh - 2]. */
+typedef struct vkx_region_label_deviate_out {
+    double y, x;          /* the smooth page point */
+    int32_t iy, ix;       /* rint(y), rint(x) (status 0) */
+    int32_t status;       /* 0 in the page, 1 dropped, 2 outside the page, 3 non-finite */
+    int32_t cls;          /* status 0: 0 keep, 1 drop, 2 tie */
+} vkx_region_label_deviate_out;
+/* quads_host: HOST float64 [n_chars][4][2] (x, y); centres_host: HOST int32 [n_centres][2] (x, y), char g's centre at g;
+ * draws_host: HOST int32 [n_chars][m][2] (x, y); out: DEVICE [n_chars * m]. */
+int vkx_region_label_deviate_dev(vkx_ctx *ctx, const double *quads_host, const int32_t *centres_host, int n_centres,
+                                 int n_chars, const int32_t *draws_host, int m, int h, int w, vkx_region_label_deviate_out *out);
+/* vkx_region_label_planes_dev replaces generate_page_char_bounding_box_mask (:578-592) and the inactive fills of
+ * generate_page_char_mask (:406) and generate_page_char_height_score_map (:439): box_mask = 1 inside any of the boxes
+ * (up, down, left, right), 0 elsewhere; char_mask = 0 and char_height = 0.0f where active_mask == 0.  Dense device planes
+ * [h, w].  One launch, no synchronisation.  Refused for a NULL pointer, n_boxes outside 0 .. 2^24 - 1, h or w outside
+ * 1 .. 32768, a box not inside the page and planes that overlap one another. */
+int vkx_region_label_planes_dev(vkx_ctx *ctx, const int32_t *boxes_host, int n_boxes, int h, int w, const uint8_t *active_mask,
+                                uint8_t *char_mask, float *char_height, uint8_t *box_mask);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

@@ -374,6 +374,9 @@ _SIGNATURES['vkx_char_mask_ellipse_sets_fresh'] = [c_void_p, c_int, ctypes.POINT
 _SIGNATURES['vkx_char_heatmap_fresh_dev'] = [c_void_p, ctypes.POINTER(VkxCharHeatmapConfig), c_void_p, c_int, c_int, c_int,
                                              c_void_p, ctypes.POINTER(VkxCharHeatmapDebug)]
 _SIGNATURES['vkx_char_heatmap_fresh'] = _SIGNATURES['vkx_char_heatmap_fresh_dev']
+_SIGNATURES['vkx_region_label_deviate_dev'] = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                               c_void_p]
+_SIGNATURES['vkx_region_label_planes_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
@@ -2353,3 +2356,50 @@ def char_heatmap(radius, template, preserving_score_min, weight_max, weight_neut
     if on_device:
         for p, _ in planes:
             p.invalidate_host()
+
+
+# vkx_region_label_deviate_out, one record per candidate
+REGION_LABEL_DEVIATE_DTYPE = np.dtype([('y', np.float64), ('x', np.float64), ('iy', np.int32), ('ix', np.int32),
+                                       ('status', np.int32), ('cls', np.int32)])
+assert REGION_LABEL_DEVIATE_DTYPE.itemsize == 32
+
+
+def region_label_deviate(quads, centres, draws_xy, shape, ctx=None):
+    """The deviate candidates of PageTextRegionLabelStep (vkx_region_label_deviate_dev): ``quads`` float64 (n, 4, 2) smooth
+    (x, y) of the first n chars, ``centres`` int32 (N >= n, 2) (x, y) of every char, ``draws_xy`` int32 (n, m, 2) (x, y).
+    ONE launch, one copy back, ONE Context.sync -> a REGION_LABEL_DEVIATE_DTYPE numpy array (n, m)."""
+    ctx = ctx or default_ctx()
+    h, w = shape
+    quads = np.ascontiguousarray(np.asarray(quads, dtype=np.float64).reshape(-1, 4, 2))
+    centres = np.ascontiguousarray(np.asarray(centres, dtype=np.int32).reshape(-1, 2))
+    draws = np.ascontiguousarray(np.asarray(draws_xy, dtype=np.int32))
+    if draws.ndim != 3 or draws.shape[2] != 2 or draws.shape[0] != quads.shape[0]:
+        raise ValueError('draws: (n, m, 2) for n quads')
+    n, m = draws.shape[:2]
+    nbytes = n * m * REGION_LABEL_DEVIATE_DTYPE.itemsize
+    out = ctx.dev_empty((max(nbytes, 1),), np.uint8)
+    check(lib().vkx_region_label_deviate_dev(ctx.handle, quads.ctypes.data, centres.ctypes.data, centres.shape[0], n,
+                                             draws.ctypes.data, m, int(h), int(w), c_void_p(out.ptr)))
+    host = ctx.pinned_empty((max(nbytes, 1),), np.uint8)
+    ctx.copy_out(out.ptr, host[:nbytes])
+    ctx.sync()
+    return host[:nbytes].view(REGION_LABEL_DEVIATE_DTYPE).reshape(n, m)
+
+
+def region_label_planes(boxes, active_mask, char_mask, char_height, box_mask):
+    """The char bounding-box mask and the inactive region of PageTextRegionLabelStep (vkx_region_label_planes_dev): ``boxes``
+    int32 (n, 4) (up, down, left, right) inside the page; dense DevArrays of one context and one shape: ``active_mask``
+    uint8, ``char_mask`` uint8 and ``char_height`` float32 (zeroed in place where the active mask is 0), ``box_mask`` uint8
+    (written whole).  ONE launch, asynchronous."""
+    ctx = active_mask.ctx
+    shape = tuple(active_mask.shape)
+    for p, dt in ((active_mask, np.uint8), (char_mask, np.uint8), (char_height, np.float32), (box_mask, np.uint8)):
+        if not isinstance(p, DevArray) or p.ctx is not ctx or np.dtype(p.dtype) != dt or tuple(p.shape) != shape \
+                or len(shape) != 2:
+            raise ValueError('region_label_planes takes 2-D DevArrays of one context and one shape')
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+    check(lib().vkx_region_label_planes_dev(ctx.handle, boxes.ctypes.data if len(boxes) else None, len(boxes), shape[0],
+                                            shape[1], c_void_p(active_mask.ptr), c_void_p(char_mask.ptr),
+                                            c_void_p(char_height.ptr), c_void_p(box_mask.ptr)))
+    for p in (char_mask, char_height, box_mask):
+        p.invalidate_host()

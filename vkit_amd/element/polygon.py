@@ -4,6 +4,7 @@ vertex bookkeeping, integer bounding box, clipping / shifting / resizing of the 
 with the ``fill_*`` / ``extract_*`` operators built on it.  The per-cell rasterisation of the image-grid
 distortions lives in the HIP grid kernels; shapely / pyclipper based operations are outside the accelerated path.
 """
+import math
 from typing import Iterable, Optional, Sequence, Tuple, Union
 
 import attrs
@@ -97,6 +98,26 @@ class Polygon:
             object.__setattr__(self, '_mask', mask)
         return self._mask
 
+    # ---- measures (reference polygon.py:218-260)
+    def get_center_point(self):
+        """The polygon centroid of shapely (GEOS), over the smooth vertices: see ``polygon_centroids``."""
+        if self.num_points < 3:
+            raise ValueError('a polygon centroid needs at least 3 points')
+        x, y = polygon_centroids(self.smooth_xy[None])[0].tolist()
+        return Point.create(y=y, x=x)
+
+    def get_rectangular_height(self):
+        # the mean of the left and right sides (vertices up-left, up-right, down-right, down-left); math.hypot, as the
+        # reference computes it (np.hypot may differ in the last bit)
+        assert self.num_points == 4
+        (ulx, uly), (urx, ury), (drx, dry), (dlx, dly) = self.smooth_xy.tolist()
+        return (math.hypot(uly - dly, ulx - dlx) + math.hypot(ury - dry, urx - drx)) / 2
+
+    def get_rectangular_width(self):
+        assert self.num_points == 4
+        (ulx, uly), (urx, ury), (drx, dry), (dlx, dly) = self.smooth_xy.tolist()
+        return (math.hypot(uly - ury, ulx - urx) + math.hypot(dly - dry, dlx - drx)) / 2
+
     # ---- fills / extraction through the raster (reference polygon.py:439-503)
     def fill_np_array(self, mat: np.ndarray, value, alpha=1.0, keep_max_value: bool = False,
                       keep_min_value: bool = False):
@@ -182,6 +203,46 @@ class Polygon:
 
 def generate_fill_by_polygons_mask(shape, polygons, mode):
     raise NotImplementedError('polygon set operations are outside the accelerated path')
+
+
+def polygon_centroids(xy: np.ndarray) -> np.ndarray:
+    """float64 (N, 2) centroids (x, y) of N polygons of k >= 3 smooth vertices each, ``xy`` float64 (N, k, 2).
+
+    The reference takes ``shapely.Polygon(smooth points).centroid``, i.e. GEOS's algorithm::Centroid.  Shapely is not a
+    dependency here, so this restates it (like the cv2 members, it is unpinned by an installed copy):
+    over the closed ring p[0..k], triangles fanned from p[0]: cg3 += a2 * (p0 + p[i] + p[i+1]) and areasum2 += a2, with
+    a2 = (p[i].x - p0.x) * (p[i+1].y - p0.y) - (p[i+1].x - p0.x) * (p[i].y - p0.y), and the centroid cg3 / 3 / areasum2.
+    GEOS signs every a2 by the ring's orientation; negating every term negates both sums exactly, so the quotient does not
+    depend on it.  A ring of zero area takes GEOS's fallback: the length-weighted mid points of its non-zero segments
+    (length sqrt(dx * dx + dy * dy)), or its first point when it has none."""
+    xy = np.asarray(xy, dtype=np.float64)
+    ring = np.concatenate([xy, xy[:, :1]], axis=1)
+    p0x, p0y = ring[:, 0, 0], ring[:, 0, 1]
+    cg3x = np.zeros(len(xy))
+    cg3y = np.zeros(len(xy))
+    area2 = np.zeros(len(xy))
+    line_x = np.zeros(len(xy))
+    line_y = np.zeros(len(xy))
+    length = np.zeros(len(xy))
+    for i in range(ring.shape[1] - 1):
+        ax, ay = ring[:, i, 0], ring[:, i, 1]
+        bx, by = ring[:, i + 1, 0], ring[:, i + 1, 1]
+        a2 = (ax - p0x) * (by - p0y) - (bx - p0x) * (ay - p0y)
+        cg3x = cg3x + a2 * (p0x + ax + bx)
+        cg3y = cg3y + a2 * (p0y + ay + by)
+        area2 = area2 + a2
+        dx, dy = ax - bx, ay - by
+        seg = np.sqrt(dx * dx + dy * dy)
+        nz = seg != 0.0
+        length = np.where(nz, length + seg, length)
+        line_x = np.where(nz, line_x + seg * ((ax + bx) / 2), line_x)
+        line_y = np.where(nz, line_y + seg * ((ay + by) / 2), line_y)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out = np.stack([cg3x / 3 / area2, cg3y / 3 / area2], axis=1)
+        line = np.stack([line_x / length, line_y / length], axis=1)
+    flat = ~(np.abs(area2) > 0.0)
+    out[flat] = np.where((length > 0.0)[flat, None], line[flat], ring[flat, 0])
+    return out
 
 
 from .point import Point, PointList, PointTuple  # noqa: E402

@@ -24,3 +24,14 @@ from .page_cropping import (  # noqa: F401
     PageCroppingStepOutput,
     page_cropping_step_factory,
 )
+from .page_text_region import PageTextRegionStepOutput  # noqa: F401
+from .page_text_region_label import (  # noqa: F401
+    PageCharRegressionLabel,
+    PageCharRegressionLabelTag,
+    PageTextRegionLabelStep,
+    PageTextRegionLabelStepConfig,
+    PageTextRegionLabelStepInput,
+    PageTextRegionLabelStepOutput,
+    Vector,
+    page_text_region_label_step_factory,
+)
