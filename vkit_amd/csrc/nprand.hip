@@ -278,8 +278,18 @@ __device__ __forceinline__ int mbcnt64(uint64_t m)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// The walk of one wavefront over one tile.  `base` = LCG state before the tile's first draw, `c_in` = leading draws
-// already consumed by the previous tile's last attempt.  Lane l owns draws 64 r + l of the tile.
+// The states of lane l's draws of rounds 0 and 1 of a tile (after draws l and 64 + l have been stepped), from `base`, the LCG state
+// before the tile's first draw: two full 128-bit products and one stride step.
+__device__ __forceinline__ void tile_lane_states(const JumpTabs &g_jump, const NpJob &job, u128 base, u128 &s, u128 &s2)
+{
+    const int lane = __lane_id();
+    s = mk128(&g_jump.lane[lane][0]) * base + mk128(&g_jump.lane[lane][2]) * mk128(job.inc);
+    s2 = mk128(g_jump.a64) * s + mk128(job.c64);
+}
+
+// The walk of one wavefront over one tile.  (`s`, `s2`) = the lane's states of rounds 0 and 1 (tile_lane_states); the walk leaves
+// them at rounds kRounds and kRounds + 1, the next tile's rounds 0 and 1.  `c_in` = leading draws already consumed by the previous
+// tile's last attempt.  Lane l owns draws 64 r + l of the tile.
 //   phase 1  all rounds, branch-free but for the event push: draw, ziggurat layer lookup, value of a fast accept; the
 //            few draws whose attempt needs more (wedge test, tail) are queued with their LCG state
 //   phase 2  the queue is evaluated densely, one event per lane: exp() / log1p() run once per tile instead of once per
@@ -346,20 +356,17 @@ __device__ __forceinline__ uint32_t compact_tile_lds(int16_t *flat, uint64_t m)
 
 template <class Emit, int MODE>
 __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 *__restrict__ zig /* LDS: ki | wi */, const double *__restrict__ fi /* LDS */,
-                          WaveWork<typename Emit::Store, MODE == kEmit || MODE == kCompact> &ws, u128 base, uint32_t c_in, long long prefix,
+                          WaveWork<typename Emit::Store, MODE == kEmit || MODE == kCompact> &ws, u128 &s, u128 &s2, uint32_t c_in, long long prefix,
                           long long draw_base, typename Emit::Store VKX_GLOBAL *rec_val, uint64_t VKX_GLOBAL *rec_mask, void *emit_dst,
                           uint32_t &count_out, uint32_t &carry_out, uint64_t &start0, uint64_t &emit0, bool &has_tail, uint32_t &flags,
                           unsigned long long *draws_used)
 {
     const int lane = __lane_id();
     const u128 inc = mk128(job.inc);
-    const u128 a64 = mk128(g_jump.a64), c64 = mk128(job.c64);
     // wave-uniform by construction; said explicitly so that the start walk below stays on the scalar unit
     c_in = (uint32_t)__builtin_amdgcn_readfirstlane((int)c_in);
     prefix = (long long)rfl64((uint64_t)prefix);
     draw_base = (long long)rfl64((uint64_t)draw_base);
-    // state after draw `lane` of the tile has been stepped
-    u128 s = mk128(&g_jump.lane[lane][0]) * base + mk128(&g_jump.lane[lane][2]) * inc;
     uint32_t nev = 0;
     if (lane < kRounds) {
         ws.semit[lane] = 0;
@@ -416,15 +423,18 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
         }
         return v;
     };
-    const LcgStride stride128 = lcg_stride(mk128(g_jump.a128), mk128(job.c128));
-    u128 s2 = a64 * s + c64;
+    LcgStride stride128 = lcg_stride(mk128(g_jump.a128), mk128(job.c128));
+    // the multiplier limbs held in VGPRs across the loop (v_mad_u64_u32 wants them there; left to itself the compiler re-copies
+    // them from SGPRs inside the loop once the lane states also live across the tiles of a run: four moves per trip)
+    asm volatile("" : "+v"(stride128.a0), "+v"(stride128.a1), "+v"(stride128.a2), "+v"(stride128.a3));
+    u128 sl = s, sl2 = s2;
     // (two iterations per trip of the loop: they share the address increments and the loop's own instructions, 1 - 2 % of the draw pass)
 #pragma unroll 2
     for (int r = 0; r < kRounds; r += 2) {
-        const u128 sa = s, sb = s2;
+        const u128 sa = sl, sb = sl2;
         const Draw da = lookup(sa), db = lookup(sb);
-        s = lcg_step(s, stride128);
-        s2 = lcg_step(s2, stride128);
+        sl = lcg_step(sl, stride128);
+        sl2 = lcg_step(sl2, stride128);
         const typename Emit::Val va = finish(r, sa, da);
         const typename Emit::Val vb = finish(r + 1, sb, db);
         // kCompact parks rounds r and r + 1 of a lane side by side (park_index): one v_perm_b32 and one 4-byte LDS write per two
@@ -432,6 +442,8 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
         if constexpr (MODE == kCompact)
             ((uint32_t *)&ws.val[0][0])[32 * r + lane] = __builtin_amdgcn_perm((uint32_t)vb, (uint32_t)va, 0x05040100u);
     }
+    s = sl;
+    s2 = sl2;
     if (nev > (uint32_t)kEvCap) {   // never observed; the job is redrawn on the host
         flags |= VKX_NP_SHORT;
         nev = kEvCap;
@@ -527,14 +539,23 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
         const uint64_t touch = __ballot((uint32_t)lane < nev && P < prev_end);
         valid = live;
         if (touch) {
-            uint32_t cover_end = c_in;
-            valid = 0;
-            for (uint32_t e = 0; e < nev; e++) {
-                const uint32_t pe = (uint32_t)__builtin_amdgcn_readlane((int)P, (int)e);
-                if (pe >= cover_end) {
-                    valid |= 1ull << e;
-                    cover_end = (uint32_t)__builtin_amdgcn_readlane((int)end, (int)e);
-                }
+            // only an event that some earlier span reaches can be void: P below the running maximum of `end` over the events before
+            // it (c_in before the first; an inclusive max-scan by DPP, shifted by one lane).  Those few are decided in order: an
+            // event is void when it starts below the end of the last valid event before it (valid spans do not overlap, so that
+            // end is the cover of the serial walk), c_in when there is none; every other event is valid
+            uint32_t m = (uint32_t)lane < nev ? end : 0u;
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x111 /* row_shr:1 */, 0xf, 0xf, true));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x112 /* row_shr:2 */, 0xf, 0xf, true));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x114 /* row_shr:4 */, 0xf, 0xf, true));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x118 /* row_shr:8 */, 0xf, 0xf, true));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x142 /* row_bcast:15 */, 0xa, 0xf, false));
+            m = max(m, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, 0x143 /* row_bcast:31 */, 0xc, 0xf, false));
+            const uint32_t reach_end = max(c_in, (uint32_t)__builtin_amdgcn_update_dpp((int)c_in, (int)m, 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+            for (uint64_t rest = __ballot((uint32_t)lane < nev && P < reach_end); rest; rest &= rest - 1) {
+                const uint32_t e = (uint32_t)__builtin_ctzll(rest);
+                const uint64_t before = valid & ((1ull << e) - 1);
+                const uint32_t cover_end = before ? (uint32_t)__builtin_amdgcn_readlane((int)end, 63 - __builtin_clzll(before)) : c_in;
+                if ((uint32_t)__builtin_amdgcn_readlane((int)P, (int)e) < cover_end) valid &= ~(1ull << e);
             }
         }
         if (valid) {
@@ -741,7 +762,9 @@ __global__ void __launch_bounds__(256) k_np_draw(const NpJob *__restrict__ jobs,
         uint32_t count, carry, flags = 0;
         uint64_t start0, emit0;
         bool has_tail;
-        walk_tile<Emit, kRecord>(job, g_jump, zig, fi, work[threadIdx.x >> 6], mk128(&states[2 * tile]), 0u, 0, 0,
+        u128 s, s2;
+        tile_lane_states(g_jump, job, mk128(&states[2 * tile]), s, s2);
+        walk_tile<Emit, kRecord>(job, g_jump, zig, fi, work[threadIdx.x >> 6], s, s2, 0u, 0, 0,
                                  (typename Emit::Store VKX_GLOBAL *)(rec_val + tile * kTile), (uint64_t VKX_GLOBAL *)(rec_mask + tile * kRounds),
                                  nullptr, count, carry, start0, emit0, has_tail, flags, nullptr);
         if (__lane_id() == 0) {
@@ -766,7 +789,7 @@ constexpr int kDrawWaves = VKX_NP_DRAW_WAVES;
 
 template <class Emit>
 __global__ void __launch_bounds__(64 * kDrawWaves) k_np_draw_compact(const NpJob *__restrict__ jobs, int n_jobs, long long total_tiles,
-                                                                    const uint64_t *__restrict__ states, TileInfo *__restrict__ info,
+                                                                    long long run, const uint64_t *__restrict__ states, TileInfo *__restrict__ info,
                                                                     vkx_np_result *__restrict__ results, const NpTabs *__restrict__ tabs)
 {
     // one LDS block with the table first: a table entry's address is 16 idx, one shift of the draw (at the table's own LDS offset,
@@ -782,14 +805,26 @@ __global__ void __launch_bounds__(64 * kDrawWaves) k_np_draw_compact(const NpJob
     WaveWork<int16_t, true> *work = lds.work;
     load_tables(zig, fi, tabs);
     const JumpTabs &g_jump = tabs->jump;
-    const long long n_waves = (long long)gridDim.x * kDrawWaves;
-    for (long long tile = (long long)blockIdx.x * kDrawWaves + (threadIdx.x >> 6); tile < total_tiles; tile += n_waves) {
-        const int j = job_of_tile(jobs, n_jobs, tile);
+    // a wavefront walks a run of consecutive tiles: the walk leaves the lane's states at the next tile's first two rounds, so the
+    // job search and the start states (two full 128-bit products and a stride step per lane) are paid once per run and job, not
+    // once per tile.  `run` = tiles per wavefront, ceil(total_tiles / wavefronts of the grid), from the host (the 64-bit division
+    // on the device costs each wavefront about a hundred VALU instructions)
+    const long long wave = (long long)blockIdx.x * kDrawWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long run_end = min(total_tiles, (wave + 1) * run);
+    int j = 0;
+    long long job_end = 0;
+    u128 s = 0, s2 = 0;
+    for (long long tile = wave * run; tile < run_end; tile++) {
+        if (tile >= job_end) {
+            j = job_of_tile(jobs, n_jobs, tile);
+            job_end = jobs[j].tile_base + jobs[j].n_tiles;
+            tile_lane_states(g_jump, jobs[j], mk128(&states[2 * tile]), s, s2);
+        }
         const NpJob &job = jobs[j];
         uint32_t count, carry, flags = 0;
         uint64_t start0, emit0;
         bool has_tail;
-        walk_tile<Emit, kCompact>(job, g_jump, zig, fi, work[threadIdx.x >> 6], mk128(&states[2 * tile]), 0u, 0, 0,
+        walk_tile<Emit, kCompact>(job, g_jump, zig, fi, work[threadIdx.x >> 6], s, s2, 0u, 0, 0,
                                   (int16_t VKX_GLOBAL *)(job.rec + (tile - job.tile_base) * kSlot), nullptr, nullptr,
                                   count, carry, start0, emit0, has_tail, flags, nullptr);
         if (__lane_id() == 0) {
@@ -864,7 +899,9 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
                 } else {
                     uint64_t s0, e0;
                     bool ht;
-                    walk_tile<EmitNone, kCount>(job, g_jump, zig, fi, work[0], mk128(&st[2 * j]), c, 0, 0, nullptr, nullptr, nullptr, count, out,
+                    u128 s, s2;
+                    tile_lane_states(g_jump, job, mk128(&st[2 * j]), s, s2);
+                    walk_tile<EmitNone, kCount>(job, g_jump, zig, fi, work[0], s, s2, c, 0, 0, nullptr, nullptr, nullptr, count, out,
                                                 s0, e0, ht, flags, nullptr);
                     simulated = true;
                 }
@@ -1290,7 +1327,9 @@ __global__ void __launch_bounds__(64) k_np_place_walk(const NpJob *__restrict__ 
             bool ht;
             void *dst = job.dst;
             if (TILES) dst = (void *)((intptr_t)(job.rec + (tile - job.tile_base) * kSlot) - 2 * (intptr_t)p.prefix);
-            walk_tile<Emit, kEmit>(job, g_jump, zig, fi, work[0], mk128(&states[2 * tile]), p.c_in & ~kIrregular,
+            u128 s, s2;
+            tile_lane_states(g_jump, job, mk128(&states[2 * tile]), s, s2);
+            walk_tile<Emit, kEmit>(job, g_jump, zig, fi, work[0], s, s2, p.c_in & ~kIrregular,
                                    (long long)p.prefix, (tile - job.tile_base) * kTile, nullptr, nullptr, dst, count, carry, start0, emit0, ht,
                                    flags, &results[j].draws);
             if (flags) atomicOr(&results[j].flags, flags);
@@ -1534,7 +1573,8 @@ static int np_chunk_front(vkx_ctx *ctx, NpChunk &c)
         // (the emitter only decides how a draw becomes an int16 step: the same for the three int16 kinds)
         VKX_TIMED_MAJOR(ctx, "k_np_draw");
         const unsigned wgc = (unsigned)((total_tiles + (long long)kDrawWaves * tiles_per_wave - 1) / ((long long)kDrawWaves * tiles_per_wave));
-        k_np_draw_compact<EmitI16><<<wgc, 64 * kDrawWaves, 0, ctx->stream>>>(dj, n_jobs, total_tiles, states, info, res, tabs);
+        const long long run = (total_tiles + (long long)wgc * kDrawWaves - 1) / ((long long)wgc * kDrawWaves);
+        k_np_draw_compact<EmitI16><<<wgc, 64 * kDrawWaves, 0, ctx->stream>>>(dj, n_jobs, total_tiles, run, states, info, res, tabs);
         VKX_LAUNCH_CHECK();
         return VKX_OK;
     }
