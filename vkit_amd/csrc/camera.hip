@@ -350,7 +350,9 @@ VKX_EXPORT int vkx_camera_states_dev(vkx_ctx *ctx, const vkx_camera_config *conf
     int rc;
     hipStream_t st = vkx_stream_by_id(ctx, stream, &rc);
     if (rc) return rc;
-    std::vector<StateDev> host((size_t)n);
+    vkx_tables tab(ctx);            // the descriptors, written where they are staged
+    if ((rc = tab.take((size_t)n * sizeof(StateDev)))) return rc;
+    StateDev *host = (StateDev *)memset(tab.host, 0, tab.bytes);
     size_t z_total = 0;
     for (int i = 0; i < n; i++) {
         StateDev &s = host[i];
@@ -362,20 +364,17 @@ VKX_EXPORT int vkx_camera_states_dev(vkx_ctx *ctx, const vkx_camera_config *conf
         s.z = (double *)(z_total * sizeof(double));     // offset for now
         if (s.kind == VKX_CAMERA_CUBIC_CURVE) z_total += (size_t)s.m.rows * s.m.cols;
     }
-    const size_t desc_bytes = ((size_t)n * sizeof(StateDev) + 255) & ~(size_t)255, out_bytes = ((size_t)n * sizeof(vkx_grid_state) + 255) & ~(size_t)255;
+    const size_t desc_bytes = vkx_align256(tab.bytes), out_bytes = vkx_align256((size_t)n * sizeof(vkx_grid_state));
     // (grown with every stream of the context drained: vkx_scratch_reserve)
     if ((rc = vkx_scratch_reserve(ctx, &ctx->camera_work, desc_bytes + out_bytes + z_total * sizeof(double)))) return rc;
     unsigned char *base = (unsigned char *)ctx->camera_work.ptr;
     for (int i = 0; i < n; i++) host[i].z = (double *)(base + desc_bytes + out_bytes) + (size_t)(uintptr_t)host[i].z / sizeof(double);
-    void *ring = nullptr;
-    if ((rc = vkx_desc_ring_take(ctx, (size_t)n * sizeof(StateDev), &ring))) return rc;
-    memcpy(ring, host.data(), (size_t)n * sizeof(StateDev));
     vkx_device_guard guard(ctx);
     hipStream_t main_stream = ctx->stream;
     // the previous call's states may still be read from this scratch by ITS kernel only (same stream order when the caller keeps to
     // one stream; a caller that alternates streams synchronises in between, as ChainBatch does)
     ctx->stream = st;
-    rc = vkx_small_to_device(ctx, base, ring, (size_t)n * sizeof(StateDev));
+    rc = tab.small_to(base);
     if (!rc) {
         VKX_TIMED(ctx, "k_camera_states");
         k_camera_states<<<n, 256, 0, st>>>((const StateDev *)base, (vkx_grid_state *)(base + desc_bytes));

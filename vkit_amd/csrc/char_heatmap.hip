@@ -180,18 +180,6 @@ __global__ void __launch_bounds__(256) k_char_heatmap_resolve(int *__restrict__ 
     }
 }
 
-int stage(vkx_ctx *ctx, vkx_scratch *s, const void *host, size_t bytes)
-{
-    void *staged = nullptr;
-    int rc = vkx_desc_ring_take(ctx, bytes, &staged);
-    if (rc) return rc;
-    memcpy(staged, host, bytes);
-    if ((rc = vkx_scratch_reserve(ctx, s, std::max(bytes, (size_t)64 << 10)))) return rc;
-    vkx_device_guard guard(ctx);
-    VKX_HIP(hipMemcpyAsync(s->ptr, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return VKX_OK;
-}
-
 // The output planes of one call, in the order of the checks and the copies of the host form.
 struct OutPlane { void *p; size_t elem; };
 
@@ -273,22 +261,22 @@ VKX_EXPORT int vkx_char_heatmap_fresh_dev(vkx_ctx *ctx, const vkx_char_heatmap_c
     tile_start[n] = (int)tiles;
 
     // one staged block: template, quads, boxes, tile starts
-    const size_t tmpl_bytes = ((size_t)E * E * 4 + 255) & ~(size_t)255;
-    const size_t quad_bytes = ((size_t)n * 64 + 255) & ~(size_t)255;
-    const size_t box_bytes = ((size_t)n * 16 + 255) & ~(size_t)255;
-    std::vector<char> block(tmpl_bytes + quad_bytes + box_bytes + sizeof(int) * tile_start.size());
-    memcpy(block.data(), config->template_host, (size_t)E * E * 4);
+    vkx_tables tab(ctx);
+    const size_t tmpl_off = tab.add((size_t)E * E * 4), quad_off = tab.add((size_t)n * 64), box_off = tab.add((size_t)n * 16);
+    const size_t tile_off = tab.add(sizeof(int) * tile_start.size());
+    if ((rc = tab.take())) return rc;
+    memcpy(tab.at<float>(tmpl_off), config->template_host, (size_t)E * E * 4);
     if (n) {
-        memcpy(block.data() + tmpl_bytes, quads_host, (size_t)n * 64);
-        memcpy(block.data() + tmpl_bytes + quad_bytes, boxes.data(), (size_t)n * 16);
+        memcpy(tab.at<double>(quad_off), quads_host, (size_t)n * 64);
+        memcpy(tab.at<int>(box_off), boxes.data(), (size_t)n * 16);
     }
-    memcpy(block.data() + tmpl_bytes + quad_bytes + box_bytes, tile_start.data(), sizeof(int) * tile_start.size());
-    if ((rc = stage(ctx, &ctx->heat_table, block.data(), block.size()))) return rc;
+    memcpy(tab.at<int>(tile_off), tile_start.data(), sizeof(int) * tile_start.size());
+    if ((rc = tab.copy_to(&ctx->heat_table, (size_t)64 << 10))) return rc;
     char *base = (char *)ctx->heat_table.ptr;
-    const float *tmpl_dev = (const float *)base;
-    const double *quads_dev = (const double *)(base + tmpl_bytes);
-    const int *boxes_dev = (const int *)(base + tmpl_bytes + quad_bytes);
-    const int *tiles_dev = (const int *)(base + tmpl_bytes + quad_bytes + box_bytes);
+    const float *tmpl_dev = (const float *)(base + tmpl_off);
+    const double *quads_dev = (const double *)(base + quad_off);
+    const int *boxes_dev = (const int *)(base + box_off);
+    const int *tiles_dev = (const int *)(base + tile_off);
     if ((rc = vkx_scratch_reserve(ctx, &ctx->heat_geo, std::max(sizeof(CharHeat) * (size_t)n, (size_t)64 << 10)))) return rc;
     CharHeat *heat = (CharHeat *)ctx->heat_geo.ptr;
 
@@ -352,7 +340,7 @@ VKX_EXPORT int vkx_char_heatmap_fresh(vkx_ctx *ctx, const vkx_char_heatmap_confi
     size_t at[7], bytes = 0;
     for (int k = 0; k < n_out; k++) {
         at[k] = bytes;
-        bytes += (page * out[k].elem + 255) & ~(size_t)255;
+        bytes += vkx_align256(page * out[k].elem);
     }
     if ((rc = vkx_scratch_reserve(ctx, &ctx->heat_host, bytes))) return rc;
     char *base = (char *)ctx->heat_host.ptr;

@@ -227,18 +227,6 @@ bool bytes_overlap(const void *a, size_t an, const void *b, size_t bn)
     return vkx_planes_overlap(a, 1, 0, an, b, 1, 0, bn);
 }
 
-int stage(vkx_ctx *ctx, vkx_scratch *s, const void *host, size_t bytes)
-{
-    void *staged = nullptr;
-    int rc = vkx_desc_ring_take(ctx, bytes, &staged);
-    if (rc) return rc;
-    memcpy(staged, host, bytes);
-    if ((rc = vkx_scratch_reserve(ctx, s, std::max(bytes, (size_t)64 << 10)))) return rc;
-    vkx_device_guard guard(ctx);
-    VKX_HIP(hipMemcpyAsync(s->ptr, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return VKX_OK;
-}
-
 // Argument checks shared by both forms.
 int check_sets(const vkx_char_set *sets, int n_sets, int L, int h, int w, long long *total)
 {
@@ -292,8 +280,12 @@ VKX_EXPORT int vkx_char_mask_ellipse_sets_fresh_dev(vkx_ctx *ctx, int internal_s
     const int n = (int)total;
     const int R = (int)std::ceil(L / std::sqrt(2.0));       // math.ceil(L / math.sqrt(2))
 
-    // the char table, in set order
-    std::vector<CharIn> table((size_t)std::max(n, 1));
+    // the char table, in set order, written where it is staged
+    vkx_tables tab(ctx);
+    tab.add(sizeof(CharIn) * (size_t)std::max(n, 1));
+    if ((rc = tab.take())) return rc;
+    CharIn *table = tab.at<CharIn>(0);
+    if (!n) table[0] = CharIn();
     std::vector<int> firsts(n_sets);
     int g = 0;
     for (int s = 0; s < n_sets; s++) {
@@ -311,12 +303,12 @@ VKX_EXPORT int vkx_char_mask_ellipse_sets_fresh_dev(vkx_ctx *ctx, int internal_s
         }
     }
     const size_t page = (size_t)h * w;
-    const size_t geo_bytes = (sizeof(CharGeo) * (size_t)n + 255) & ~(size_t)255;
-    const size_t box_bytes = (sizeof(int) * 5 * (size_t)n + 255) & ~(size_t)255;
+    const size_t geo_bytes = vkx_align256(sizeof(CharGeo) * (size_t)n);
+    const size_t box_bytes = vkx_align256(sizeof(int) * 5 * (size_t)n);
     if ((rc = vkx_scratch_reserve(ctx, &ctx->char_geo, std::max(geo_bytes + box_bytes, (size_t)64 << 10)))) return rc;
     CharGeo *geo = (CharGeo *)ctx->char_geo.ptr;
     int *boxes = (int *)((char *)ctx->char_geo.ptr + geo_bytes);
-    if ((rc = stage(ctx, &ctx->char_table, table.data(), sizeof(CharIn) * table.size()))) return rc;
+    if ((rc = tab.copy_to(&ctx->char_table, (size_t)64 << 10))) return rc;
     const CharIn *chars = (const CharIn *)ctx->char_table.ptr;
 
     // 1. setup, then the boxes and statuses to the host: the call's one synchronisation
@@ -366,7 +358,12 @@ VKX_EXPORT int vkx_char_mask_ellipse_sets_fresh_dev(vkx_ctx *ctx, int internal_s
         if (ctx->char_owner_zeroed < owner_bytes) VKX_HIP(hipMemsetAsync(ctx->char_owner.ptr, 0, ctx->char_owner.cap, ctx->stream));
     }
     ctx->char_owner_zeroed = 0;
-    SetDev sd[kMaxSets];
+    // one staged block: sets, tile starts, packed offsets
+    vkx_tables lay(ctx);
+    const size_t sets_off = lay.add(sizeof(SetDev) * kMaxSets), ts_off = lay.add(sizeof(int) * tile_start.size());
+    const size_t packed_off = lay.add(sizeof(long long) * packed.size());
+    if ((rc = lay.take())) return rc;
+    SetDev *sd = lay.at<SetDev>(sets_off);
     for (int s = 0; s < n_sets; s++) {
         sd[s].mask = sets[s].mask;
         sd[s].score = sets[s].score;
@@ -375,17 +372,12 @@ VKX_EXPORT int vkx_char_mask_ellipse_sets_fresh_dev(vkx_ctx *ctx, int internal_s
         sd[s].first = firsts[s];
         sd[s].n = sets[s].n_chars;
     }
-    // one staged block: sets, tile starts, packed offsets
-    const size_t sets_bytes = (sizeof(SetDev) * kMaxSets + 255) & ~(size_t)255;
-    const size_t ts_bytes = (sizeof(int) * tile_start.size() + 255) & ~(size_t)255;
-    std::vector<char> block(sets_bytes + ts_bytes + sizeof(long long) * packed.size());
-    memcpy(block.data(), sd, sizeof(SetDev) * n_sets);
-    memcpy(block.data() + sets_bytes, tile_start.data(), sizeof(int) * tile_start.size());
-    memcpy(block.data() + sets_bytes + ts_bytes, packed.data(), sizeof(long long) * packed.size());
-    if ((rc = stage(ctx, &ctx->char_layout, block.data(), block.size()))) return rc;
-    const SetDev *sets_dev = (const SetDev *)ctx->char_layout.ptr;
-    const int *tile_dev = (const int *)((char *)ctx->char_layout.ptr + sets_bytes);
-    const long long *packed_dev = (const long long *)((char *)ctx->char_layout.ptr + sets_bytes + ts_bytes);
+    memcpy(lay.at<int>(ts_off), tile_start.data(), sizeof(int) * tile_start.size());
+    memcpy(lay.at<long long>(packed_off), packed.data(), sizeof(long long) * packed.size());
+    if ((rc = lay.copy_to(&ctx->char_layout, (size_t)64 << 10))) return rc;
+    const SetDev *sets_dev = (const SetDev *)((char *)ctx->char_layout.ptr + sets_off);
+    const int *tile_dev = (const int *)((char *)ctx->char_layout.ptr + ts_off);
+    const long long *packed_dev = (const long long *)((char *)ctx->char_layout.ptr + packed_off);
 
     if (tiles) {
         VKX_TIMED(ctx, "k_char_mask_raster");
@@ -415,11 +407,11 @@ VKX_EXPORT int vkx_char_mask_ellipse_sets_fresh(vkx_ctx *ctx, int internal_side_
     std::vector<size_t> at(3 * n_sets);
     for (int s = 0; s < n_sets; s++) {
         at[3 * s] = bytes;
-        bytes += sets[s].mask ? (page + 255) & ~(size_t)255 : 0;
+        bytes += sets[s].mask ? vkx_align256(page) : 0;
         at[3 * s + 1] = bytes;
-        bytes += sets[s].score ? (4 * page + 255) & ~(size_t)255 : 0;
+        bytes += sets[s].score ? vkx_align256(4 * page) : 0;
         at[3 * s + 2] = bytes;
-        bytes += sets[s].char_masks ? ((size_t)sets[s].char_masks_cap + 255) & ~(size_t)255 : 0;
+        bytes += sets[s].char_masks ? vkx_align256((size_t)sets[s].char_masks_cap) : 0;
     }
     if ((rc = vkx_scratch_reserve(ctx, &ctx->char_host, std::max(bytes, (size_t)256)))) return rc;
     char *base = (char *)ctx->char_host.ptr;

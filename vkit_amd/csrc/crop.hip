@@ -160,20 +160,6 @@ int check_windows(const vkx_crop_window *windows, int n, int h, int w, int crop)
     return VKX_OK;
 }
 
-// a host table into the device slot `s`, on the compute stream (staged through the page-locked ring, which stays
-// untouched until the copy has run)
-int stage_table(vkx_ctx *ctx, vkx_scratch *s, const void *host, size_t bytes)
-{
-    void *staged = nullptr;
-    int rc = vkx_desc_ring_take(ctx, bytes, &staged);
-    if (rc) return rc;
-    memcpy(staged, host, bytes);
-    if ((rc = vkx_scratch_reserve(ctx, s, std::max(bytes, (size_t)64 << 10)))) return rc;   // grows (and syncs) rarely
-    vkx_device_guard guard(ctx);
-    VKX_HIP(hipMemcpyAsync(s->ptr, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return VKX_OK;
-}
-
 bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
 {
     return vkx_planes_overlap(a, 1, 0, a_bytes, b, 1, 0, b_bytes);
@@ -199,7 +185,10 @@ VKX_EXPORT int vkx_crop_count_dev(vkx_ctx *ctx, const uint8_t *image, int h, int
     if (image) VKX_REQUIRE(!ranges_overlap(image, page * cn, partials, out_bytes), "source and destination overlap");
     const vkx_crop_window *windows = nullptr;
     if (n_windows) {
-        if ((rc = stage_table(ctx, &ctx->crop_windows, windows_host, sizeof(vkx_crop_window) * n_windows))) return rc;
+        vkx_tables tab(ctx);
+        if ((rc = tab.take(sizeof(vkx_crop_window) * n_windows))) return rc;
+        memcpy(tab.host, windows_host, tab.bytes);
+        if ((rc = tab.copy_to(&ctx->crop_windows, (size_t)64 << 10))) return rc;   // grows (and syncs) rarely
         windows = (const vkx_crop_window *)ctx->crop_windows.ptr;
     }
     dim3 grid(n_parts, 1 + n_windows);
@@ -250,8 +239,12 @@ VKX_EXPORT int vkx_crop_planes_dev(vkx_ctx *ctx, int h, int w, int core_size, in
         }
     }
     if (n_planes == 0) return VKX_OK;
-    if ((rc = stage_table(ctx, &ctx->crop_windows, windows_host, sizeof(vkx_crop_window) * n_windows))) return rc;
-    if ((rc = stage_table(ctx, &ctx->crop_planes, planes_host, sizeof(vkx_crop_plane) * n_planes))) return rc;
+    // the two tables keep a slot each (the count pass leaves its windows in theirs), so each travels as a copy of its own
+    vkx_tables wins(ctx), planes(ctx);
+    if ((rc = wins.take(sizeof(vkx_crop_window) * n_windows)) || (rc = planes.take(sizeof(vkx_crop_plane) * n_planes))) return rc;
+    memcpy(wins.host, windows_host, wins.bytes);
+    memcpy(planes.host, planes_host, planes.bytes);
+    if ((rc = wins.copy_to(&ctx->crop_windows, (size_t)64 << 10)) || (rc = planes.copy_to(&ctx->crop_planes, (size_t)64 << 10))) return rc;
     dim3 grid(vkx_blocks(crop, 64), vkx_blocks(crop, 4), n_planes);
     {
         VKX_TIMED(ctx, "k_crop_planes");

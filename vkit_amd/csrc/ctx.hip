@@ -264,7 +264,13 @@ static int ring_quiesce(vkx_ctx *ctx)
 
 int vkx_desc_ring_take(vkx_ctx *ctx, size_t bytes, void **hptr)
 {
-    bytes = (bytes + 255) & ~(size_t)255;
+    bytes = vkx_align256(bytes);
+    if (ctx->desc_hold && (bytes > ctx->desc_cap || ctx->desc_off + bytes > ctx->desc_cap)) {
+        // the block a not-yet-queued kernel reads in place must neither be freed nor handed out again
+        ctx->desc_hold = 2;
+        vkx_set_error("descriptor ring: %zu more bytes do not fit behind a block that is held for reading in place", bytes);
+        return VKX_ERR_NOMEM;
+    }
     if (bytes > ctx->desc_cap) {
         // (re)allocate: nothing queued may still read the old ring
         vkx_device_guard guard(ctx);
@@ -272,6 +278,7 @@ int vkx_desc_ring_take(vkx_ctx *ctx, size_t bytes, void **hptr)
         if (qrc) return qrc;
         if (ctx->desc_ring) VKX_HIP(hipHostFree(ctx->desc_ring));
         ctx->desc_ring = nullptr;
+        ctx->desc_cap = ctx->desc_off = 0;     // a failed allocation leaves an empty ring: the next take allocates again
         const size_t cap = bytes * 4 > ((size_t)4 << 20) ? bytes * 4 : ((size_t)4 << 20);
         VKX_HIP(hipHostMalloc((void **)&ctx->desc_ring, cap, hipHostMallocDefault));
         ctx->desc_cap = cap;

@@ -261,15 +261,11 @@ VKX_EXPORT int vkx_ellipse_mask_u8_dev(vkx_ctx *ctx, uint8_t *mask, ptrdiff_t st
         ellipse_segments(cx, cy, ax, ay, segs);
     }
     if (segs.empty()) return VKX_OK;
-    vkx_device_guard guard(ctx);
-    const size_t bytes = segs.size() * sizeof(Segment);
-    void *staged = nullptr;
-    int rc = vkx_desc_ring_take(ctx, bytes, &staged);
+    vkx_tables tab(ctx);
+    int rc = tab.take(segs.size() * sizeof(Segment));
     if (rc) return rc;
-    memcpy(staged, segs.data(), bytes);
-    rc = vkx_scratch_reserve(ctx, &ctx->misc, bytes);
-    if (rc) return rc;
-    VKX_HIP(hipMemcpyAsync(ctx->misc.ptr, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(tab.host, segs.data(), tab.bytes);
+    if ((rc = tab.copy_to(&ctx->misc))) return rc;
     {
         VKX_TIMED(ctx, "k_ellipse_segments");
         k_ellipse_segments<<<vkx_blocks(segs.size(), 4), 256, 0, ctx->stream>>>((const Segment *)ctx->misc.ptr, (int)segs.size(),

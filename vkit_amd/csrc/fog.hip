@@ -257,8 +257,7 @@ VKX_EXPORT int vkx_glass_round_dev(vkx_ctx *ctx, int32_t *pos_y, int32_t *pos_x,
     VKX_REQUIRE(ctx->glass_win.ptr && ctx->glass_win.cap >= sizeof(unsigned long long) * (size_t)h * w, "vkx_glass_init_dev first");
     vkx_device_guard guard(ctx);
     int rc;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t part = up(sizeof(int) * (size_t)n);
+    const size_t part = vkx_align256(sizeof(int) * (size_t)n);
     if ((rc = vkx_scratch_reserve(ctx, &ctx->fog_work, 5 * part))) return rc;
     unsigned char *base = (unsigned char *)ctx->fog_work.ptr;
     int *d_jy = (int *)base, *d_jx = (int *)(base + part), *d_to = (int *)(base + 2 * part);

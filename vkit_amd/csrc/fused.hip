@@ -1242,25 +1242,24 @@ int vkx_chain_plan_setup(vkx_ctx *ctx, vkx_chain_plan *p)
     if (n_items > 65535) return VKX_ERR_UNSUPPORTED;      // gridDim.y
     if ((rc = vkx_scratch_reserve(ctx, s_bins, sizeof(TileBin) * nbins))) return rc;
     const size_t items_bytes = sizeof(ItemDev) * (size_t)n_items, prefix_bytes = sizeof(int) * p->prefix.size();
-    const size_t items_off = 0, prefix_off = (items_bytes + 255) & ~(size_t)255;
-    const size_t misc_bytes = prefix_off + prefix_bytes;
+    vkx_tables tab(ctx);
+    const size_t items_off = tab.add(items_bytes), prefix_off = tab.add(prefix_bytes), misc_bytes = tab.bytes;
     if ((rc = vkx_scratch_reserve(ctx, s_misc, misc_bytes))) return rc;
     if (!p->elements && (rc = vkx_hsv_tables(ctx, (const void **)&p->lut))) return rc;
     unsigned char *misc = (unsigned char *)s_misc->ptr;
     // the descriptors travel through the ctx's page-locked ring: the copy is queued and the launch returns without a
     // stream synchronisation (host-array pipelines keep several launches in flight)
-    void *ring = nullptr;
-    if ((rc = vkx_desc_ring_take(ctx, misc_bytes, &ring))) return rc;
-    memcpy((unsigned char *)ring + items_off, p->dev.data(), items_bytes);
-    memcpy((unsigned char *)ring + prefix_off, p->prefix.data(), prefix_bytes);
+    if ((rc = tab.take())) return rc;
+    memcpy(tab.at<char>(items_off), p->dev.data(), items_bytes);
+    memcpy(tab.at<char>(prefix_off), p->prefix.data(), prefix_bytes);
     p->d_items = (const ItemDev *)(misc + items_off);
     p->d_cell_prefix = (const int *)(misc + prefix_off);
     p->bins = (TileBin *)s_bins->ptr;
     p->cells = (vkc::CellC *)s_cells->ptr;
     p->deferred = (int *)((unsigned char *)s_cells->ptr + cells_bytes);
     {
-        void *ring_dev = nullptr;
-        VKX_HIP(hipHostGetDevicePointer(&ring_dev, ring, 0));
+        const unsigned char *ring_dev = tab.mapped();
+        if (!ring_dev) { vkx_set_error("%s: the descriptor ring is not mapped into the device's address space", __func__); return VKX_ERR_HIP; }
         const size_t n_words = (misc_bytes + 3) / 4;
         VKX_TIMED(ctx, "k_chain_prologue");
         k_chain_prologue<<<vkx_blocks(std::max(n_words, nbins), 256), 256, 0, ctx->stream>>>((uint32_t *)misc, (const uint32_t *)ring_dev,

@@ -226,18 +226,18 @@ VKX_EXPORT int vkx_grid_project_points(vkx_ctx *ctx, const int32_t *src_vertices
     VKX_REQUIRE(pts_xy_host && pts_smooth_xy_host && out_xy_host, "NULL argument");
     const size_t vbytes = sizeof(int32_t) * 2 * (size_t)rows * cols;
     const size_t ibytes = sizeof(int32_t) * 2 * (size_t)n, dbytes = sizeof(double) * 2 * (size_t)n;
-    const size_t off_dv = (vbytes + 255) & ~(size_t)255, off_pi = off_dv * 2, off_ps = off_pi + ((ibytes + 255) & ~(size_t)255);
-    const size_t off_out = off_ps + ((dbytes + 255) & ~(size_t)255), off_bad = off_out + ((dbytes + 255) & ~(size_t)255);
+    vkx_tables tab(ctx);          // (the source lattice is the first part, at offset 0)
+    const size_t off_sv = tab.add(vbytes), off_dv = tab.add(vbytes), off_pi = tab.add(ibytes), off_ps = tab.add(dbytes);
+    const size_t off_out = tab.add(dbytes), off_bad = tab.add(256);
     // Everything the kernel reads, and what it writes, in ONE block of the page-locked (mapped) ring: the lattices and the points are
     // read once, the results are read by the host right after -- the kernel works on the host block in place and the call is one
     // dispatch (it was four copies in, a memset, the kernel and two copies out: 5 - 7 dispatches of a page's 98).  The flag is a plain
     // store (any offending index serves; atomics on host memory need PCIe atomics).
-    void *ring = nullptr;
-    int rc = off_bad + 256 <= ((size_t)8 << 20) ? vkx_desc_ring_take(ctx, off_bad + 256, &ring) : VKX_ERR_UNSUPPORTED;
-    const uint8_t *mapped = rc == VKX_OK ? (const uint8_t *)vkx_ring_device_ptr(ring) : nullptr;
+    int rc = tab.bytes <= ((size_t)8 << 20) ? tab.take() : VKX_ERR_UNSUPPORTED;
+    const uint8_t *mapped = rc == VKX_OK ? tab.mapped() : nullptr;
     if (mapped) {
-        uint8_t *host = (uint8_t *)ring;
-        memcpy(host, src_vertices_host, vbytes);
+        uint8_t *host = tab.host;
+        memcpy(host + off_sv, src_vertices_host, vbytes);
         memcpy(host + off_dv, dst_vertices_host, vbytes);
         memcpy(host + off_pi, pts_xy_host, ibytes);
         memcpy(host + off_ps, pts_smooth_xy_host, dbytes);
@@ -254,7 +254,7 @@ VKX_EXPORT int vkx_grid_project_points(vkx_ctx *ctx, const int32_t *src_vertices
         memcpy(out_xy_host, host + off_out, dbytes);
         return VKX_OK;
     }
-    rc = vkx_scratch_reserve(ctx, &ctx->stage[0], off_bad + 256);
+    rc = vkx_scratch_reserve(ctx, &ctx->stage[0], tab.bytes);
     if (rc) return rc;
     uint8_t *base = (uint8_t *)ctx->stage[0].ptr;
     VKX_HIP(hipMemcpyAsync(base, src_vertices_host, vbytes, hipMemcpyHostToDevice, ctx->stream));

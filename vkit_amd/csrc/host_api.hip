@@ -11,7 +11,7 @@ namespace {
 // hipMemcpy2DAsync so arbitrary host row pitches are honoured.
 class HostStage {
 public:
-    explicit HostStage(vkx_ctx *ctx) : ctx_(ctx) {}
+    explicit HostStage(vkx_ctx *ctx) : ctx_(ctx), mapped_(ctx) {}
 
     // returns the plane id; device pitch is row_bytes (tightly packed)
     int add(const void *host_in, void *host_out, size_t row_bytes, int rows, ptrdiff_t host_pitch)
@@ -20,7 +20,7 @@ public:
         p.in = host_in; p.out = host_out; p.row_bytes = row_bytes; p.rows = rows; p.pitch = host_pitch;
         p.off = total_;
         if (rows > 1 && (host_pitch < 0 || (size_t)host_pitch < row_bytes)) bad_pitch_ = true;   // vkx.h: a pitch of at least one row
-        total_ += (row_bytes * (size_t)(rows > 0 ? rows : 0) + 255) & ~(size_t)255;
+        total_ += vkx_align256(row_bytes * (size_t)(rows > 0 ? rows : 0));
         planes_.push_back(p);
         return (int)planes_.size() - 1;
     }
@@ -43,7 +43,7 @@ public:
         constexpr size_t kRingMax = (size_t)48 << 20;
         size_t in_total = 0;
         for (auto &p : planes_)
-            if (p.in && p.row_bytes && p.rows > 0) in_total += (p.row_bytes * (size_t)p.rows + 255) & ~(size_t)255;
+            if (p.in && p.row_bytes && p.rows > 0) in_total += vkx_align256(p.row_bytes * (size_t)p.rows);
         uint8_t *ring = nullptr;
         if (in_total > 0 && in_total <= kRingMax) {
             void *r = nullptr;
@@ -73,7 +73,7 @@ public:
         };
         for (auto &p : planes_) {
             if (!p.in || p.row_bytes == 0 || p.rows <= 0) continue;
-            const size_t bytes = p.row_bytes * (size_t)p.rows, padded = (bytes + 255) & ~(size_t)255;
+            const size_t bytes = p.row_bytes * (size_t)p.rows, padded = vkx_align256(bytes);
             if (ring) {
                 // device offsets of consecutive planes are contiguous (add() pads to 256 like the ring does)
                 if (run_bytes && run_dev + run_bytes != p.off) VKX_HIP(flush());
@@ -103,16 +103,16 @@ public:
     // the page-locked ring and read there, in place, over the link -- no copy to device memory at all.  The link carries each byte
     // once either way; what goes is the copy's dispatches (a C4 page staged 13 MB of layer planes with 9 runtime copy kernels) and,
     // for pageable sources, the runtime's own staging pass.  false: too large for the ring or not mappable (use commit()).
+    // The ring is held (vkx_tables::mapped) until release_hold() or the end of the call: a further take of the call (the composite's
+    // tile tables) cannot wrap onto the planes or free them.
     bool commit_mapped()
     {
         if (bad_pitch_ || total_ == 0 || total_ > ((size_t)48 << 20)) return false;   // commit() reports a bad pitch
         for (auto &p : planes_)
             if (p.out) return false;             // outputs need device memory + finish()
-        void *r = nullptr;
-        if (vkx_desc_ring_take(ctx_, total_, &r) != VKX_OK) return false;
-        uint8_t *mapped = (uint8_t *)const_cast<void *>(vkx_ring_device_ptr(r));
+        if (mapped_.take(total_) != VKX_OK) return false;
+        uint8_t *mapped = mapped_.mapped(), *ring = mapped_.host;
         if (!mapped) return false;
-        uint8_t *ring = (uint8_t *)r;
         for (auto &p : planes_) {
             if (!p.in || p.row_bytes == 0 || p.rows <= 0) continue;
             if ((size_t)p.pitch == p.row_bytes || p.rows == 1) memcpy(ring + p.off, p.in, p.row_bytes * (size_t)p.rows);
@@ -122,6 +122,8 @@ public:
         base_ = mapped;
         return true;
     }
+    // true: a take was refused while the planes were held -- the call failed for that, nothing of it is queued; commit() and run it again
+    bool release_hold() { return mapped_.release(); }
 
     template <class T> T *dev(int id) const { return id < 0 ? nullptr : (T *)(base_ + planes_[id].off); }
     size_t total_bytes() const { return total_; }
@@ -153,6 +155,7 @@ private:
     std::vector<Plane> planes_;
     size_t total_ = 0;
     bool bad_pitch_ = false;
+    vkx_tables mapped_;           // the block of commit_mapped(), and its hold on the ring
     uint8_t *base_ = nullptr;
 };
 
@@ -454,14 +457,24 @@ VKX_EXPORT int vkx_fill_u8_dev_host_layers(vkx_ctx *ctx, uint8_t *dst_dev, int h
     static const int map_env = [] { const char *e = getenv("VKX_LAYERS_MAPPED"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     const bool mapped = map_env >= 0 ? map_env != 0 : st.total_bytes() <= ((size_t)64 << 10);
     if (!mapped || !st.commit_mapped()) VKX_TRY(st.commit(true));
-    std::vector<vkx_layer> dl(layers, layers + n_layers);
-    for (int i = 0; i < n_layers; i++) {
-        if (mid[i] >= 0) { dl[i].mask = st.dev<uint8_t>(mid[i]); dl[i].mask_stride = layers[i].width; }
-        if (aid[i] >= 0) { dl[i].alpha = st.dev<float>(aid[i]); dl[i].alpha_stride_el = layers[i].width; }
-        if (vid[i] >= 0) { dl[i].value = st.dev<uint8_t>(vid[i]); dl[i].value_stride = (ptrdiff_t)layers[i].width * cn; }
-        dl[i].mode &= ~kOnDevice;
+    auto composite = [&] {
+        std::vector<vkx_layer> dl(layers, layers + n_layers);
+        for (int i = 0; i < n_layers; i++) {
+            if (mid[i] >= 0) { dl[i].mask = st.dev<uint8_t>(mid[i]); dl[i].mask_stride = layers[i].width; }
+            if (aid[i] >= 0) { dl[i].alpha = st.dev<float>(aid[i]); dl[i].alpha_stride_el = layers[i].width; }
+            if (vid[i] >= 0) { dl[i].value = st.dev<uint8_t>(vid[i]); dl[i].value_stride = (ptrdiff_t)layers[i].width * cn; }
+            dl[i].mode &= ~kOnDevice;
+        }
+        return vkx_fill_u8_dev(ctx, dst_dev, h, w, cn, dst_stride, dl.data(), n_layers);
+    };
+    int rc = composite();
+    // the composite's tile tables did not fit behind the planes held in the ring (it takes them before its first launch):
+    // the planes go to device memory instead, as above
+    if (st.release_hold()) {
+        VKX_TRY(st.commit(true));
+        rc = composite();
     }
-    return vkx_fill_u8_dev(ctx, dst_dev, h, w, cn, dst_stride, dl.data(), n_layers);
+    return rc;
 }
 
 VKX_EXPORT int vkx_fill_u8(vkx_ctx *ctx, uint8_t *dst, int h, int w, int cn, ptrdiff_t dst_stride,

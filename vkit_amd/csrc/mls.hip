@@ -306,9 +306,9 @@ VKX_EXPORT int vkx_mls_project(vkx_ctx *ctx, const float *src_handles, const flo
     if (n_vertices == 0) return VKX_OK;
     VKX_REQUIRE(vertices_xy && out_xy, "NULL argument");
     vkx_device_guard guard(ctx);
-    const size_t hf = (sizeof(float) * 2 * (size_t)n_handles + 255) & ~(size_t)255;
-    const size_t hdb = (sizeof(double) * 2 * (size_t)n_handles + 255) & ~(size_t)255;
-    const size_t vb = (sizeof(double) * 2 * (size_t)n_vertices + 255) & ~(size_t)255;
+    const size_t hf = vkx_align256(sizeof(float) * 2 * (size_t)n_handles);
+    const size_t hdb = vkx_align256(sizeof(double) * 2 * (size_t)n_handles);
+    const size_t vb = vkx_align256(sizeof(double) * 2 * (size_t)n_vertices);
     const size_t off_q = hf, off_ps = 2 * hf, off_qs = off_ps + hdb, off_v = off_qs + hdb, off_out = off_v + vb,
                  off_bad = off_out + vb;
     int rc = vkx_scratch_reserve(ctx, &ctx->stage[0], off_bad + 256);
@@ -347,8 +347,11 @@ VKX_EXPORT int vkx_mls_states_dev(vkx_ctx *ctx, const vkx_mls_config *configs, i
     int rc;
     hipStream_t st = vkx_stream_by_id(ctx, stream, &rc);
     if (rc) return rc;
+    vkx_tables tab(ctx);           // the descriptors, then every state's handle tables
+    tab.add((size_t)n * sizeof(MlsStateDev));
     std::vector<MlsStateDev> host((size_t)n);
-    size_t table_bytes = 0, smooth_doubles = 0;
+    std::vector<size_t> handles_off((size_t)n);
+    size_t smooth_doubles = 0;
     int max_vertices = 0, max_handles = 0;
     for (int i = 0; i < n; i++) {
         const vkx_mls_config &c = configs[i];
@@ -361,30 +364,27 @@ VKX_EXPORT int vkx_mls_states_dev(vkx_ctx *ctx, const vkx_mls_config *configs, i
         s.height = c.height; s.width = c.width; s.grid_size = c.grid_size; s.pad = 0;
         s.sv = src_vertices[i]; s.dv = dst_vertices[i];
         s.hd.n = c.n_handles;
-        table_bytes += ((size_t)c.n_handles * 48 + 255) & ~(size_t)255;      // 2 x float32 [n, 2] + 2 x float64 [n, 2]
+        handles_off[i] = tab.add((size_t)c.n_handles * 48);      // 2 x float32 [n, 2] + 2 x float64 [n, 2]
         smooth_doubles += (size_t)s.rows * s.cols * 2;
         max_vertices = std::max(max_vertices, s.rows * s.cols);
         max_handles = std::max(max_handles, c.n_handles);
     }
-    const size_t desc_bytes = ((size_t)n * sizeof(MlsStateDev) + 255) & ~(size_t)255, out_bytes = ((size_t)n * sizeof(vkx_grid_state) + 255) & ~(size_t)255;
-    const size_t flag_bytes = ((size_t)n * 4 + 255) & ~(size_t)255;
-    const size_t upload = desc_bytes + table_bytes;
+    const size_t out_bytes = vkx_align256((size_t)n * sizeof(vkx_grid_state)), flag_bytes = vkx_align256((size_t)n * 4);
+    const size_t upload = vkx_align256(tab.bytes);
     if ((rc = vkx_scratch_reserve(ctx, &ctx->mls_work, upload + out_bytes + flag_bytes + smooth_doubles * sizeof(double)))) return rc;
     unsigned char *base = (unsigned char *)ctx->mls_work.ptr;
-    void *ring = nullptr;
-    if ((rc = vkx_desc_ring_take(ctx, upload, &ring))) return rc;
-    unsigned char *r = (unsigned char *)ring;
-    size_t off = desc_bytes, soff = 0;
+    if ((rc = tab.take())) return rc;
+    unsigned char *r = tab.host;
+    size_t soff = 0;
     double *smooth_base = (double *)(base + upload + out_bytes + flag_bytes);
     for (int i = 0; i < n; i++) {
         const vkx_mls_config &c = configs[i];
         MlsStateDev &s = host[i];
-        const size_t nf = (size_t)c.n_handles * 2;
+        const size_t nf = (size_t)c.n_handles * 2, off = handles_off[i];
         memcpy(r + off, c.src_handles, nf * 4);               s.hd.p = (const float *)(base + off);
         memcpy(r + off + nf * 4, c.dst_handles, nf * 4);      s.hd.q = (const float *)(base + off + nf * 4);
         memcpy(r + off + nf * 8, c.src_handles_smooth, nf * 8);   s.hd.ps = (const double *)(base + off + nf * 8);
         memcpy(r + off + nf * 16, c.dst_handles_smooth, nf * 8);  s.hd.qs = (const double *)(base + off + nf * 16);
-        off += ((size_t)c.n_handles * 48 + 255) & ~(size_t)255;
         s.smooth = smooth_base + soff;
         soff += (size_t)s.rows * s.cols * 2;
     }
@@ -394,8 +394,8 @@ VKX_EXPORT int vkx_mls_states_dev(vkx_ctx *ctx, const vkx_mls_config *configs, i
     unsigned *flags = (unsigned *)(base + upload + out_bytes);
     vkx_grid_state *out = (vkx_grid_state *)(base + upload);
     ctx->stream = st;
-    hipError_t e = hipMemcpyAsync(base, ring, upload, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, flag_bytes, st);
+    rc = tab.copy_to(base);                // on `st`
+    hipError_t e = rc ? hipErrorUnknown : hipMemsetAsync(flags, 0, flag_bytes, st);
     if (e == hipSuccess) {
         VKX_TIMED(ctx, "k_mls_states_project");
         const size_t lds = max_handles <= kLdsHandles ? sizeof(float) * 4 * (size_t)max_handles : 0;
@@ -407,8 +407,7 @@ VKX_EXPORT int vkx_mls_states_dev(vkx_ctx *ctx, const vkx_mls_config *configs, i
         k_mls_states_tail<<<n, 256, 0, st>>>((const MlsStateDev *)base, flags, out);
         e = hipGetLastError();
     }
-    rc = VKX_OK;
-    if (e != hipSuccess) { vkx_set_error("%s: %s", __func__, hipGetErrorString(e)); rc = VKX_ERR_HIP; }
+    if (!rc && e != hipSuccess) { vkx_set_error("%s: %s", __func__, hipGetErrorString(e)); rc = VKX_ERR_HIP; }
     if (!rc) rc = vkx_small_to_host(ctx, states_host, out, (size_t)n * sizeof(vkx_grid_state));
     ctx->stream = main_stream;
     if (rc) return rc;

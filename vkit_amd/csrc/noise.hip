@@ -153,16 +153,14 @@ VKX_EXPORT int vkx_noise_normal_i16_batch_dev(vkx_ctx *ctx, const vkx_noise_plan
     constexpr size_t kT16 = 65536 * sizeof(int16_t), kT8 = 65536;
     int rc;
     if (!ctx->noise_table.ptr || ctx->noise_table_std != std) {
-        if ((rc = vkx_scratch_reserve(ctx, &ctx->noise_table, kT16 + kT8))) return rc;
-        void *ring = nullptr;
-        if ((rc = vkx_desc_ring_take(ctx, kT16 + kT8, &ring))) return rc;
-        int16_t *t16 = (int16_t *)ring;
-        int8_t *t8 = (int8_t *)ring + kT16;
+        vkx_tables tab(ctx);
+        if ((rc = tab.take(kT16 + kT8))) return rc;
+        int16_t *t16 = tab.at<int16_t>(0);
+        int8_t *t8 = tab.at<int8_t>(kT16);
         build_normal_table(std, t16);
         ctx->noise_table_fits8 = t16[0] >= -127 && t16[65535] <= 127;
         for (int u = 0; u < 65536; u++) t8[u] = (int8_t)(ctx->noise_table_fits8 ? t16[u] : 0);
-        vkx_device_guard guard(ctx);
-        VKX_HIP(hipMemcpyAsync(ctx->noise_table.ptr, ring, kT16 + kT8, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = tab.copy_to(&ctx->noise_table))) return rc;
         ctx->noise_table_std = std;
     }
     const int16_t *t16 = (const int16_t *)ctx->noise_table.ptr;
@@ -181,14 +179,12 @@ VKX_EXPORT int vkx_noise_normal_i16_batch_dev(vkx_ctx *ctx, const vkx_noise_plan
             if (planes[i].h && planes[i].w) one = device_form(planes[i]);
         n_dev = 1;
     } else {
-        if ((rc = vkx_scratch_reserve(ctx, &ctx->misc, sizeof(NoisePlane) * (size_t)live))) return rc;
-        void *ring = nullptr;
-        if ((rc = vkx_desc_ring_take(ctx, sizeof(NoisePlane) * (size_t)live, &ring))) return rc;
-        NoisePlane *h = (NoisePlane *)ring;
+        vkx_tables tab(ctx);
+        if ((rc = tab.take(sizeof(NoisePlane) * (size_t)live)) || (rc = vkx_scratch_reserve(ctx, &ctx->misc, tab.bytes))) return rc;
+        NoisePlane *h = tab.at<NoisePlane>(0);
         for (int i = 0; i < n_planes; i++)
             if (planes[i].h && planes[i].w) h[n_dev++] = device_form(planes[i]);
-        vkx_device_guard guard(ctx);
-        if ((rc = vkx_small_to_device(ctx, ctx->misc.ptr, ring, sizeof(NoisePlane) * (size_t)live))) return rc;
+        if ((rc = tab.small_to(ctx->misc.ptr))) return rc;
         d_planes = (const NoisePlane *)ctx->misc.ptr;
     }
     vkx_device_guard guard(ctx);

@@ -1386,17 +1386,15 @@ static int np_tables(vkx_ctx *ctx, const NpTabs **out)
 {
     if (!ctx->np_tabs.ptr) {
         build_jump_tabs();
-        int rc = vkx_scratch_reserve(ctx, &ctx->np_tabs, sizeof(NpTabs));
+        vkx_tables tab(ctx);
+        int rc = tab.take(sizeof(NpTabs));
         if (rc) return rc;
-        void *ring = nullptr;
-        if ((rc = vkx_desc_ring_take(ctx, sizeof(NpTabs), &ring))) return rc;
-        NpTabs *t = (NpTabs *)ring;
+        NpTabs *t = tab.at<NpTabs>(0);
         t->jump = g_jump_host;
         memcpy(t->ki, kNpZigK, 2048);
         memcpy(t->wi, kNpZigW, 2048);
         memcpy(t->fi, kNpZigF, 2048);
-        vkx_device_guard guard(ctx);
-        VKX_HIP(hipMemcpyAsync(ctx->np_tabs.ptr, t, sizeof(NpTabs), hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = tab.copy_to(&ctx->np_tabs))) return rc;
     }
     *out = (const NpTabs *)ctx->np_tabs.ptr;
     return VKX_OK;
@@ -1420,7 +1418,7 @@ vkx_np_tiles_shape vkx_np_tiles_shape_of(long long n)
     s.n_tiles = np_tiles_for_n(n, false);
     s.slot_elems = kSlot;
     s.table_offset = 16;
-    s.slots_offset = (16 + 8 * ((size_t)s.n_tiles + 1) + 255) & ~(size_t)255;
+    s.slots_offset = vkx_align256(16 + 8 * ((size_t)s.n_tiles + 1));
     s.bytes = s.slots_offset + (size_t)s.n_tiles * kSlot * 2;
     s.samples_per_tile = (double)kTile * 0.97850;      // E[samples per raw draw] of numpy's ziggurat: 0.97850 (measured over 3e6 samples)
     return s;
@@ -1470,7 +1468,7 @@ static int np_chunk_prepare(vkx_ctx *ctx, NpChunk &c)
         c.total_tiles += tiles;
     }
     size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    auto take = [&off](size_t bytes) { const size_t o = off; off += vkx_align256(bytes); return o; };
     c.o_states = take((size_t)c.total_tiles * 16);
     c.o_info = take(uniform ? 0 : (size_t)c.total_tiles * sizeof(TileInfo));
     c.o_plan = take(uniform ? 0 : (size_t)c.total_tiles * sizeof(TilePlan));
@@ -1487,10 +1485,10 @@ static int np_chunk_prepare(vkx_ctx *ctx, NpChunk &c)
     // the device forms of the jobs: in the kernel arguments of the first kernel (small calls) or through the ctx ring
     c.inline_jobs = c.n_jobs <= kInlineJobs;
     NpJob *hj = c.pack.jobs;
+    vkx_tables tab(ctx);
     if (!c.inline_jobs) {
-        void *ring = nullptr;
-        if ((rc = vkx_desc_ring_take(ctx, (size_t)c.n_jobs * sizeof(NpJob), &ring))) return rc;
-        hj = (NpJob *)ring;
+        if ((rc = tab.take((size_t)c.n_jobs * sizeof(NpJob)))) return rc;
+        hj = tab.at<NpJob>(0);
     }
     const u128 g64 = ((u128)g_jump_host.g64[1] << 64) | g_jump_host.g64[0];
     const u128 g128 = ((u128)g_jump_host.g128[1] << 64) | g_jump_host.g128[0];
@@ -1524,7 +1522,7 @@ static int np_chunk_prepare(vkx_ctx *ctx, NpChunk &c)
             d.rec = (int16_t *)(c.base + c.o_rval) + d.tile_base * kSlot;
         }
     }
-    if (!c.inline_jobs && (rc = vkx_small_to_device(ctx, c.base + c.o_jobs, hj, (size_t)c.n_jobs * sizeof(NpJob)))) return rc;
+    if (!c.inline_jobs && (rc = tab.small_to(c.base + c.o_jobs))) return rc;
     // page-locked results: the chunk's last kernel writes them through the mapping
     c.res_mapped = nullptr;
     if (hipHostGetDevicePointer((void **)&c.res_mapped, c.results_host, 0) != hipSuccess) {

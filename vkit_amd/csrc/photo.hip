@@ -1404,16 +1404,13 @@ VKX_EXPORT int vkx_apply_lut_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int
     // the table is the caller's memory: it travels through the page-locked descriptor ring, no stream synchronisation.  The dense
     // kernel stages it to LDS once per workgroup straight from the (mapped) ring: no copy, one dispatch per call instead of two
     // (PageResizingStep binarises seven planes per page through this entry)
-    void *staged = nullptr;
-    rc = vkx_desc_ring_take(ctx, (size_t)256 * cn, &staged);
-    if (rc) return rc;
-    memcpy(staged, lut_host, (size_t)256 * cn);
-    const uint8_t *table = (const uint8_t *)vkx_ring_device_ptr(staged);
+    vkx_tables tab(ctx);
+    if ((rc = tab.take((size_t)256 * cn))) return rc;
+    memcpy(tab.host, lut_host, tab.bytes);
     const bool dense = dense16(src, src_stride, dst, dst_stride, (size_t)w * cn, h);
-    if (!table || !dense) {          // the strided kernel reads the table per pixel: from device memory
-        rc = vkx_scratch_reserve(ctx, &ctx->misc, 1024);
-        if (rc) return rc;
-        VKX_HIP(hipMemcpyAsync(ctx->misc.ptr, staged, (size_t)256 * cn, hipMemcpyHostToDevice, ctx->stream));
+    const uint8_t *table = dense ? tab.mapped() : nullptr;
+    if (!table) {                    // the strided kernel reads the table per pixel: from device memory
+        if ((rc = tab.copy_to(&ctx->misc, 1024))) return rc;
         table = (const uint8_t *)ctx->misc.ptr;
     }
     if (dense) {
@@ -1435,8 +1432,8 @@ VKX_EXPORT int vkx_apply_lut_u8_planes_dev(vkx_ctx *ctx, const vkx_lut_plane *pl
     LutPlanes P;
     memset(&P, 0, sizeof(P));
     size_t n_max = 0;
-    void *staged = nullptr;
-    int rc = vkx_desc_ring_take(ctx, (size_t)256 * n_planes, &staged);
+    vkx_tables tab(ctx);
+    int rc = tab.take((size_t)256 * n_planes);
     if (rc) return rc;
     for (int i = 0; i < n_planes; i++) {
         const vkx_lut_plane &pl = planes[i];
@@ -1444,13 +1441,12 @@ VKX_EXPORT int vkx_apply_lut_u8_planes_dev(vkx_ctx *ctx, const vkx_lut_plane *pl
         VKX_REQUIRE((((uintptr_t)pl.src | (uintptr_t)pl.dst) & 15) == 0, "planes are 16-byte aligned, dense");
         P.src[i] = pl.src; P.dst[i] = pl.dst; P.n[i] = pl.n_bytes;
         n_max = std::max(n_max, pl.n_bytes);
-        memcpy((uint8_t *)staged + 256 * i, pl.lut_host, 256);
+        memcpy(tab.host + 256 * i, pl.lut_host, 256);
     }
     if (n_max == 0) return VKX_OK;
-    const uint8_t *tables = (const uint8_t *)vkx_ring_device_ptr(staged);
+    const uint8_t *tables = tab.mapped();
     if (!tables) {
-        if ((rc = vkx_scratch_reserve(ctx, &ctx->misc, 2048))) return rc;
-        VKX_HIP(hipMemcpyAsync(ctx->misc.ptr, staged, (size_t)256 * n_planes, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = tab.copy_to(&ctx->misc, 2048))) return rc;
         tables = (const uint8_t *)ctx->misc.ptr;
     }
     vkx_device_guard guard(ctx);

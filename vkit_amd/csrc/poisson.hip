@@ -821,13 +821,12 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
         ctx->pz_tabs_ready = true;
     }
     const PzTabs *tabs = (const PzTabs *)ctx->pz_tabs.ptr;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_mean = 0, o_var = o_mean + up(sizeof(float) * n_blk), o_rows = o_var + up(sizeof(float) * n_blk), o_order = o_rows + up(sizeof(float) * n_blk),
-                 o_plan = o_order + up(sizeof(int) * n_blk),
-                 o_bpos = o_plan + up(sizeof(PzBlock) * n_blk), o_pos = o_bpos + up(sizeof(long long) * (n_blk + 1));
+    const size_t o_mean = 0, o_var = o_mean + vkx_align256(sizeof(float) * n_blk), o_rows = o_var + vkx_align256(sizeof(float) * n_blk), o_order = o_rows + vkx_align256(sizeof(float) * n_blk),
+                 o_plan = o_order + vkx_align256(sizeof(int) * n_blk),
+                 o_bpos = o_plan + vkx_align256(sizeof(PzBlock) * n_blk), o_pos = o_bpos + vkx_align256(sizeof(long long) * (n_blk + 1));
     // superblocks hold at least one block each: n_blk + 2 positions always suffice
     // counters: the ticket | per superblock: groups done, `done` flag | per group: blocks done
-    const size_t o_counter = o_pos + up(sizeof(long long) * (n_blk + 2)), o_reply = o_counter + up(sizeof(unsigned) * (3 * (size_t)n_blk + 8)), work_bytes = o_reply + 256;
+    const size_t o_counter = o_pos + vkx_align256(sizeof(long long) * (n_blk + 2)), o_reply = o_counter + vkx_align256(sizeof(unsigned) * (3 * (size_t)n_blk + 8)), work_bytes = o_reply + 256;
     if ((rc = vkx_scratch_reserve(ctx, &ctx->pz_work, work_bytes))) return rc;
     unsigned char *work = (unsigned char *)ctx->pz_work.ptr;
     float *d_mean = (float *)(work + o_mean), *d_var = (float *)(work + o_var), *d_rows = (float *)(work + o_rows);
@@ -961,8 +960,8 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
         return VKX_OK;
     }
     us_plan = since(t_begin) - us_stats;
-    const size_t e_slot_bytes = up(sizeof(uint16_t) * (size_t)e_max + 16), e_stride = e_slot_bytes / sizeof(uint16_t);
-    const size_t draws_bytes = up(sizeof(double) * (size_t)(M + 2)), sup_bytes = up(sizeof(PzSuper) * supers.size());
+    const size_t e_slot_bytes = vkx_align256(sizeof(uint16_t) * (size_t)e_max + 16), e_stride = e_slot_bytes / sizeof(uint16_t);
+    const size_t draws_bytes = vkx_align256(sizeof(double) * (size_t)(M + 2)), sup_bytes = vkx_align256(sizeof(PzSuper) * supers.size());
     if ((rc = vkx_scratch_reserve(ctx, &ctx->pz_draws, draws_bytes + 3 * kSlots * e_slot_bytes + sup_bytes))) return rc;
     double *d_draws = (double *)ctx->pz_draws.ptr;
     uint16_t *d_E = (uint16_t *)((unsigned char *)ctx->pz_draws.ptr + draws_bytes);

@@ -296,10 +296,10 @@ static int paint_sets_dev(vkx_ctx *ctx, const vkx_paint_set *sets, int n_sets, i
         e_base += (size_t)set_pts;
         v_base += (size_t)S.n_polys;
     }
-    const size_t ebytes = (sizeof(PolyEdge) * edges.size() + 255) & ~(size_t)255;
-    const size_t ibytes = (sizeof(PaintItem) * items.size() + 255) & ~(size_t)255;
-    const size_t vbytes = (sizeof(float) * values.size() + 255) & ~(size_t)255;
-    int rc = vkx_scratch_reserve(ctx, &ctx->misc, 256 + ebytes + ibytes + vbytes);
+    vkx_tables tab(ctx);         // behind the overflow flag's 256 bytes of ctx->misc
+    const size_t e_off = tab.add(sizeof(PolyEdge) * edges.size()), i_off = tab.add(sizeof(PaintItem) * items.size());
+    const size_t v_off = tab.add(sizeof(float) * values.size());
+    int rc = vkx_scratch_reserve(ctx, &ctx->misc, 256 + vkx_align256(tab.bytes));
     if (rc) return rc;
     // the ownership raster is the paint's own block: zero at rest (k_paint_resolve clears what it reads), memset only when it grows
     const size_t owner_bytes = (size_t)h * w * 4 * (size_t)n_sets;
@@ -308,23 +308,21 @@ static int paint_sets_dev(vkx_ctx *ctx, const vkx_paint_set *sets, int n_sets, i
     if (rc) return rc;
     unsigned char *misc = (unsigned char *)ctx->misc.ptr;
     int *overflow = (int *)misc;
-    PolyEdge *d_edges = (PolyEdge *)(misc + 256);
-    PaintItem *d_items = (PaintItem *)(misc + 256 + ebytes);
-    float *d_values = (float *)(misc + 256 + ebytes + ibytes);
+    PolyEdge *d_edges = (PolyEdge *)(misc + 256 + e_off);
+    PaintItem *d_items = (PaintItem *)(misc + 256 + i_off);
+    float *d_values = (float *)(misc + 256 + v_off);
     int *owner = (int *)ctx->paint_owner.ptr;
     // The edge / item / value tables travel through the context's page-locked ring as ONE asynchronous copy: the call returns
     // with its kernels queued (a page paints four label planes: two stream synchronisations and a flag read-back per call were
     // 0.45 ms of a 2.2 ms page).  A polygon of at most kPaintCross vertices cannot cross a scanline more often than the span
     // kernel holds, so only calls with larger polygons read the overflow flag back (and synchronise for it).
-    const size_t table_bytes = ebytes + ibytes + vbytes;
     vkx_device_guard guard(ctx);
-    if (table_bytes) {
-        void *ring = nullptr;
-        if ((rc = vkx_desc_ring_take(ctx, table_bytes, &ring))) return rc;
-        if (!edges.empty()) memcpy(ring, edges.data(), sizeof(PolyEdge) * edges.size());
-        if (!items.empty()) memcpy((unsigned char *)ring + ebytes, items.data(), sizeof(PaintItem) * items.size());
-        if (!values.empty()) memcpy((unsigned char *)ring + ebytes + ibytes, values.data(), sizeof(float) * values.size());
-        VKX_HIP(hipMemcpyAsync(d_edges, ring, table_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (tab.bytes) {
+        if ((rc = tab.take())) return rc;
+        if (!edges.empty()) memcpy(tab.at<PolyEdge>(e_off), edges.data(), sizeof(PolyEdge) * edges.size());
+        if (!items.empty()) memcpy(tab.at<PaintItem>(i_off), items.data(), sizeof(PaintItem) * items.size());
+        if (!values.empty()) memcpy(tab.at<float>(v_off), values.data(), sizeof(float) * values.size());
+        if ((rc = tab.copy_to(misc + 256))) return rc;
     }
     if (may_overflow) VKX_HIP(hipMemsetAsync(overflow, 0, sizeof(int), ctx->stream));      // (only such calls can set it, and only they read it)
     if (ctx->paint_owner_zeroed < owner_bytes) VKX_HIP(hipMemsetAsync(owner, 0, ctx->paint_owner.cap, ctx->stream));
@@ -396,7 +394,7 @@ VKX_EXPORT int vkx_paint_polys(vkx_ctx *ctx, const int32_t *pts_host, const int3
     VKX_REQUIRE(h > 0 && w > 0, "bad shape");
     VKX_REQUIRE_PITCH(mask_stride, w, mask ? h : 1);
     VKX_REQUIRE_PITCH(score_stride_el, w, score ? h : 1);
-    const size_t mbytes = mask ? (((size_t)h * w + 255) & ~(size_t)255) : 0;
+    const size_t mbytes = mask ? vkx_align256((size_t)h * w) : 0;
     const size_t sbytes = score ? (size_t)h * w * 4 : 0;
     int rc = vkx_scratch_reserve(ctx, &ctx->stage[1], mbytes + sbytes);
     if (rc) return rc;

@@ -169,20 +169,6 @@ __global__ void __launch_bounds__(256) k_region_label_planes(const int4 *__restr
     }
 }
 
-int stage(vkx_ctx *ctx, vkx_scratch *s, const void *host, size_t bytes)
-{
-    void *staged = nullptr;
-    int rc = vkx_desc_ring_take(ctx, bytes, &staged);
-    if (rc) return rc;
-    memcpy(staged, host, bytes);
-    if ((rc = vkx_scratch_reserve(ctx, s, std::max(bytes, (size_t)64 << 10)))) return rc;
-    vkx_device_guard guard(ctx);
-    VKX_HIP(hipMemcpyAsync(s->ptr, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return VKX_OK;
-}
-
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 
 VKX_EXPORT int vkx_region_label_deviate_dev(vkx_ctx *ctx, const double *quads_host, const int32_t *centres_host, int n_centres,
@@ -219,22 +205,23 @@ VKX_EXPORT int vkx_region_label_deviate_dev(vkx_ctx *ctx, const double *quads_ho
             VKX_REQUIRE(d[0] >= 1 && d[0] <= b[3] - 2 && d[1] >= 1 && d[1] <= b[2] - 2, "a draw outside [1, box - 2]");
         }
     }
-    const size_t quad_bytes = align256((size_t)n_chars * 64), box_bytes = align256((size_t)n_chars * 16);
-    const size_t centre_bytes = align256((size_t)n_centres * 8), draw_bytes = (size_t)n_chars * m * 8;
-    std::vector<char> block(quad_bytes + box_bytes + centre_bytes + draw_bytes);
-    memcpy(block.data(), quads_host, (size_t)n_chars * 64);
-    memcpy(block.data() + quad_bytes, boxes.data(), (size_t)n_chars * 16);
-    memcpy(block.data() + quad_bytes + box_bytes, centres_host, (size_t)n_centres * 8);
-    memcpy(block.data() + quad_bytes + box_bytes + centre_bytes, draws_host, draw_bytes);
-    int rc = stage(ctx, &ctx->rl_deviate, block.data(), block.size());
+    vkx_tables tab(ctx);
+    const size_t quad_off = tab.add((size_t)n_chars * 64), box_off = tab.add((size_t)n_chars * 16);
+    const size_t centre_off = tab.add((size_t)n_centres * 8), draw_off = tab.add((size_t)n_chars * m * 8);
+    int rc = tab.take();
     if (rc) return rc;
+    memcpy(tab.at<double>(quad_off), quads_host, (size_t)n_chars * 64);
+    memcpy(tab.at<int>(box_off), boxes.data(), (size_t)n_chars * 16);
+    memcpy(tab.at<int32_t>(centre_off), centres_host, (size_t)n_centres * 8);
+    memcpy(tab.at<int32_t>(draw_off), draws_host, (size_t)n_chars * m * 8);
+    if ((rc = tab.copy_to(&ctx->rl_deviate, (size_t)64 << 10))) return rc;
     char *base = (char *)ctx->rl_deviate.ptr;
     const int chars_per_block = std::max(1, kDevBlock / m);
     {
         VKX_TIMED(ctx, "k_region_label_deviate");
         k_region_label_deviate<<<vkx_blocks(n_chars, chars_per_block), kDevBlock, 0, ctx->stream>>>(
-            (const double *)base, (const int *)(base + quad_bytes), (const int2 *)(base + quad_bytes + box_bytes), n_centres,
-            n_chars, (const int2 *)(base + quad_bytes + box_bytes + centre_bytes), m, chars_per_block, h, w, out);
+            (const double *)(base + quad_off), (const int *)(base + box_off), (const int2 *)(base + centre_off), n_centres,
+            n_chars, (const int2 *)(base + draw_off), m, chars_per_block, h, w, out);
     }
     VKX_LAUNCH_CHECK();
     return VKX_OK;
@@ -281,22 +268,22 @@ VKX_EXPORT int vkx_region_label_planes_dev(vkx_ctx *ctx, const int32_t *boxes_ho
     std::vector<int> entries((size_t)std::max(tile_start[tiles], 1)), fill(tile_start.begin(), tile_start.end() - 1);
     visit([&](int t, int k, bool) { entries[fill[t]++] = k; });
 
-    const size_t box_bytes = align256((size_t)n_boxes * 16), start_bytes = align256(((size_t)tiles + 1) * 4);
-    const size_t entry_bytes = align256(entries.size() * 4);
-    std::vector<char> block(box_bytes + start_bytes + entry_bytes + (size_t)tiles);
-    if (n_boxes) memcpy(block.data(), boxes_host, (size_t)n_boxes * 16);
-    memcpy(block.data() + box_bytes, tile_start.data(), ((size_t)tiles + 1) * 4);
-    memcpy(block.data() + box_bytes + start_bytes, entries.data(), entries.size() * 4);
-    memcpy(block.data() + box_bytes + start_bytes + entry_bytes, full.data(), (size_t)tiles);
-    int rc = stage(ctx, &ctx->rl_planes, block.data(), block.size());
+    vkx_tables tab(ctx);
+    const size_t box_off = tab.add((size_t)n_boxes * 16), start_off = tab.add(((size_t)tiles + 1) * 4);
+    const size_t entry_off = tab.add(entries.size() * 4), full_off = tab.add((size_t)tiles);
+    int rc = tab.take();
     if (rc) return rc;
+    if (n_boxes) memcpy(tab.at<int32_t>(box_off), boxes_host, (size_t)n_boxes * 16);
+    memcpy(tab.at<int>(start_off), tile_start.data(), ((size_t)tiles + 1) * 4);
+    memcpy(tab.at<int>(entry_off), entries.data(), entries.size() * 4);
+    memcpy(tab.at<uint8_t>(full_off), full.data(), (size_t)tiles);
+    if ((rc = tab.copy_to(&ctx->rl_planes, (size_t)64 << 10))) return rc;
     char *base = (char *)ctx->rl_planes.ptr;
     {
         VKX_TIMED(ctx, "k_region_label_planes");
         k_region_label_planes<<<(unsigned)tiles, 256, 0, ctx->stream>>>(
-            (const int4 *)base, (const int *)(base + box_bytes), (const int *)(base + box_bytes + start_bytes),
-            (const uint8_t *)(base + box_bytes + start_bytes + entry_bytes), tiles_x, h, w, active_mask, char_mask, char_height,
-            box_mask);
+            (const int4 *)(base + box_off), (const int *)(base + start_off), (const int *)(base + entry_off),
+            (const uint8_t *)(base + full_off), tiles_x, h, w, active_mask, char_mask, char_height, box_mask);
     }
     VKX_LAUNCH_CHECK();
     return VKX_OK;

@@ -543,21 +543,17 @@ int cached_tables(vkx_ctx *ctx, const int key[6], Build build, std::vector<const
         std::vector<int> m;
         build(&arrays, &m);
         if (arrays.size() > 7) return VKX_ERR_INVALID;
-        size_t total = 0;
-        for (size_t i = 0; i < arrays.size(); i++) { slot->off[i] = total; total += (arrays[i].second + 255) & ~(size_t)255; }
+        vkx_tables tab(ctx);
+        for (size_t i = 0; i < arrays.size(); i++) slot->off[i] = tab.add(arrays[i].second);
         slot->off[7] = arrays.size();
         slot->key[0] = -1;
-        int rc = vkx_scratch_reserve(ctx, &slot->buf, total ? total : 256);
-        if (rc) return rc;
         // the tables travel as ONE copy out of the page-locked ring (which keeps them alive): no copy per table, no stream
         // synchronisation per cache miss -- every page resizes to a geometry of its own
-        if (total) {
-            void *ring = nullptr;
-            if ((rc = vkx_desc_ring_take(ctx, total, &ring))) return rc;
-            for (size_t i = 0; i < arrays.size(); i++)
-                if (arrays[i].second) memcpy((unsigned char *)ring + slot->off[i], arrays[i].first, arrays[i].second);
-            VKX_HIP(hipMemcpyAsync(slot->buf.ptr, ring, total, hipMemcpyHostToDevice, ctx->stream));
-        }
+        int rc = tab.bytes ? tab.take() : vkx_scratch_reserve(ctx, &slot->buf, 256);
+        if (rc) return rc;
+        for (size_t i = 0; i < arrays.size(); i++)
+            if (arrays[i].second) memcpy(tab.at<char>(slot->off[i]), arrays[i].first, arrays[i].second);
+        if (tab.bytes && (rc = tab.copy_to(&slot->buf, 256))) return rc;
         slot->yofs.swap(m);
         std::copy(key, key + 6, slot->key);
     }
@@ -884,26 +880,22 @@ int resize_tables(vkx_ctx *ctx, int taps, bool fixed, int sh, int sw, int dh, in
             xo.swap(tx.ofs); yo.swap(ty.ofs); xc.swap(tx.coef); yc.swap(ty.coef); xi.swap(tx.icoef); yi.swap(ty.icoef);
         }
         const size_t csz = fixed ? sizeof(short) : sizeof(float);
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        slot->off[0] = 0;
-        slot->off[1] = slot->off[0] + up(sizeof(int) * dw);
-        slot->off[2] = slot->off[1] + up(csz * taps * dw);
-        slot->off[3] = slot->off[2] + up(sizeof(int) * dh);
+        vkx_tables tab(ctx);
+        slot->off[0] = tab.add(sizeof(int) * dw);
+        slot->off[1] = tab.add(csz * taps * dw);
+        slot->off[2] = tab.add(sizeof(int) * dh);
+        slot->off[3] = tab.add(csz * taps * dh);
         slot->key[0] = -1;                        // invalid until the upload below has succeeded
-        int rc = vkx_scratch_reserve(ctx, &slot->buf, slot->off[3] + up(csz * taps * dh));
-        if (rc) return rc;
         const void *xsrc = fixed ? (const void *)xi.data() : (const void *)xc.data();
         const void *ysrc = fixed ? (const void *)yi.data() : (const void *)yc.data();
         // one copy out of the page-locked ring for the four tables (the ring keeps them alive: no synchronisation)
-        const size_t total = slot->off[3] + up(csz * taps * dh);
-        void *ring = nullptr;
-        if ((rc = vkx_desc_ring_take(ctx, total, &ring))) return rc;
-        unsigned char *stage = (unsigned char *)ring;
-        memcpy(stage + slot->off[0], xo.data(), sizeof(int) * dw);
-        memcpy(stage + slot->off[2], yo.data(), sizeof(int) * dh);
-        memcpy(stage + slot->off[1], xsrc, csz * taps * dw);
-        memcpy(stage + slot->off[3], ysrc, csz * taps * dh);
-        VKX_HIP(hipMemcpyAsync(slot->buf.ptr, stage, total, hipMemcpyHostToDevice, ctx->stream));
+        int rc = tab.take();
+        if (rc) return rc;
+        memcpy(tab.at<char>(slot->off[0]), xo.data(), sizeof(int) * dw);
+        memcpy(tab.at<char>(slot->off[2]), yo.data(), sizeof(int) * dh);
+        memcpy(tab.at<char>(slot->off[1]), xsrc, csz * taps * dw);
+        memcpy(tab.at<char>(slot->off[3]), ysrc, csz * taps * dh);
+        if ((rc = tab.copy_to(&slot->buf))) return rc;
         slot->yofs.swap(yo);
         std::copy(key, key + 6, slot->key);
     }
@@ -1054,20 +1046,17 @@ VKX_EXPORT int vkx_resize_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int s
     std::vector<short> xa, yb;
     build_linear_axis(sw, dw, true, &xo, &xa);
     build_linear_axis(sh, dh, false, &yo, &yb);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o0 = 0, o1 = o0 + up(sizeof(int) * dw), o2 = o1 + up(sizeof(short) * 2 * dw), o3 = o2 + up(sizeof(int) * dh);
-    const size_t total = o3 + up(sizeof(short) * 2 * dh);
-    int rc = vkx_scratch_reserve(ctx, &ctx->misc, total);
+    vkx_tables tab(ctx);      // one copy for the four tables, no synchronisation
+    const size_t o0 = tab.add(sizeof(int) * dw), o1 = tab.add(sizeof(short) * 2 * dw), o2 = tab.add(sizeof(int) * dh);
+    const size_t o3 = tab.add(sizeof(short) * 2 * dh);
+    int rc = tab.take();
     if (rc) return rc;
+    memcpy(tab.at<int>(o0), xo.data(), sizeof(int) * dw);
+    memcpy(tab.at<short>(o1), xa.data(), sizeof(short) * 2 * dw);
+    memcpy(tab.at<int>(o2), yo.data(), sizeof(int) * dh);
+    memcpy(tab.at<short>(o3), yb.data(), sizeof(short) * 2 * dh);
+    if ((rc = tab.copy_to(&ctx->misc))) return rc;
     unsigned char *base = (unsigned char *)ctx->misc.ptr;
-    void *ring = nullptr;
-    if ((rc = vkx_desc_ring_take(ctx, total, &ring))) return rc;      // one copy for the four tables, no synchronisation
-    unsigned char *stage = (unsigned char *)ring;
-    memcpy(stage + o0, xo.data(), sizeof(int) * dw);
-    memcpy(stage + o1, xa.data(), sizeof(short) * 2 * dw);
-    memcpy(stage + o2, yo.data(), sizeof(int) * dh);
-    memcpy(stage + o3, yb.data(), sizeof(short) * 2 * dh);
-    VKX_HIP(hipMemcpyAsync(base, stage, total, hipMemcpyHostToDevice, ctx->stream));
     const int *dxo = (const int *)(base + o0), *dyo = (const int *)(base + o2);
     const short *dxa = (const short *)(base + o1), *dyb = (const short *)(base + o3);
     VKX_TIMED(ctx, "k_resize_linear");

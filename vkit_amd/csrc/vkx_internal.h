@@ -131,6 +131,10 @@ struct vkx_ctx {
     std::vector<hipEvent_t> order_events;              // reusable events of vkx_ctx_order / vkx_event_record
     unsigned char *desc_ring = nullptr;
     size_t desc_cap = 0, desc_off = 0;
+    // Call-scoped hold: a block was handed out for a kernel to read in place (vkx_tables::mapped, HostStage::commit_mapped) and
+    // that kernel is not queued yet, so no synchronisation protects the block.  While it is set a take that would wrap onto the
+    // block or regrow the ring under it fails (VKX_ERR_NOMEM) and sets desc_hold to 2; the caller falls back to its copy path.
+    int desc_hold = 0;
 
     // The tap tables of the last few CUBIC / LANCZOS4 resize geometries (PageResizingStep resizes seven elements with one
     // geometry: the tables are built and uploaded for the first one only).
@@ -191,6 +195,54 @@ int vkx_small_to_device(vkx_ctx *ctx, void *dev, const void *ring_host, size_t b
 int vkx_small_to_host(vkx_ctx *ctx, void *host, const void *dev, size_t bytes);
 hipStream_t vkx_stream_by_id(vkx_ctx *ctx, int id, int *rc);
 const void *vkx_ring_device_ptr(const void *ring_host);              // a ring block as kernels address it (mapped host memory), or nullptr
+
+static inline size_t vkx_align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The small tables a call builds on the host (edge lists, tile bins, descriptors, LUTs) on their way to the device: lay the
+// parts out with add() (each starts on a 256-byte boundary), take() ONE ring block for all of them, write each part where
+// at<T>(offset) points -- straight into the ring --, then deliver the block in the way the site has measured to be best:
+// copy_to() (one hipMemcpyAsync on ctx->stream), small_to() (vkx_small_to_device) or mapped() (read, or written, in place).
+struct vkx_tables {
+    vkx_ctx *ctx;
+    size_t bytes = 0;                  // the end of the last part: what take() asks for and the copies move
+    unsigned char *host = nullptr;     // the ring block, after take()
+    bool holds = false;                // mapped() set the ring's hold
+    explicit vkx_tables(vkx_ctx *c) : ctx(c) {}
+    ~vkx_tables() { release(); }
+    vkx_tables(const vkx_tables &) = delete;
+    vkx_tables &operator=(const vkx_tables &) = delete;
+
+    size_t add(size_t n) { const size_t off = vkx_align256(bytes); bytes = off + n; return off; }
+    int take(size_t n = 0) { if (n) add(n); return vkx_desc_ring_take(ctx, bytes, (void **)&host); }   // (n: a last, or the only, part)
+    template <class T> T *at(size_t off) const { return (T *)(host + off); }
+    int copy_to(void *dev) const           // ... to a base the caller reserved (at least `bytes`)
+    {
+        vkx_device_guard guard(ctx);
+        VKX_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return VKX_OK;
+    }
+    int copy_to(vkx_scratch *s, size_t min_cap = 0)   // ... to s->ptr, reserved here with the site's minimum capacity
+    {
+        const int rc = vkx_scratch_reserve(ctx, s, bytes > min_cap ? bytes : min_cap);
+        return rc ? rc : copy_to(s->ptr);
+    }
+    int small_to(void *dev) const { vkx_device_guard guard(ctx); return vkx_small_to_device(ctx, dev, host, bytes); }
+    // The block as kernels address it, or nullptr where the ring cannot be mapped (the site falls back to a copy, or fails).  The
+    // kernel that will read it is not queued yet, so the ring is held (vkx_ctx::desc_hold) until release() or the end of this object.
+    unsigned char *mapped()
+    {
+        unsigned char *dev = (unsigned char *)const_cast<void *>(vkx_ring_device_ptr(host));
+        if (dev && !ctx->desc_hold) { ctx->desc_hold = 1; holds = true; }
+        return dev;
+    }
+    bool release()                     // true: a take was refused during the hold
+    {
+        const bool refused = holds && ctx->desc_hold == 2;
+        if (holds) ctx->desc_hold = 0;
+        holds = false;
+        return refused;
+    }
+};
 int vkx_stream_order(vkx_ctx *ctx, hipStream_t later, hipStream_t earlier);
 void vkx_ctx_join_streams(vkx_ctx *ctx, hipStream_t main_stream);   // error exits of multi-stream calls: main after the side streams, ctx->stream = main
 int vkx_chain_consume_lattices_mark(vkx_ctx *ctx);                   // staged chain paths: the compute stream waits for a pending lattices-ready mark
