@@ -818,6 +818,34 @@ typedef struct vkx_crop_plane {
 int vkx_crop_planes_dev(vkx_ctx *ctx, int h, int w, int core_size, int pad_size, int factor, const vkx_crop_window *windows_host,
                         int n_windows, const vkx_crop_plane *planes_host, int n_planes);
 
+/* ---- the combiner image engine (engine/image/combiner.py:178-333, ImageCombinerEngine.synthesize_image) -----------------
+ * Writes the whole page dst = uint8 [h, w, 3] (device, dense) in one launch from texture tiles:
+ *   mosaic = zeros, then every tile in table order: mosaic[up : down + 1, left : right + 1] = the upper left
+ *            (down + 1 - up) x (right + 1 - left) corner of its source image (combiner.py:286-291); a pixel no tile covers
+ *            is 0, a pixel two tiles cover takes the later one;
+ *   edge   = union over the tiles of the four bands of fill_np_edge_mask (combiner.py:146-176): rows [up - half, up + half]
+ *            and [down - half, down + half] over columns left .. right, columns [left - half, left + half] and
+ *            [right - half, right + half] over rows up .. down, clipped to the page;
+ *   dst    = edge ? cv.GaussianBlur(mosaic, (ksize, ksize), sigma) : mosaic (combiner.py:326-331), the blur with the
+ *            arithmetic of vkx_gaussian_blur_u8_dev (8.8 fixed point, BORDER_REFLECT_101) on the UNBLURRED mosaic.
+ * The reference passes half = gaussian_blur_kernel_size / 2 + 1 and sigma = half / 3.  `tiles_host` and `sources_host` are
+ * HOST tables; a source's image is a DEVICE pointer.  Asynchronous on the context's stream.  Refused (VKX_ERR_INVALID,
+ * nothing written) for a NULL pointer, h or w outside 0 .. 2^19 or h * w >= 2^29 (an empty page writes nothing), ksize even,
+ * below 1 or above 15 (the LDS window of a 64 x 16 block holds a halo of 7), half outside 0 .. 64, sigma not finite or
+ * <= 0, a tile outside the page or larger than its source, a source index out of range, a source without pixels, a
+ * destination overlapping a source, and a table whose tiles meet more than 2^26 (64 x 16 block, tile) pairs in all. */
+typedef struct vkx_combine_tile {
+    int32_t up, down, left, right;     /* inclusive, inside the page */
+    int32_t source;                    /* index into the source table */
+} vkx_combine_tile;
+typedef struct vkx_combine_source {
+    const uint8_t *image;              /* device, uint8 [height, width, 3], dense */
+    int32_t height, width;
+} vkx_combine_source;
+int vkx_image_combine_u8c3_dev(vkx_ctx *ctx, const vkx_combine_tile *tiles_host, int n_tiles,
+                               const vkx_combine_source *sources_host, int n_sources, int ksize, int half, double sigma,
+                               uint8_t *dst, int h, int w);
+
 /* ---- the external_ellipse char-mask engine (engine/char_mask/external_ellipse.py:104-220) ------------------------------
  * Per char (4 points, smooth float64 (x, y)) and internal side length L (1 .. 2048): R = ceil(L / sqrt 2), E = 2 R + 1, the
  * template build_np_distance(R) <= R (engine/char_heatmap/default.py:30-40); H1 = getPerspectiveTransform(char square

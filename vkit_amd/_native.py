@@ -249,6 +249,14 @@ class VkxCropPlane(ctypes.Structure):
         (name, ctypes.c_int32) for name in ('cn', 'is_f32', 'core_only', 'is_mask', 'clip', 'fill', 'window')]
 
 
+class VkxCombineTile(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in ('up', 'down', 'left', 'right', 'source')]
+
+
+class VkxCombineSource(ctypes.Structure):
+    _fields_ = [('image', c_void_p), ('height', ctypes.c_int32), ('width', ctypes.c_int32)]
+
+
 NP_NORMAL_I16, NP_NORMAL_ADD_U8, NP_SPECKLE_U8, NP_CHOICE3_U8, NP_IMPULSE_U8, NP_NORMAL_TILES = 0, 1, 2, 3, 4, 5
 NP_AMBIGUOUS, NP_SHORT = 1, 2
 
@@ -369,6 +377,8 @@ _SIGNATURES['vkx_crop_count_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_
                                      ctypes.POINTER(VkxCropWindow), c_int, c_int, c_void_p]
 _SIGNATURES['vkx_crop_planes_dev'] = [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(VkxCropWindow), c_int,
                                       ctypes.POINTER(VkxCropPlane), c_int]
+_SIGNATURES['vkx_image_combine_u8c3_dev'] = [c_void_p, ctypes.POINTER(VkxCombineTile), c_int, ctypes.POINTER(VkxCombineSource), c_int,
+                                             c_int, c_int, c_double, c_void_p, c_int, c_int]
 _SIGNATURES['vkx_char_mask_ellipse_sets_fresh_dev'] = [c_void_p, c_int, ctypes.POINTER(VkxCharSet), c_int, c_int, c_int]
 _SIGNATURES['vkx_char_mask_ellipse_sets_fresh'] = [c_void_p, c_int, ctypes.POINTER(VkxCharSet), c_int, c_int, c_int]
 _SIGNATURES['vkx_char_heatmap_fresh_dev'] = [c_void_p, ctypes.POINTER(VkxCharHeatmapConfig), c_void_p, c_int, c_int, c_int,
@@ -2219,6 +2229,51 @@ def crop_planes(jobs, windows, page_shape, core_size, pad_size, factor=0):
     check(lib().vkx_crop_planes_dev(ctx.handle, h, w, int(core_size), int(pad_size), int(factor), _crop_window_table(windows),
                                     len(windows), table, n))
     return outs
+
+
+def image_combine(tiles, sources, shape, ksize, sigma, ctx=None, half=None):
+    """The combiner image engine's page in ONE launch (vkx_image_combine_u8c3_dev): ``tiles`` int (n, 5) rows (up, down, left,
+    right, source index), inclusive and in paint order; ``sources`` the textures, uint8 (H, W, 3) DevArrays of one context (a
+    numpy texture is uploaded for the call); ``shape`` (h, w) of the page; the seam's Gaussian ``ksize`` / ``sigma`` and the band
+    half width ``half`` (default: the reference's ksize // 2 + 1).  -> the page, uint8 (h, w, 3): a DevArray inside
+    ``resident(True)`` (asynchronous on the context's stream), a host array otherwise."""
+    h, w = (int(v) for v in shape)
+    owners = [s.ctx for s in sources if isinstance(s, DevArray)]
+    ctx = ctx or (owners[0] if owners else default_ctx())
+    if any(o is not ctx for o in owners):
+        raise ValueError('the textures of one call live on one context')
+    table = np.ascontiguousarray(np.asarray(tiles, dtype=np.int64).reshape(-1, 5))
+    if table.size and (np.abs(table) >= 2 ** 31).any():
+        raise ValueError('tile table out of the int32 range')
+    recs = (VkxCombineTile * max(1, len(table)))()
+    if len(table):
+        view = struct_view(recs)
+        for k, name in enumerate(('up', 'down', 'left', 'right', 'source')):
+            view[name][:len(table)] = table[:, k]
+    keep = []
+    srcs = (VkxCombineSource * max(1, len(sources)))()
+    for rec, src in zip(srcs, sources):
+        if not isinstance(src, DevArray):
+            src = ctx.to_device(np.ascontiguousarray(src))
+        if np.dtype(src.dtype) != np.uint8 or src.ndim != 3 or src.shape[2] != 3:
+            raise ValueError('a texture is uint8 (H, W, 3)')
+        keep.append(src)
+        rec.image, rec.height, rec.width = src.ptr, src.shape[0], src.shape[1]
+    out = ctx.dev_empty((h, w, 3), np.uint8)
+    check(lib().vkx_image_combine_u8c3_dev(ctx.handle, recs, len(table), srcs, len(sources), int(ksize),
+                                           int(ksize) // 2 + 1 if half is None else int(half), float(sigma), c_void_p(out.ptr), h, w))
+    return out if resident_mode() else out.host()
+
+
+def dev_full(shape, value, dtype=np.uint8, ctx=None):
+    """A DevArray with every byte-sized element set to ``value`` (a device fill: nothing crosses the bus)."""
+    ctx = ctx or default_ctx()
+    if np.dtype(dtype).itemsize != 1:
+        raise ValueError('dev_full fills single-byte elements')
+    arr = ctx.dev_empty(shape, dtype)
+    if arr.nbytes:
+        check(lib().vkx_memset(ctx.handle, c_void_p(arr.ptr), int(value) & 255, arr.nbytes))
+    return arr
 
 
 class CharMaskSet:

@@ -320,17 +320,6 @@ __device__ __forceinline__ bool div_pair_f32_fast(double nx, double ny, double d
     return __builtin_amdgcn_ballot_w64(danger) == 0;
 }
 
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        if (p < 0) p = -p;
-        else p = 2 * (len - 1) - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
-
 // cv.remap's bilinear sample of an RGB pixel whose 2 x 2 taps are not all inside the source (the rim of the result and
 // everything that maps outside): vkd::sample_u8<3> on the kernel's global-address-space source pointer, every tap its own
 // predicated byte load.  Returns r | b << 16 and g.
@@ -685,7 +674,7 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
         int srcl[2 * RMAX + 1];   // lane (x 4) holding tap i of this lane's horizontal stencil (BORDER_REFLECT_101)
 #pragma unroll
         for (int i = 0; i < 2 * RMAX + 1; i++) {
-            int s = (R > 0 && i < K) ? (INTERIOR ? lane + i - R : reflect101(gx + i - R, dw) - wx0) : lane;
+            int s = (R > 0 && i < K) ? (INTERIOR ? lane + i - R : vkd::reflect101(gx + i - R, dw) - wx0) : lane;
             srcl[i] = min(max(s, 0), W - 1) << 2;   // ds_bpermute takes the source lane as a byte address
         }
         const unsigned fast_xlim = (unsigned)max(sw - 2, 0), fast_ylim = (unsigned)max(sh - 1, 0);
@@ -1009,7 +998,7 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
 #pragma unroll
                     for (int j = 0; j < 2 * RMAX + 1; j++) {
                         if (j < K) {
-                            const int yy = INTERIOR ? cy + j : reflect101(gy + j - R, dh) - wy0;
+                            const int yy = INTERIOR ? cy + j : vkd::reflect101(gy + j - R, dh) - wy0;
                             const uint16_t *h16 = (const uint16_t *)(own + (yy & ~1) * P_ + lane) + (yy & 1);
                             a0 += __umul24(kq[j], (uint32_t)h16[0]);
                             a1 += __umul24(kq[j], (uint32_t)h16[128]);
@@ -1019,7 +1008,7 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
                     r = (int)((a0 + 32768u) >> 16); g = (int)((a1 + 32768u) >> 16); b = (int)((a2 + 32768u) >> 16);
                 }
                 if (phase_limit == 20) {      // debugging aid: the horizontal sums of the centre row, >> 8
-                    const int yy = INTERIOR ? cy + R : reflect101(gy, dh) - wy0;
+                    const int yy = INTERIOR ? cy + R : vkd::reflect101(gy, dh) - wy0;
                     const uint16_t *h16 = (const uint16_t *)(own + (yy & ~1) * P_ + lane) + (yy & 1);
                     r = h16[0] >> 8; g = h16[128] >> 8; b = h16[256] >> 8;
                 }

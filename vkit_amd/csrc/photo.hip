@@ -50,17 +50,6 @@ int gaussian_kernel_q8(int n, double sigma, uint16_t *kq)
     return 0;
 }
 
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        if (p < 0) p = -p;
-        else p = 2 * (len - 1) - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
-
 // Horizontal u8 x 8.8 -> 8.8 then vertical 8.8 x 8.8 -> 16.16, (v + 2^15) >> 16, BORDER_REFLECT_101.
 template <int CN>
 __global__ void __launch_bounds__(256) k_gaussian_blur(const uint8_t *__restrict__ src, int h, int w, ptrdiff_t sstride,
@@ -74,12 +63,12 @@ __global__ void __launch_bounds__(256) k_gaussian_blur(const uint8_t *__restrict
 #pragma unroll
     for (int c = 0; c < CN; c++) acc[c] = 0;
     for (int j = 0; j < K.kh; j++) {
-        const uint8_t *row = src + (ptrdiff_t)reflect101(y + j - ry, h) * sstride;
+        const uint8_t *row = src + (ptrdiff_t)vkd::reflect101(y + j - ry, h) * sstride;
         uint32_t hacc[CN];
 #pragma unroll
         for (int c = 0; c < CN; c++) hacc[c] = 0;
         for (int i = 0; i < K.kw; i++) {
-            const uint8_t *p = row + (ptrdiff_t)reflect101(x + i - rx, w) * CN;
+            const uint8_t *p = row + (ptrdiff_t)vkd::reflect101(x + i - rx, w) * CN;
             const uint32_t kx = K.kw == 1 ? 256u : K.k[i];
 #pragma unroll
             for (int c = 0; c < CN; c++) hacc[c] += kx * p[c];
@@ -108,13 +97,13 @@ __global__ void __launch_bounds__(256) k_gaussian_blur_tiled(const uint8_t *__re
     const int r = K.kw / 2;                       // kw == kh here
     const int tw = 64 - 2 * r;
     const int x0 = blockIdx.x * tw, y0 = blockIdx.y * kBlurTileH;
-    const int gx = reflect101(x0 - r + lane, w);   // the column this lane holds during the horizontal pass
+    const int gx = vkd::reflect101(x0 - r + lane, w);   // the column this lane holds during the horizontal pass
     const int rows = min(kBlurTileH, h - y0) + 2 * r;
     uint32_t kq[2 * kBlurRMax + 1];
 #pragma unroll
     for (int i = 0; i < 2 * kBlurRMax + 1; i++) kq[i] = i < K.kw ? K.k[i] : 0;
     for (int row = wave; row < rows; row += 4) {
-        const uint8_t *p = src + (ptrdiff_t)reflect101(y0 - r + row, h) * sstride + (ptrdiff_t)gx * CN;
+        const uint8_t *p = src + (ptrdiff_t)vkd::reflect101(y0 - r + row, h) * sstride + (ptrdiff_t)gx * CN;
         uint32_t px[CN], acc[CN];
 #pragma unroll
         for (int c = 0; c < CN; c++) { px[c] = p[c]; acc[c] = 0; }
@@ -170,7 +159,7 @@ __global__ void __launch_bounds__(256) k_gaussian_blur_rgb(const uint8_t *__rest
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * kBlurTileH + 8 * wave;
     if (y0 >= h) return;
-    const int gx = reflect101(x0 - R + lane, w);
+    const int gx = vkd::reflect101(x0 - R + lane, w);
     const bool last = gx == w - 1;          // the image's last column reads the dword that ENDS with its pixel
     uint32_t kq[KS];
 #pragma unroll
@@ -181,7 +170,7 @@ __global__ void __launch_bounds__(256) k_gaussian_blur_rgb(const uint8_t *__rest
         for (int r = 0; r < NR; r++) ry[r] = y0 - R + r;
     } else {
 #pragma unroll
-        for (int r = 0; r < NR; r++) ry[r] = reflect101(y0 - R + r, h);
+        for (int r = 0; r < NR; r++) ry[r] = vkd::reflect101(y0 - R + r, h);
     }
     const uint32_t voff = (uint32_t)gx * 3u - (last ? 1u : 0u);       // scalar row base + 32-bit lane offset: saddr loads
     uint32_t px[NR];
@@ -266,7 +255,7 @@ __global__ void __launch_bounds__(256) k_filter2d_u8(const uint8_t *__restrict__
     const int tw = kF2dTileW + K.kw - 1, th = kF2dTileH + K.kh - 1;
     for (int i = threadIdx.x; i < tw * th; i += 256) {
         const int ty = i / tw, tx = i - ty * tw;
-        const uint8_t *p = src + (ptrdiff_t)reflect101(y0 + ty - ay, h) * sstride + (ptrdiff_t)reflect101(x0 + tx - ax, w) * CN;
+        const uint8_t *p = src + (ptrdiff_t)vkd::reflect101(y0 + ty - ay, h) * sstride + (ptrdiff_t)vkd::reflect101(x0 + tx - ax, w) * CN;
 #pragma unroll
         for (int c = 0; c < CN; c++) tile[i * CN + c] = p[c];
     }

@@ -111,6 +111,7 @@ struct vkx_ctx {
     vkx_scratch fog_work;                     // fog field (fog.hip): raw draws + the float64 centres of a level; a glass round's temporaries
     vkx_scratch jpeg_planes;                  // jpeg round trip (jpeg.hip): the decoded Y, Cb, Cr planes at their padded sizes
     vkx_scratch crop_windows, crop_planes;      // page cropping (crop.hip): the window and plane tables of the last call
+    vkx_scratch combine_tables;               // combiner image engine (image_combine.hip): block bins + tile records of the last call
     vkx_scratch char_table, char_geo, char_layout, char_host;   // char masks (char_mask.hip): chars, setup results, tile layout,
                                                                 // staging of the host form
     vkx_scratch char_owner;                   // ... the ownership planes: all zero between calls (the resolve clears what it reads)
@@ -283,6 +284,18 @@ __device__ __forceinline__ int cv_round(double v)
 {
     if (!(v >= -2147483648.5 && v < 2147483647.5)) return INT_MIN;
     return __double2int_rn(v);
+}
+// BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba): the border rule of the uint8 Gaussian blur, shared by every kernel that reads
+// a blur window (photo.hip, fused.hip, image_combine.hip).
+__device__ __forceinline__ int reflect101(int p, int len)
+{
+    if ((unsigned)p < (unsigned)len) return p;
+    if (len == 1) return 0;
+    do {
+        if (p < 0) p = -p;
+        else p = 2 * (len - 1) - p;
+    } while ((unsigned)p >= (unsigned)len);
+    return p;
 }
 __device__ __forceinline__ int sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 __device__ __forceinline__ int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }

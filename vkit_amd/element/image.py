@@ -133,6 +133,26 @@ class Image(LazyMat, Shapable):
     def from_shapable(cls, shapable: Shapable, num_channels: int = 3, value: Union[Tuple[int, ...], int] = 255):
         return cls.from_shape(shapable.shape, num_channels=num_channels, value=value)
 
+    @classmethod
+    def from_pil_image(cls, pil_image):
+        # an explicit copy: the array of a PIL image is not writable
+        return cls(mat=np.array(pil_image, dtype=np.uint8))
+
+    @classmethod
+    def from_file(cls, path, disable_exif_orientation: bool = False):
+        """The decoded file (reference image.py:325-349): Pillow ``open`` + ``load``, the EXIF orientation applied unless
+        disabled, the mode inferred from the decoded array (2-D: GRAYSCALE, 3 channels: RGB, 4: RGBA)."""
+        import os
+        from PIL import Image as PilImage, ImageOps as PilImageOps
+        # PilImage.open cannot handle `~`
+        pil_image = PilImage.open(os.path.expanduser(os.fspath(path)))
+        pil_image.load()
+        if not disable_exif_orientation:
+            # tag 0x0112; transposed only when set, which avoids a copy
+            if pil_image.getexif().get(0x0112):
+                pil_image = PilImageOps.exif_transpose(pil_image)
+        return cls.from_pil_image(pil_image)
+
     # ---- properties
     @property
     def height(self):

@@ -1,5 +1,13 @@
 from .page_assembler import *  # noqa: F401,F403
 from .page_assembler import page_assembler_step_factory  # noqa: F401
+from .page_background import (  # noqa: F401
+    PageBackgroundStep,
+    PageBackgroundStepConfig,
+    PageBackgroundStepInput,
+    PageBackgroundStepKey,
+    PageShapeStepOutput,
+    page_background_step_factory,
+)
 from .page_distortion import (  # noqa: F401
     ElementFlattener,
     PageDistortionStep,

@@ -254,15 +254,13 @@ class PageAssemblerStep(PipelineStep[PageAssemblerStepConfig, PageAssemblerStepI
     def run(self, input: PageAssemblerStepInput, rng: RandomGenerator):
         page_layout = input.page_layout_step_output.page_layout
         background_image = input.page_background_step_output.background_image
-        page_image_collection = input.page_image_step_output.page_image_collection
-        page_bottom_layer_image = input.page_image_step_output.page_bottom_layer_image
-        barcodes = input.page_barcode_step_output
-        page_text_line_collection = input.page_text_line_step_output.page_text_line_collection
-        seal_collection = input.page_text_line_step_output.page_seal_impression_text_line_collection
-        symbols = input.page_non_text_symbol_step_output
-        bounding_boxes = input.page_text_line_bounding_box_step_output
-        labels = input.page_text_line_label_step_output
 
+        if background_image.on_device:
+            # a background born on the device (PageBackgroundStep in resident mode) is taken where it is: the page starts as a device-to-
+            # device copy of it, queued on the stream that produced it -- no download, no upload, nothing read over the bus
+            assert tuple(background_image.arr.shape) == (page_layout.height, page_layout.width, 3)
+            assert background_image.arr.dtype == np.uint8
+            return self.assemble(input, attrs.evolve(background_image, mat=_native.device_copy(background_image.arr)), None)
         assert background_image.mat.shape == (page_layout.height, page_layout.width, 3)
         # the page is assembled on the device: the background (the copy the reference makes, page_assembler.py:143) is the FIRST layer of the
         # one composite launch -- a plain full-page copy, read in place from the page-locked ring like every other layer plane, so the
@@ -274,6 +272,20 @@ class PageAssemblerStep(PipelineStep[PageAssemblerStepConfig, PageAssemblerStepI
                     and background_image.box is None)
         assembled_image = attrs.evolve(background_image, mat=ctx.dev_empty(background_mat.shape, np.uint8) if as_layer
                                        else ctx.to_device(background_mat))
+        return self.assemble(input, assembled_image, background_mat if as_layer else None)
+
+    def assemble(self, input: PageAssemblerStepInput, assembled_image: Image, background_layer: Optional[np.ndarray]):
+        """The layers of the page composited onto ``assembled_image`` (a device-resident image); ``background_layer``: the host
+        background as the first layer, or None when the image already holds it."""
+        page_layout = input.page_layout_step_output.page_layout
+        page_image_collection = input.page_image_step_output.page_image_collection
+        page_bottom_layer_image = input.page_image_step_output.page_bottom_layer_image
+        barcodes = input.page_barcode_step_output
+        page_text_line_collection = input.page_text_line_step_output.page_text_line_collection
+        seal_collection = input.page_text_line_step_output.page_seal_impression_text_line_collection
+        symbols = input.page_non_text_symbol_step_output
+        bounding_boxes = input.page_text_line_bounding_box_step_output
+        labels = input.page_text_line_label_step_output
 
         # Seal impressions are rotated first (device warps, independent of the page); their layers are recorded
         # last, so the composite order is untouched.
@@ -300,9 +312,9 @@ class PageAssemblerStep(PipelineStep[PageAssemblerStepConfig, PageAssemblerStepI
                 polygon.to_shifted_polygon(offset_y=up, offset_x=left) for polygon in (rotated.polygons or ()))
 
         with deferred_fill(assembled_image.arr):
-            if as_layer:
+            if background_layer is not None:
                 Box(up=0, down=assembled_image.height - 1, left=0, right=assembled_image.width - 1).fill_image(
-                    assembled_image, background_mat, alpha=1.0)
+                    assembled_image, background_layer, alpha=1.0)
             for page_image in page_image_collection.page_images:
                 page_image.box.fill_image(assembled_image, page_image.image, alpha=page_image.alpha)
             for score_map in barcodes.barcode_qr_score_maps:

@@ -23,6 +23,16 @@ def _is_path(obj: Any):
     return isinstance(obj, (str, PathLike))
 
 
+def is_path_type(path: Any):
+    return _is_path(path)
+
+
+def read_json_file(path: PathType):
+    """The JSON document at ``path`` (environment variables and ``~`` expanded)."""
+    with open(os.path.expandvars(os.path.expanduser(os.fspath(path)))) as fin:
+        return json.load(fin)
+
+
 def _structure_value(value: Any, tp: Any):
     """Best-effort structuring of ``value`` into annotation ``tp`` (attrs classes, enums, Optional, sequences)."""
     if value is None or tp is Any or tp is None:
@@ -72,8 +82,7 @@ def dyn_structure(dyn_object: Any, target_cls: Type[_T], support_path_type: bool
         if force_path_type:
             assert is_path
         if is_path:
-            with open(os.path.expandvars(os.path.expanduser(os.fspath(dyn_object)))) as fin:
-                dyn_object = json.load(fin)
+            dyn_object = read_json_file(dyn_object)
     try:
         if isinstance(dyn_object, target_cls):
             return dyn_object
