@@ -27,15 +27,18 @@ COVERED_DEV = {
     'vkx_jpeg_roundtrip_u8_dev', 'vkx_zoom_in_blur_u8_dev', 'vkx_noise_normal_i16_dev',
 }
 
-# host entry points run on pitched host buffers with canaries (HostStage's pitched gather and copy-out)
+# host entry points run on pitched host buffers with canaries: the pitched gather and copy-out of HostStage
+# (vkit_amd/csrc/vkx_host_stage.h), and the plane copies of the three host forms that stage by hand (vkx_ellipse_mask_u8,
+# vkx_ellipse_streak_u8, vkx_sum_f32_u8)
 COVERED_HOST = {
     'vkx_remap_u8', 'vkx_warp_affine_u8', 'vkx_gaussian_blur_u8', 'vkx_filter2d_u8', 'vkx_color_shift_rgb', 'vkx_blend_u8',
     'vkx_fill_u8', 'vkx_resize_u8', 'vkx_resize_f32', 'vkx_line_streak_u8', 'vkx_speckle_noise_u8', 'vkx_fog_f32_u8',
     'vkx_gather_u8', 'vkx_jpeg_roundtrip_u8', 'vkx_zoom_in_blur_u8', 'vkx_cvt_color_u8', 'vkx_noise_normal_i16',
+    'vkx_ellipse_mask_u8', 'vkx_ellipse_streak_u8', 'vkx_sum_f32_u8',
 }
 
-_HOST_FORM = 'the host form stages through the same HostStage gather / copy-out as the host entry points of COVERED_HOST ' \
-             'and runs the _dev form this table covers'
+_HOST_FORM = 'the host form is a vkx_host_run call (vkit_amd/csrc/vkx_host_stage.h): the HostStage gather / copy-out of the ' \
+             'host entry points of COVERED_HOST around the _dev form this table covers'
 
 EXEMPT = {
     'vkx_remap_f32': _HOST_FORM,
@@ -49,11 +52,8 @@ EXEMPT = {
     'vkx_color_balance_rgb': _HOST_FORM,
     'vkx_pointwise_u8': _HOST_FORM,
     'vkx_histogram_u8': _HOST_FORM,
-    'vkx_sum_f32_u8': _HOST_FORM,
     'vkx_apply_lut_u8': _HOST_FORM,
     'vkx_impulse_noise_u8': _HOST_FORM,
-    'vkx_ellipse_mask_u8': _HOST_FORM,
-    'vkx_ellipse_streak_u8': _HOST_FORM,
     'vkx_fill_f32': _HOST_FORM,
     'vkx_resize_cubic_u8': _HOST_FORM,
     'vkx_resize_cubic_f32': _HOST_FORM,

@@ -530,12 +530,12 @@ def build_cases():
         add(f'ellipse_streak cn{cn}', 'vkx_ellipse_streak_u8', {'img': (img, img.shape, u8, 'inout')},
             lambda fn, P, cn=cn, col=col, axes=axes: fn(H, P['img'].p, 70, 90, cn, P['img'].stride, 44, 33, axes.ctypes.data, 2, 2,
                                                         col.ctypes.data, 0.7),
-            {'img': later(_ellipse_streak, O, img, (44, 33), axes, 2, tuple(int(c) for c in col[:cn]), 0.7)})
+            {'img': later(_ellipse_streak, O, img, (44, 33), axes, 2, tuple(int(c) for c in col[:cn]), 0.7)}, host=True)
     mask0 = (rng.random((70, 90)) < 0.02).astype(np.uint8) * 7
     axes = np.array([[20, 12], [35, 28], [3, 50]], np.int32)
     wantm = later(_outlined, O, mask0, (44, 33), axes, 3)
     add('ellipse_mask', 'vkx_ellipse_mask_u8', {'mask': (mask0, mask0.shape, u8, 'inout')},
-        lambda fn, P: fn(H, P['mask'].p, P['mask'].stride, 70, 90, 44, 33, axes.ctypes.data, 3, 3), {'mask': wantm})
+        lambda fn, P: fn(H, P['mask'].p, P['mask'].stride, 70, 90, 44, 33, axes.ctypes.data, 3, 3), {'mask': wantm}, host=True)
 
     # ---- noise and effects
     for cn in (1, 3):
@@ -591,7 +591,7 @@ def build_cases():
             out = np.zeros(len(chans), np.float32)
             rc = fn(H, P['src'].p, 67, 129, cn, P['src'].stride, chans.ctypes.data, len(chans), seq, out.ctypes.data)
             return rc, {'sums': out}
-        add(f'sum_f32 cn{cn} seq{seq}', 'vkx_sum_f32_u8', {'src': (img, img.shape, u8, 'in')}, summ, {'sums': want})
+        add(f'sum_f32 cn{cn} seq{seq}', 'vkx_sum_f32_u8', {'src': (img, img.shape, u8, 'in')}, summ, {'sums': want}, host=True)
     h, w = 39, 57
     rgb, gray, rgba = _img(rng, h, w, 3), _img(rng, h, w, 1), _img(rng, h, w, 4)
     a255 = np.full((h, w, 1), 255, np.uint8)
@@ -672,7 +672,8 @@ def test_layouts(case_name):
 
 @pytest.mark.gpu
 def test_host_entry_points_on_pitched_host_memory(case_name):
-    """the non-_dev form on host buffers whose pitch exceeds the row (HostStage's pitched gather and copy-out)"""
+    """the non-_dev form on host buffers whose pitch exceeds the row (the pitched gather and copy-out of HostStage,
+    vkit_amd/csrc/vkx_host_stage.h, or the host form's own plane copies)"""
     from vkit_amd import _native as N
     case = cases()[case_name]
     ctx = N.default_ctx()

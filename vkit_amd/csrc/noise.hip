@@ -16,6 +16,7 @@
 //     the midpoint of the u-th of 65536 equal slices, built on the host in double precision, clamped to +-32767).
 // The quantisation of the probabilities to multiples of 2^-16 cuts the tails beyond ~4.2 std.
 #include "vkx_internal.h"
+#include "vkx_host_stage.h"
 
 #include <math.h>
 #include <algorithm>
@@ -211,19 +212,10 @@ VKX_EXPORT int vkx_noise_normal_i16(vkx_ctx *ctx, int16_t *dst, ptrdiff_t stride
                                     uint64_t seed)
 {
     VKX_REQUIRE(ctx && dst, "NULL argument");
-    VKX_REQUIRE(h >= 0 && w >= 0 && cn >= 1 && cn <= 4 && stride_el >= (ptrdiff_t)w * cn, "bad shape");
+    VKX_REQUIRE(h >= 0 && w >= 0 && cn >= 1 && cn <= 4, "bad shape");
     if (h == 0 || w == 0) return VKX_OK;
-    const size_t bytes = sizeof(int16_t) * (size_t)h * w * cn;
-    int rc = vkx_scratch_reserve(ctx, &ctx->stage[1], bytes);
-    if (rc) return rc;
-    rc = vkx_noise_normal_i16_dev(ctx, (int16_t *)ctx->stage[1].ptr, (ptrdiff_t)w * cn, h, w, cn, std, seed);
-    if (rc) return rc;
-    vkx_device_guard guard(ctx);
-    if (stride_el == (ptrdiff_t)w * cn)
-        VKX_HIP(hipMemcpyAsync(dst, ctx->stage[1].ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    else
-        VKX_HIP(vkx_copy_plane(dst, (size_t)stride_el * 2, ctx->stage[1].ptr, (size_t)w * cn * 2, (size_t)w * cn * 2, (size_t)h,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-    VKX_HIP(hipStreamSynchronize(ctx->stream));
-    return VKX_OK;
+    auto d = vkx_out(dst, h, w, cn, stride_el);
+    return vkx_host_run(ctx, {&d}, [&] {
+        return vkx_noise_normal_i16_dev(ctx, d.dev(), d.pitch, h, w, cn, std, seed);
+    });
 }

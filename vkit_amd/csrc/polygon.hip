@@ -9,6 +9,7 @@
 //                   [ceil(xa), floor(xb)] cooperatively.
 // Vertices are host data (a few to a few thousand points); the edge table is built on the host and staged.
 #include "vkx_internal.h"
+#include "vkx_host_stage.h"
 #include <string.h>
 #include "vkx_cell.h"
 
@@ -460,15 +461,10 @@ VKX_EXPORT int vkx_fill_poly_mask_u8(vkx_ctx *ctx, const int32_t *pts_host, int 
 {
     VKX_REQUIRE(ctx && pts_host && mask, "NULL argument");
     VKX_REQUIRE(npts > 0 && h > 0 && w > 0, "bad shape");
-    VKX_REQUIRE_PITCH(stride, w, h);
-    const size_t bytes = (size_t)h * w;
-    int rc = vkx_scratch_reserve(ctx, &ctx->stage[1], bytes);
-    if (rc) return rc;
-    uint8_t *d = (uint8_t *)ctx->stage[1].ptr;
-    VKX_HIP(hipMemsetAsync(d, 0, bytes, ctx->stream));
-    rc = vkx_fill_poly_mask_u8_dev(ctx, pts_host, npts, d, h, w, w);
-    if (rc) return rc;
-    VKX_HIP(vkx_copy_plane(mask, (size_t)stride, d, (size_t)w, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, ctx->stream));
-    VKX_HIP(hipStreamSynchronize(ctx->stream));
-    return VKX_OK;
+    auto m = vkx_out(mask, h, w, 1, stride);
+    return vkx_host_run(ctx, {&m}, [&] {
+        vkx_device_guard guard(ctx);
+        VKX_HIP(hipMemsetAsync(m.dev(), 0, (size_t)h * w, ctx->stream));
+        return vkx_fill_poly_mask_u8_dev(ctx, pts_host, npts, m.dev(), h, w, m.pitch);
+    });
 }

@@ -92,7 +92,9 @@ struct vkx_ctx {
     vkx_scratch misc;     // small parameter blocks (layers, element descriptors)
     vkx_scratch tables;   // constant lookup tables (HSV division LUTs), uploaded once
     bool tables_ready = false;
-    vkx_scratch stage[6]; // staging planes of the host-pointer entry points
+    vkx_scratch stage[2]; // [0]: the planes of a host-pointer entry point (vkx_host_stage.h; the host forms of ellipse.hip, reduce.hip, poisson.hip,
+                          // grid.hip, mls.hip and nprand.hip stage there themselves); [1]: a second block of the forms that stage themselves
+                          // (the mask of ellipse.hip, the planes of vkx_paint_polys, the results of vkx_np_poisson_u8 and vkx_np_draw)
     vkx_scratch chain[3]; // ping-pong planes of the batched chain entry point; [2]: a tile buffer expanded to its int16 plane
     vkx_scratch chain_cells, chain_bins, chain_misc;   // cell records / tile bins / descriptors of the fused chain: its setup kernels
                                                        // run on the side stream while the shared slots above serve the compute stream
