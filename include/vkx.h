@@ -599,6 +599,10 @@ int vkx_np_draw_batch_dev(vkx_ctx *ctx, const vkx_np_job *jobs_host, int n_jobs,
 int vkx_np_tiles_layout(int64_t n, int64_t *n_tiles, int64_t *slot_elems, int64_t *table_offset, int64_t *slots_offset, int64_t *bytes);
 /* dst int16 [n] (device, 8-byte aligned) = the plane a finished tile buffer stands for; asynchronous on the ctx stream */
 int vkx_np_tiles_expand_dev(vkx_ctx *ctx, const void *tiles, int64_t n, int16_t *dst);
+/* Debug: est[i] (device, float64) = the float32-logarithm estimate of -log(1 - u), u = (draws[i] >> 11) * 2^-53, from which the integer
+ * kinds decide a ziggurat tail pass; *eps (host, may be NULL) = the absolute error the kernels assume of it.  Asynchronous on the ctx
+ * stream.  The kernels take the float64 log1p wherever that error could change a decision or an emitted integer. */
+int vkx_np_tail_log_est_dev(vkx_ctx *ctx, const uint64_t *draws, int64_t n, double *est, double *eps);
 /* one job whose src / dst are HOST arrays; synchronous */
 int vkx_np_draw(vkx_ctx *ctx, const vkx_np_job *job, vkx_np_result *result_host);
 

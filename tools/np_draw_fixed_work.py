@@ -8,7 +8,7 @@ tile's first 64 is a tail draw and how many passes the tail loop makes, whether 
 events some earlier span reaches, the phase-3 walks and the cover loop's trips.  Blocks are sorted into the kernel's parts by what
 they hold (tools/np_draw_census.py's block split; the rules are below in `part_of`); a part's blocks run as often as the part.
 
-Usage: tools/np_draw_fixed_work.py [--src nprand.hip] [--run-carry] [--jobs 16] [--tiles-per-wave 2] [--tiles 3000]
+Usage: tools/np_draw_fixed_work.py [--src nprand.hip] [--run-carry] [--jobs 16] [--tiles-per-wave 2] [--tiles 3000] [--scale 10]
                                    [--valu SQ_INSTS_VALU] [--waves SQ_WAVES]
   --jobs / --tiles-per-wave / --valu / --waves: the launch the PMC figures were taken at (bench --batch 32: two launches of 16
   streams per step, ~78 700 tiles each, two tiles per wavefront).  Tiles per launch = wavefronts x tiles per wavefront: the
@@ -41,14 +41,36 @@ def u2dbl(u):
     return (u >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
 
 
-def tile_stats(n_tiles, seed):
+TAIL_EPS = 2.0 ** -16      # kTailEps of nprand.hip
+K_INV_R, NOR_R = 0.27366123732975827, 3.6541528853610088
+
+
+def tail_fast_pass(u1, u2, neg, scale):
+    """The fast tail pass of the integer emitters as nprand.hip decides it, with numpy's float32 log2 standing in for v_log_f32:
+    'reject' / 'accept' when the float32 estimates prove the pass (and, for an accept, the emitted integer), else 'float64'."""
+    l1 = -0.6931471805599453 * float(np.log2(np.float32(1.0 - u1)))
+    l2 = -0.6931471805599453 * float(np.log2(np.float32(1.0 - u2)))
+    xe = K_INV_R * l1
+    r2 = xe * xe
+    diff = 2.0 * l2 - r2
+    bound = 2.0 * TAIL_EPS + K_INV_R * K_INV_R * (2.0 * l1 * TAIL_EPS + TAIL_EPS * TAIL_EPS) + 2.0 ** -30 * (1.0 + r2)
+    if abs(diff) <= bound:
+        return 'float64'
+    if diff < 0.0:
+        return 'reject'
+    v = scale * (-(NOR_R + xe) if neg else NOR_R + xe)
+    dist = abs((v - math.floor(v)) - 0.5)
+    return 'accept' if dist > abs(scale) * K_INV_R * TAIL_EPS + 2.0 ** -26 + abs(v) * 2.0 ** -50 else 'float64'
+
+
+def tile_stats(n_tiles, seed, scale=10.0, fast_tail=True):
     """Per tile: events, push rounds, tail passes of the first phase-2 pass, exp() fallback, reach / touch, cover-loop trips."""
     ki, wi, fi = tables()
     raw = np.random.default_rng(seed).bit_generator.random_raw(n_tiles * TILE + 512).astype(np.uint64)
     idx = (raw & np.uint64(0xff)).astype(np.int64)
     rabs = (raw >> np.uint64(9)) & np.uint64((1 << 52) - 1)
     slow = rabs >= ki[idx]
-    st = {k: [] for k in ('nev', 'push_rounds', 'tail_passes', 'exp_any', 'touch', 'reach', 'cov_trips', 'over64')}
+    st = {k: [] for k in ('nev', 'push_rounds', 'tail_passes', 'tail_f64', 'tail_all', 'exp_any', 'touch', 'reach', 'cov_trips', 'over64')}
     for t in range(n_tiles):
         b = t * TILE
         pos = np.flatnonzero(slow[b:b + TILE])
@@ -56,7 +78,7 @@ def tile_stats(n_tiles, seed):
         st['nev'].append(nev)
         st['over64'].append(nev > 64)
         st['push_rounds'].append(len(np.unique(pos >> 6)))
-        lens, exp_any, passes = [], False, 0
+        lens, exp_any, passes, f64, all_passes = [], False, 0, 0, 0
         for k, p in enumerate(pos):
             g = b + p
             if idx[g] != 0:
@@ -73,6 +95,10 @@ def tile_stats(n_tiles, seed):
                     u1, u2 = u2dbl(raw[q + 1:q + 3])
                     q += 2
                     n += 2
+                    all_passes += 1
+                    # (a trip of the tail loop runs the float64 pass when one of its lanes asks for it: rare enough to add up)
+                    if fast_tail and k < 64 and tail_fast_pass(u1, u2, (int(rabs[g]) >> 8) & 1, scale) == 'float64':
+                        f64 += 1
                     xx = -0.27366123732975827 * math.log1p(-u1)
                     if -2 * math.log1p(-u2) > xx * xx:
                         break
@@ -80,6 +106,8 @@ def tile_stats(n_tiles, seed):
                 if k < 64:
                     passes = max(passes, (n - 1) // 2)
         st['tail_passes'].append(passes)
+        st['tail_f64'].append(f64 if fast_tail else passes)
+        st['tail_all'].append(all_passes)
         st['exp_any'].append(exp_any)
         ends = pos + np.array(lens, np.int64)
         prev_end = np.concatenate(([0], ends[:-1]))
@@ -107,7 +135,8 @@ def part_of(b, phase1_loop, loops):
     if b['depth'] >= 2:
         sig = loops[b['loop']]
         if sig['rcp']:
-            return 'tail loop'
+            # (a build with the fast tail pass keeps the float64 pass -- the blocks with log1p's divisions -- for the lanes in doubt)
+            return 'tail float64 pass' if sig['log32'] and any(o.startswith('v_rcp_f64') for o in b['ops']) else 'tail loop'
         if sig['gload']:
             return 'job search'
         if sig['readlane'] and not sig['ds']:
@@ -127,6 +156,7 @@ def main():
     ap.add_argument('--tiles-per-wave', type=float, default=2)
     ap.add_argument('--tiles', type=int, default=3000)
     ap.add_argument('--seed', type=int, default=12345)
+    ap.add_argument('--scale', type=float, default=10.0, help='std of the streams (the bench draws at 10): the fast tail pass proves its integer against it')
     ap.add_argument('--valu', type=float, default=2.2452e8, help='PMC SQ_INSTS_VALU of k_np_draw_compact per launch')
     ap.add_argument('--waves', type=float, default=39364, help='PMC SQ_WAVES of the same launches')
     ap.add_argument('--run-carry', action='store_true', help='the build carries the lane states along a run of tiles')
@@ -141,9 +171,10 @@ def main():
     loops = {}
     for b in blocks:
         if b['depth'] >= 2:
-            s = loops.setdefault(b['loop'], {'rcp': False, 'gload': False, 'readlane': False, 'ds': False, 'depth3': False,
+            s = loops.setdefault(b['loop'], {'rcp': False, 'log32': False, 'gload': False, 'readlane': False, 'ds': False, 'depth3': False,
                                              'ds_read_u16': False, 'lshl64': False})
             s['rcp'] |= any(o.startswith('v_rcp_f64') for o in b['ops'])
+            s['log32'] |= any(o.startswith('v_log_f32') for o in b['ops'])
             s['gload'] |= any(o.startswith('global_load') for o in b['ops'])
             s['readlane'] |= 'v_readlane_b32' in b['ops']
             s['ds'] |= any(o.startswith('ds_') for o in b['ops'])
@@ -154,7 +185,7 @@ def main():
     # pass the float64 exp() fallback (the depth-1 block with v_fma_f64 after the one with v_exp_f32) runs when a lane asks for
     # it, the tail branch around its loop (the block before the loop and those after it up to the mask atomics) when a lane has one
     parts = [part_of(b, phase1, loops) for b in blocks]
-    tail_idx = [i for i, p in enumerate(parts) if p == 'tail loop']
+    tail_idx = [i for i, p in enumerate(parts) if p in ('tail loop', 'tail float64 pass')]
     cond = {}
     if tail_idx:
         heads = sorted({blocks[i]['loop'] for i in tail_idx}, key=lambda l: min(i for i in tail_idx if blocks[i]['loop'] == l))
@@ -204,7 +235,8 @@ def main():
             parts[i] = 'tile start'
         elif parts[i] == 'per tile' and any('row_bcast' in s for s in b.get('text', [])):
             parts[i] = 'phase 3 reach scan'
-    st = tile_stats(args.tiles, args.seed)
+    fast_tail = any(s['log32'] for s in loops.values())
+    st = tile_stats(args.tiles, args.seed, args.scale, fast_tail)
     k1 = sum(b['ops'].count('ds_read_b128') for b in blocks if b['loop'] == phase1 and not C.is_push(b)) or 2
     trips = ROUNDS / k1
     # per tile: how often a block of each part runs
@@ -220,6 +252,7 @@ def main():
         'phase 1 push': None,            # a push block belongs to one round of the trip: it runs when that round has an event
         'job search': math.ceil(math.log2(max(args.jobs, 2))) / (args.tiles_per_wave if args.run_carry else 1.0),
         'tail loop': float(st['tail_passes'].mean()),
+        'tail float64 pass': float(st['tail_f64'].mean()),
         'phase 3 walk': float((st['reach'] if args.run_carry else st['nev'] * st['touch']).mean()),
         'phase 3 serial (> 64 events)': float((st['nev'] * st['over64']).mean()),
         'phase 3 cover loop': float(st['cov_trips'].mean()),
@@ -245,6 +278,9 @@ def main():
           f'(passes {st["tail_passes"].mean():.3f}), exp() fallback {st["exp_any"].mean():.4f}, touch {st["touch"].mean():.3f}, '
           f'events an earlier span reaches {st["reach"].mean():.2f}, > 64 events {st["over64"].mean():.4f}.  '
           f'Launch: {args.jobs} streams, {args.tiles_per_wave:g} tiles per wavefront.\n')
+    if fast_tail:
+        print(f'Fast tail pass (std {args.scale:g}): {int(st["tail_all"].sum())} tail passes in all, {int(st["tail_f64"].sum())} of them through the '
+              f'float64 pass ({100 * st["tail_f64"].sum() / max(1.0, st["tail_all"].sum()):.3f} %).\n')
     print('| part | blocks | static VALU | runs per tile | VALU per tile | per round |')
     print('|---|---|---|---|---|---|')
     for part, (v, w, names) in sorted(rows.items(), key=lambda kv: -kv[1][1]):

@@ -211,14 +211,54 @@ __device__ __forceinline__ int rounded_step(const NpJob &job, double z, bool ine
     // the step is stored (the draw pass packs two of them into a dword as they are)
     return (int)(uint32_t)__double_as_longlong(v + 6755399441055744.0);
 }
+// The ziggurat tail, decided in float32 (walk_tile, phase 2)
+// ----------------------------------------------------------
+// A tail pass takes two uniforms and asks whether 2 * L2 > (kNorInvR * L1)^2 with L = -log(1 - u); the sample is +-(kNorR + kNorInvR * L1).
+// The emitters that keep an integer of it need neither logarithm to float64 precision: the pass is decided, and the integer
+// formed, from an estimate of L whose absolute error is bounded by kTailEps, wherever the bound leaves no doubt; the rest takes
+// the float64 log1p path.
+//
+// tail_log_est: w = (float)(1 - u), L ~ -ln 2 * v_log_f32(w), the scaling in float64.  u is a multiple of 2^-53 in [0, 1), so 1 - u
+// is exact in float64 and lies in [2^-53, 1]: w is a normal float32 and log2(w) lies in [-53, 0].
+//   narrowing    |w - (1 - u)| <= 2^-24 (1 - u), which moves ln by at most 2^-24 / (1 - 2^-24) < 1.0000001 * 2^-24
+//   instruction  v_log_f32 is documented to 1 ulp of its result; |result| <= 53 < 64, where an ulp is 2^-18: <= 2^-18 in log2,
+//                ln 2 * 2^-18 = 0.6932 * 2^-18 in ln
+//   scaling      one float64 product by the float64 ln 2: relative 2^-52 of at most 36.8, < 2^-46
+// Sum: 0.6932 * 2^-18 + 2^-24 + 2^-46 < 0.71 * 2^-18 = 2.71e-6.  kTailEps = 2^-16 is that bound with a factor 5.6 to spare
+// (tests/test_gpu_np_draw_tail.py measures the estimate against log1p and wants the worst error below kTailEps / 4).  The windows in
+// which device libm and glibc may disagree (2^-40 relative on the decision, 1e-9 on the integer) are ten thousand times narrower than
+// what kTailEps induces, and the proofs add them as slack: a proven decision or integer is numpy's and raises no flag.
+constexpr double kTailEps = 0x1p-16;
+__device__ __forceinline__ double tail_log_est(uint64_t draw)
+{
+    const float w = (float)(1.0 - u2dbl(draw));
+    return -0.69314718055994530942 * (double)__builtin_amdgcn_logf(w);
+}
+// The integer of a tail sample from the estimate ze = +-(kNorR + kNorInvR * L1e): |ze - z| <= kNorInvR * kTailEps, so
+// |scale * ze - scale * z| <= scale * kNorInvR * kTailEps, and rint() of the two agree when scale * ze is further than that from
+// the nearest half-integer.  Slack: 2^-26 covers the 1e-9 window of rounded_step's own libm test, |v| 2^-50 the float64
+// roundings of the two products and sums on either side (four, half an ulp each).
+__device__ __forceinline__ bool rounded_step_proven(const NpJob &job, double ze)
+{
+    const double v = job.scale * ze;
+    const double dist = fabs((v - floor(v)) - 0.5);
+    return dist > fabs(job.scale) * (kNorInvR * kTailEps) + 0x1p-26 + fabs(v) * 0x1p-50;
+}
+
+// kFastTail: the emitter keeps at most an integer of a tail sample; tail_proven(job, ze): that integer is the same for every z
+// within kNorInvR * kTailEps of ze.
 struct EmitNone {
+    static constexpr bool kFastTail = true;     // (the walk that only counts: the decisions)
     typedef int Val;
     typedef int16_t Store;
+    __device__ static bool tail_proven(const NpJob &, double) { return true; }
     __device__ static Val make(const NpJob &, double, bool, uint32_t &) { return 0; }
     __device__ static void store(const NpJob &, void *, long long, Val, bool, uint32_t &) {}
 };
 struct EmitI16 {   // np.round(0 + std * z).astype(int16)
     static constexpr bool kCheckAtStore = false;
+    static constexpr bool kFastTail = true;
+    __device__ static bool tail_proven(const NpJob &job, double ze) { return rounded_step_proven(job, ze); }
     typedef int Val;
     typedef int16_t Store;
     __device__ static Val make(const NpJob &job, double z, bool inexact, uint32_t &flags) { return rounded_step(job, z, inexact, flags); }
@@ -226,6 +266,8 @@ struct EmitI16 {   // np.round(0 + std * z).astype(int16)
 };
 struct EmitAddU8 {   // clip(int16(px) + noise, 0, 255): the whole gaussion_noise operator
     static constexpr bool kCheckAtStore = false;
+    static constexpr bool kFastTail = true;
+    __device__ static bool tail_proven(const NpJob &job, double ze) { return rounded_step_proven(job, ze); }
     typedef int Val;
     typedef int16_t Store;
     __device__ static Val make(const NpJob &job, double z, bool inexact, uint32_t &flags) { return rounded_step(job, z, inexact, flags); }
@@ -237,6 +279,7 @@ struct EmitAddU8 {   // clip(int16(px) + noise, 0, 255): the whole gaussion_nois
 };
 struct EmitSpeckle {   // uint8(clip(px + px * (0 + std * z), 0, 255)) in float64
     static constexpr bool kCheckAtStore = true;
+    static constexpr bool kFastTail = false;    // the float64 draw itself is stored
     typedef double Val;
     typedef double Store;
     __device__ static Val make(const NpJob &, double z, bool, uint32_t &) { return z; }
@@ -487,12 +530,36 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                 u128 t = se;
                 uint32_t len = 1;
                 double xx;
+                const bool neg = (rabs >> 8) & 1;
+                bool inexact = true;     // z carries log1p's last bits
                 for (;;) {
                     t = PCG_MULT * t + inc;
-                    const double u1 = u2dbl(pcg_out(t));
+                    const uint64_t d1 = pcg_out(t);
                     t = PCG_MULT * t + inc;
-                    const double u2 = u2dbl(pcg_out(t));
+                    const uint64_t d2 = pcg_out(t);
                     len += 2;
+                    if constexpr (Emit::kFastTail) {
+                        // the pass from float32 estimates of the two logarithms (see kTailEps): with |L1e - L1|, |L2e - L2| <= eps the
+                        // difference 2 L2 - (k L1)^2, k = kNorInvR, is known to 2 eps + k^2 (2 L1e eps + eps^2); slack 2^-30 (1 + r2)
+                        // covers the float64 roundings here and the 2^-40 r2 window of the libm test below.  Beyond that the sign is
+                        // numpy's: a reject goes on to the next pass, an accept stands when the emitter's integer is proven too.
+                        // Whatever is left in doubt -- and everything under VKX_NP_DEBUG_WIDE_MARGIN -- takes the float64 pass below.
+                        if (job.margin < 1.0) {
+                            const double L1 = tail_log_est(d1), L2 = tail_log_est(d2);
+                            const double xe = kNorInvR * L1, r2 = xe * xe;
+                            const double diff = (L2 + L2) - r2;
+                            const double bound = 2.0 * kTailEps + (kNorInvR * kNorInvR) * (2.0 * L1 * kTailEps + kTailEps * kTailEps) +
+                                                 0x1p-30 * (1.0 + r2);
+                            const bool decided = fabs(diff) > bound;
+                            if (decided && diff < 0.0 && len <= 200) continue;
+                            if (decided && diff > 0.0 && Emit::tail_proven(job, neg ? -(kNorR + xe) : kNorR + xe)) {
+                                xx = xe;
+                                inexact = false;
+                                break;
+                            }
+                        }
+                    }
+                    const double u1 = u2dbl(d1), u2 = u2dbl(d2);
                     xx = -kNorInvR * log1p(-u1);
                     const double yy = -log1p(-u2);
                     const double l2 = yy + yy, r2 = xx * xx;
@@ -500,13 +567,13 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                     if (l2 > r2 || len > 200) break;
                 }
                 if (len > 200) flags |= VKX_NP_SHORT;
-                const double z = ((rabs >> 8) & 1) ? -(kNorR + xx) : kNorR + xx;
+                const double z = neg ? -(kNorR + xx) : kNorR + xx;
                 if (MODE == kRecord) {
-                    rec_val[pos] = (typename Emit::Store)Emit::make(job, z, true, flags);
+                    rec_val[pos] = (typename Emit::Store)Emit::make(job, z, inexact, flags);
                 } else if (MODE == kCompact) {
-                    (&ws.val[0][0])[park_index(pos)] = (typename Emit::Store)Emit::make(job, z, true, flags);
+                    (&ws.val[0][0])[park_index(pos)] = (typename Emit::Store)Emit::make(job, z, inexact, flags);
                 } else if (MODE == kEmit) {
-                    const typename Emit::Val v = Emit::make(job, z, true, flags);
+                    const typename Emit::Val v = Emit::make(job, z, inexact, flags);
                     uint64_t bits = 0;
                     memcpy(&bits, &v, sizeof v);
                     ws.ev_s[ev][0] = bits;
@@ -1380,6 +1447,13 @@ __global__ void __launch_bounds__(256) k_np_choice_impulse(const NpJob *__restri
     np_results_out(done, results, results_host, n_jobs);
 }
 
+// tail_log_est on a list of raw draws, for the test that pins kTailEps (vkx_np_tail_log_est_dev).
+__global__ void __launch_bounds__(256) k_np_tail_log_est(const uint64_t *__restrict__ draws, long long n, double *__restrict__ est)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) est[i] = tail_log_est(draws[i]);
+}
+
 } // namespace
 
 static int np_tables(vkx_ctx *ctx, const NpTabs **out)
@@ -1784,6 +1858,19 @@ VKX_EXPORT int vkx_np_draw_batch_dev(vkx_ctx *ctx, const vkx_np_job *jobs, int n
     }
     for (int k = std::max(0, n_chunks - 2); k < n_chunks; k++) VKX_HIP(hipStreamWaitEvent(main_stream, placed[k], 0));
     for (hipEvent_t e : placed) (void)hipEventDestroy(e);      // destruction is deferred until the event has completed
+    return VKX_OK;
+}
+
+// What the fast tail pass of the integer kinds takes for -log(1 - u), u = (draw >> 11) * 2^-53, and the error bound it assumes.
+VKX_EXPORT int vkx_np_tail_log_est_dev(vkx_ctx *ctx, const uint64_t *draws, int64_t n, double *est, double *eps)
+{
+    VKX_REQUIRE(ctx && draws && est, "NULL argument");
+    VKX_REQUIRE(n >= 1 && n <= 0x7fffffffLL, "1 .. 2^31 - 1 draws");
+    if (eps) *eps = kTailEps;
+    vkx_device_guard guard(ctx);
+    VKX_TIMED(ctx, "k_np_tail_log_est");
+    k_np_tail_log_est<<<vkx_blocks((size_t)n, 256), 256, 0, ctx->stream>>>(draws, (long long)n, est);
+    VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
 
