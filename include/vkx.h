@@ -956,6 +956,25 @@ int vkx_region_label_deviate_dev(vkx_ctx *ctx, const double *quads_host, const i
 int vkx_region_label_planes_dev(vkx_ctx *ctx, const int32_t *boxes_host, int n_boxes, int h, int w, const uint8_t *active_mask,
                                 uint8_t *char_mask, float *char_height, uint8_t *box_mask);
 
+/* ---- PageTextRegionCroppingStep (pipeline/text_detection/page_text_region_cropping.py) ----------------------------------
+ * vkx_region_crop_select_dev replaces the two STRtree queries and the preserved-char filter of one attempt (:160-187), for
+ * every candidate window of a page at once.  Per window (up, down, left, right) -- an original_core_box, which may reach
+ * outside the page --: a centroid label (x, y, char_idx) is kept when left <= x <= right and up <= y <= down (closed bounds:
+ * a shapely box intersects a point on its edge); a deviate label is kept when it passes the same test and its char_idx is
+ * the char_idx of a kept centroid label of that window.  counts[window] = (kept centroid labels, kept deviate labels);
+ * row `window` of each index table holds the kept label indices in ascending order (the reference walks sorted(query(...)))
+ * in its first count entries, the rest of the row is unspecified.  Integer compares only.  Dense tables, no pitch.  One
+ * launch, no synchronisation.  While every char_idx is below 262 144 the call keeps nothing but the staged tables on the
+ * context; beyond that it reserves up to 64 MB of context scratch for bitmaps, kept until the context is destroyed.
+ * Refused (VKX_ERR_INVALID, nothing launched) for a NULL pointer (a table or an index table of
+ * zero labels may be NULL), n_windows outside 1 .. 4096, a label count outside 0 .. 2^24 - 1, a char_idx outside
+ * 0 .. 2^24 - 1, a box with down < up or right < left and outputs that overlap one another.
+ * windows_host: HOST int32 [n_windows][4]; centroid_host / deviate_host: HOST int32 [n][3]; counts: DEVICE int32
+ * [n_windows][2]; centroid_rows / deviate_rows: DEVICE int32 [n_windows][n_centroid] / [n_windows][n_deviate]. */
+int vkx_region_crop_select_dev(vkx_ctx *ctx, const int32_t *windows_host, int n_windows, const int32_t *centroid_host,
+                               int n_centroid, const int32_t *deviate_host, int n_deviate, int32_t *counts,
+                               int32_t *centroid_rows, int32_t *deviate_rows);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Wall time of the three pipeline callers of the path on a C4-shaped synthetic page (1024^2, 64 text lines, 384 char
 polygons): PageAssemblerStep.run, PageDistortionStep.run, PageResizingStep.run -- host arrays in, host arrays out -- and
-where the host time goes (cProfile, top cumulative entries).  Usage: tools/page_steps.py [size] [n_lines] > out.json"""
+where the host time goes (cProfile, top cumulative entries).  Usage: tools/page_steps.py [size] [n_lines] > out.json
+
+    tools/page_steps.py text_region_cropping [size] [out.json]
+
+runs one leg alone: PageTextRegionCroppingStep.run on a device-resident page (default 1024^2) whose label counts are those of
+the largest case of tests/golden/text_region_cropping.npz times the ratio of the page sides; the record (default
+profiles/text_region_cropping_kernels.json) holds the kernel time of k_region_crop_select and of k_crop_planes, the step's wall
+time, the wall time of the selection call alone and, beside them, the wall time of the numpy restatement of the selection
+(tests/text_region_cropping_restate.py) on the same tables and windows."""
 import cProfile
 import io
 import json
@@ -21,8 +29,9 @@ from vkit_amd.pipeline.text_detection.synthetic_page import synthetic_page_input
 from vkit_amd import _native as N
 from vkit_amd.pipeline import text_detection as T
 
-size = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-n_lines = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+LEG = len(sys.argv) > 1 and sys.argv[1] == 'text_region_cropping'
+size = int(sys.argv[1]) if len(sys.argv) > 1 and not LEG else 1024
+n_lines = int(sys.argv[2]) if len(sys.argv) > 2 and not LEG else 64
 ctx = N.default_ctx()
 step_input = _synthetic_page_input(seed=3, size=size, n_lines=n_lines)
 assembler = T.page_assembler_step_factory.create()
@@ -64,6 +73,85 @@ def top(fn, reps, n=14):
         pstats.Stats(pr, stream=buf).sort_stats(key).print_stats(n)
         res[key] = [l.strip().replace(ROOT + '/', '') for l in buf.getvalue().splitlines() if l.strip() and l.strip()[0].isdigit()][:n + 1]
     return res
+
+
+def text_region_cropping_leg(size, path):
+    import text_region_cropping_restate as R
+    from vkit_amd.element import Image, Mask, Point, ScoreMap
+    from vkit_amd.pipeline.text_detection import page_text_region_cropping as M
+    largest = max(R.load_golden(), key=lambda r: len(r['label_key']))
+    scale = size // max(largest['shape'])
+    n_chars = (int(largest['label_key'][:, 1].max()) + 1) * scale
+    rng = default_rng(11)
+    tags = (T.PageCharRegressionLabelTag.CENTROID, T.PageCharRegressionLabelTag.DEVIATE)
+    labels = []
+    for g in range(n_chars):
+        cy, cx = rng.uniform(8, size - 8, 2).tolist()
+        corners = [Point.create(y=cy + dy, x=cx + dx) for dy, dx in ((-6, -5), (-6, 5), (6, 5), (6, -5))]
+        for tag in (0, 1):
+            y, x = (cy, cx) if tag == 0 else (cy + rng.uniform(-4, 4), cx + rng.uniform(-3, 3))
+            labels.append(T.PageCharRegressionLabel(char_idx=g, tag=tags[tag], label_point_smooth_y=y, label_point_smooth_x=x,
+                                                    downsampled_label_point_y=round(y), downsampled_label_point_x=round(x),
+                                                    up_left=corners[0], up_right=corners[1], down_right=corners[2],
+                                                    down_left=corners[3]))
+    shape = (size, size)
+    planes = dict(page_image=rng.integers(0, 256, shape + (3,), dtype=np.uint8), char=rng.integers(0, 2, shape, dtype=np.uint8),
+                  height=rng.random(shape, dtype=np.float32) * 30, gaussian=rng.random(shape, dtype=np.float32),
+                  box=rng.integers(0, 2, shape, dtype=np.uint8))
+    dev = {k: ctx.to_device(v) for k, v in planes.items()}
+    config = dict(core_size=size * 3 // 8, pad_size=size // 16)
+    pages = 4
+    step = T.page_text_region_cropping_step_factory.create(config)
+    step_in = T.PageTextRegionCroppingStepInput(
+        page_cropping_step_output=T.PageCroppingStepOutput(cropped_pages=[None] * pages),
+        page_text_region_step_output=T.PageTextRegionStepOutput(
+            page_image=Image(mat=dev['page_image']), page_active_mask=Mask(mat=np.ones(shape, np.uint8)), page_char_polygons=[],
+            page_text_region_polygons=[], page_char_polygon_text_region_polygon_indices=[], shape_before_rotate=shape,
+            rotate_angle=0, debug=None),
+        page_text_region_label_step_output=T.PageTextRegionLabelStepOutput(
+            page_char_mask=Mask(mat=dev['char']), page_char_height_score_map=ScoreMap(mat=dev['height'], is_prob=False),
+            page_char_gaussian_score_map=ScoreMap(mat=dev['gaussian']), page_char_regression_labels=labels,
+            page_char_bounding_box_mask=Mask(mat=dev['box'])))
+    reps = 20
+    samples = len(step.run(step_in, default_rng(0)).cropped_page_text_regions)
+    dt, kernels = timed(lambda s: step.run(step_in, default_rng(s)), reps, 'step')
+    centroid = M.label_table([lb for lb in labels if lb.tag == tags[0]])
+    deviate = M.label_table([lb for lb in labels if lb.tag == tags[1]])
+    probe = default_rng(1)
+    windows = M.core_box_table([step._state(shape, shape, 0, probe) for _ in range(max(3, 2 * pages))])
+
+    def median_ms(fn):
+        fn()
+        each = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            each.append(time.perf_counter() - t0)
+        return round(sorted(each)[reps // 2] * 1e3, 4)
+
+    record = {
+        'page': f'{size}x{size}', 'chars': n_chars, 'centroid_labels': len(centroid), 'deviate_labels': len(deviate),
+        'candidate_windows': len(windows), 'samples': samples, 'config': config, 'runs': reps,
+        'kernel_ms_per_run': kernels,
+        'step_wall_ms': dict(PER_RUN['step'], mean_ms=round(dt * 1e3, 3)),
+        'label_table_build_wall_ms': median_ms(lambda: (M.label_table(labels[0::2]), M.label_table(labels[1::2]))),
+        'selection_call_wall_ms': median_ms(lambda: N.region_crop_select(windows, centroid, deviate, ctx=ctx)),
+        'numpy_selection_wall_ms': median_ms(lambda: R.select(windows, centroid, deviate)),
+        'note': 'selection_call_wall_ms is _native.region_crop_select alone (staging, launch, the three copies back, the '
+                'synchronisation); numpy_selection_wall_ms the restatement R.select on the same tables and windows; both are part of, '
+                'or stand for a part of, step_wall_ms, which also builds the label tables from the label objects '
+                '(label_table_build_wall_ms), crops and shifts the kept labels',
+    }
+    with open(path, 'w') as f:
+        json.dump(record, f, indent=1)
+        f.write('\n')
+    print(json.dumps(record, indent=1))
+
+
+if LEG:
+    text_region_cropping_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
+                             sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, 'profiles', 'text_region_cropping_kernels.json'))
+    sys.exit(0)
 
 
 out = {'page': f'{size}x{size}', 'text_lines': n_lines}

@@ -388,6 +388,8 @@ _SIGNATURES['vkx_char_heatmap_fresh'] = _SIGNATURES['vkx_char_heatmap_fresh_dev'
 _SIGNATURES['vkx_region_label_deviate_dev'] = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                                c_void_p]
 _SIGNATURES['vkx_region_label_planes_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+_SIGNATURES['vkx_region_crop_select_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                             c_void_p]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
@@ -2459,3 +2461,48 @@ def region_label_planes(boxes, active_mask, char_mask, char_height, box_mask):
                                             c_void_p(char_height.ptr), c_void_p(box_mask.ptr)))
     for p in (char_mask, char_height, box_mask):
         p.invalidate_host()
+
+
+# index tables up to this size travel whole with the counts (region_crop_select)
+REGION_CROP_WHOLE_ROWS_MAX = 1 << 20
+
+
+def region_crop_select(windows, centroid, deviate, ctx=None):
+    """The label selection of PageTextRegionCroppingStep for every candidate window at once (vkx_region_crop_select_dev):
+    ``windows`` int32 (n, 4) (up, down, left, right), the original_core_box of each candidate; ``centroid`` / ``deviate`` int32
+    (k, 3) (x, y, char_idx).  ONE launch and ONE Context.sync -> (counts int32 (n, 2), [kept centroid indices per window],
+    [kept deviate indices per window]), each index array int32 and ascending.  The prefixes that the counts say are valid are
+    all that is read.  A step's tables (a few windows, thousands of labels: at most REGION_CROP_WHOLE_ROWS_MAX bytes of
+    index tables) are queued behind the counts as one copy each and wait for the same synchronisation; larger tables wait for
+    the counts, then only their valid prefixes are queued and waited for with a second Context.sync."""
+    ctx = ctx or default_ctx()
+    windows = np.ascontiguousarray(np.asarray(windows, dtype=np.int32).reshape(-1, 4))
+    tables = [np.ascontiguousarray(np.asarray(t, dtype=np.int32).reshape(-1, 3)) for t in (centroid, deviate)]
+    n = len(windows)
+    counts_dev = ctx.dev_empty((max(n, 1), 2), np.int32)
+    rows_dev = [ctx.dev_empty((max(n * len(t), 1),), np.int32) for t in tables]
+    check(lib().vkx_region_crop_select_dev(ctx.handle, windows.ctypes.data, n,
+                                           tables[0].ctypes.data if len(tables[0]) else None, len(tables[0]),
+                                           tables[1].ctypes.data if len(tables[1]) else None, len(tables[1]),
+                                           c_void_p(counts_dev.ptr), c_void_p(rows_dev[0].ptr), c_void_p(rows_dev[1].ptr)))
+    counts = ctx.pinned_empty((n, 2), np.int32)
+    ctx.copy_out(counts_dev.ptr, counts)
+    if 4 * n * (len(tables[0]) + len(tables[1])) <= REGION_CROP_WHOLE_ROWS_MAX:
+        whole = [ctx.pinned_empty((n, len(t)), np.int32) for t in tables]
+        for host, dev in zip(whole, rows_dev):
+            if host.size:
+                ctx.copy_out(dev.ptr, host)
+        ctx.sync()
+        rows = [[np.array(host[i, :counts[i, t]]) for i in range(n)] for t, host in enumerate(whole)]
+        return np.array(counts), rows[0], rows[1]
+    ctx.sync()
+    starts = np.concatenate([[0], np.cumsum(counts.T.reshape(-1), dtype=np.int64)])      # table 0's windows, then table 1's
+    packed = ctx.pinned_empty((max(int(starts[-1]), 1),), np.int32)
+    for t, (table, dev) in enumerate(zip(tables, rows_dev)):
+        for i in range(n):
+            k = t * n + i
+            if starts[k + 1] > starts[k]:
+                ctx.copy_out(dev.ptr + 4 * i * len(table), packed[starts[k]:starts[k + 1]])
+    ctx.sync()
+    rows = [[np.array(packed[starts[t * n + i]:starts[t * n + i + 1]]) for i in range(n)] for t in range(2)]
+    return np.array(counts), rows[0], rows[1]

@@ -123,6 +123,8 @@ struct vkx_ctx {
     vkx_scratch heat_planes;                  // ... the max / min / count planes (int [3][h * w])
     size_t heat_clean_page = 0;               // ... the page size they hold their initial values for (0: none)
     vkx_scratch rl_deviate, rl_planes;        // text-region labels (region_label.hip): the staged inputs of the two launches
+    vkx_scratch rc_tables, rc_bitmap;         // text-region cropping (region_crop.hip): the staged tables; the preserved-char
+                                              // bitmaps of the workgroups when they do not fit LDS
     vkx_scratch glass_win;                    // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows
     bool pz_tabs_ready = false;

@@ -43,3 +43,12 @@ from .page_text_region_label import (  # noqa: F401
     Vector,
     page_text_region_label_step_factory,
 )
+# (its DownsampledLabel stays in the module: the name above is page_cropping's, as in the reference's package)
+from .page_text_region_cropping import (  # noqa: F401
+    CroppedPageTextRegion,
+    PageTextRegionCroppingStep,
+    PageTextRegionCroppingStepConfig,
+    PageTextRegionCroppingStepInput,
+    PageTextRegionCroppingStepOutput,
+    page_text_region_cropping_step_factory,
+)
