@@ -975,6 +975,63 @@ int vkx_region_crop_select_dev(vkx_ctx *ctx, const int32_t *windows_host, int n_
                                int n_centroid, const int32_t *deviate_host, int n_deviate, int32_t *counts,
                                int32_t *centroid_rows, int32_t *deviate_rows);
 
+/* ---- the pixel half of PageTextRegionStep (pipeline/text_detection/page_text_region.py) ---------------------------------
+ * Four batched entry points, each ONE launch for all text regions of a page and no synchronisation; their per-region records
+ * are HOST tables.  A record addresses its source planes by device pointer and row step (bytes from a row to the next, at
+ * least one row, unused with a single row: the pitch contract of this header), so a source may be a rectangle inside a
+ * page plane or a plane of its own; what a call writes is dense and lies at a byte offset of one packed buffer `dst` of
+ * `dst_bytes` bytes.  Refused (VKX_ERR_INVALID, nothing launched): a NULL pointer, a count outside 1 .. 4096 (0 .. 4096 for
+ * the stack), a side outside 1 .. 32767, a row step shorter than a row or negative, a destination outside `dst`,
+ * destinations that overlap one another and a source plane that overlaps `dst`.  A pair writes its image, its mask or
+ * both: a negative dst_image_off / dst_mask_off leaves that plane out, and its source pointer is then not read (the
+ * reference trims and resizes image and mask by separate calls, whose shapes can differ: Image.to_cropped_image takes
+ * `down or height - 1`); a pair that writes neither is refused.
+ *
+ * vkx_region_warp_dev: rotate.distort of TextRegionFlattener.build_flattened_text_regions (:603-608) and of
+ * FlattenedTextRegion.to_post_rotated_flattened_text_region (:148-153): per pair cv.warpAffine(src, m, dsize) of an image
+ * (uint8 x 3) and a mask (uint8) with the pair's own forward matrix, pixel for pixel vkx_warp_affine_u8_dev's.
+ * Of the warped plane the window of dst_h x dst_w at (up, left) is written: the trim to the rotated mask's external box
+ * (:617-628) is a second call on the boxes of vkx_region_extent_dev.  extract != 0: an image source pixel counts as 0 where
+ * the pair's source mask is 0 (Mask.extract_image, :589). */
+typedef struct vkx_region_warp_pair {
+    const uint8_t *src_image;           /* device uint8 [src_h][src_w][3] */
+    const uint8_t *src_mask;            /* device uint8 [src_h][src_w] */
+    int64_t src_image_step, src_mask_step;
+    int32_t src_h, src_w;
+    float m[6];                         /* the forward 2 x 3 matrix of RotateState, row-major */
+    int32_t up, left, dst_h, dst_w;     /* the window of the warped plane that is written */
+    int64_t dst_image_off, dst_mask_off;
+} vkx_region_warp_pair;
+int vkx_region_warp_dev(vkx_ctx *ctx, const vkx_region_warp_pair *pairs_host, int n_pairs, int extract, uint8_t *dst,
+                        size_t dst_bytes);
+/* vkx_region_extent_dev: Mask.to_external_box (element/mask.py:614-633) of n dense masks [h][w] packed in `masks` at
+ * offsets_host[i] with shapes_host[i] = (h, w): extents[i] = (up, down, left, right) of the pixels > 0, or -1 four times
+ * for a mask without one.  extents: DEVICE int32 [n][4]; the caller copies it back and synchronises once. */
+int vkx_region_extent_dev(vkx_ctx *ctx, const uint8_t *masks, size_t masks_bytes, const int64_t *offsets_host,
+                          const int32_t *shapes_host, int n_masks, int32_t *extents);
+/* vkx_region_resize_dev: FlattenedTextRegion.to_resized_flattened_text_region (:114-122): per pair the image as
+ * cv.resize(INTER_CUBIC) and the mask as cv.resize((mask > 0) * 255, INTER_CUBIC) > 0, pixel for pixel
+ * vkx_resize_cubic_u8_dev's. */
+typedef struct vkx_region_resize_pair {
+    const uint8_t *src_image;           /* device uint8 [src_h][src_w][3] */
+    const uint8_t *src_mask;            /* device uint8 [src_h][src_w] */
+    int64_t src_image_step, src_mask_step;
+    int32_t src_h, src_w, dst_h, dst_w;
+    int64_t dst_image_off, dst_mask_off;
+} vkx_region_resize_pair;
+int vkx_region_resize_dev(vkx_ctx *ctx, const vkx_region_resize_pair *pairs_host, int n_pairs, uint8_t *dst, size_t dst_bytes);
+/* vkx_region_stack_dev: build_background_image_for_stacking (:732-745) and the fills of stack_flattened_text_regions
+ * (:805-840) into fresh planes: page_image uint8 [h][w][3] and page_mask uint8 [h][w], dense, every pixel of both written
+ * once: where a region covers a pixel with mask > 0 the pixel of the LAST such region and mask 1, elsewhere channel
+ * (y + x) % 3 at 255, the others 0, and mask 0.  Regions are dense planes [h][w][3] / [h][w] with their box origin; a box
+ * outside the page and a region plane that overlaps a page plane are refused. */
+typedef struct vkx_region_stack_item {
+    const uint8_t *image, *mask;
+    int32_t h, w, up, left;
+} vkx_region_stack_item;
+int vkx_region_stack_dev(vkx_ctx *ctx, const vkx_region_stack_item *items_host, int n_items, uint8_t *page_image,
+                         uint8_t *page_mask, int h, int w);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

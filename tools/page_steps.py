@@ -9,7 +9,16 @@ runs one leg alone: PageTextRegionCroppingStep.run on a device-resident page (de
 the largest case of tests/golden/text_region_cropping.npz times the ratio of the page sides; the record (default
 profiles/text_region_cropping_kernels.json) holds the kernel time of k_region_crop_select and of k_crop_planes, the step's wall
 time, the wall time of the selection call alone and, beside them, the wall time of the numpy restatement of the selection
-(tests/text_region_cropping_restate.py) on the same tables and windows."""
+(tests/text_region_cropping_restate.py) on the same tables and windows.
+
+    tools/page_steps.py text_region_flatten [size] [out.json]
+
+runs the pixel half of PageTextRegionStep on a device-resident synthetic page (default 1024^2, 128 text-line-shaped regions) two
+ways: the batched path of csrc/region_flatten.hip (build_flattened_text_regions, resize_flattened_text_regions,
+post_rotate_flattened_text_regions, stack_flattened_text_regions) and the same work composed per region from the single-plane
+operators (Mask.extract_image, rotate.distort, the external box in numpy, to_cropped_image, to_resized_image / to_resized_mask,
+Box.fill_image / fill_mask).  The record (default profiles/text_region_flatten_kernels.json) holds, for each, the wall time, the
+time of every kernel and the dispatch counts per page."""
 import cProfile
 import io
 import json
@@ -29,7 +38,7 @@ from vkit_amd.pipeline.text_detection.synthetic_page import synthetic_page_input
 from vkit_amd import _native as N
 from vkit_amd.pipeline import text_detection as T
 
-LEG = len(sys.argv) > 1 and sys.argv[1] == 'text_region_cropping'
+LEG = len(sys.argv) > 1 and sys.argv[1] in ('text_region_cropping', 'text_region_flatten')
 size = int(sys.argv[1]) if len(sys.argv) > 1 and not LEG else 1024
 n_lines = int(sys.argv[2]) if len(sys.argv) > 2 and not LEG else 64
 ctx = N.default_ctx()
@@ -148,6 +157,102 @@ def text_region_cropping_leg(size, path):
     print(json.dumps(record, indent=1))
 
 
+def text_region_flatten_leg(size, path):
+    from vkit_amd.element import Box, Image, Mask
+    from vkit_amd.mechanism.distortion import rotate
+    from vkit_amd.pipeline.text_detection import page_text_region as F
+    rng = default_rng(17)
+    n_regions, reps = 128, 10
+    page = rng.integers(0, 256, (size, size, 3), dtype=np.uint8)
+    masks_host, angles, heights, post = [], [], [], []
+    for _ in range(n_regions):
+        bh, bw = int(rng.integers(16, 49)), int(rng.integers(60, min(400, size // 2) + 1))
+        up, left = int(rng.integers(0, size - bh + 1)), int(rng.integers(0, size - bw + 1))
+        mat = np.ones((bh, bw), np.uint8)
+        mat[:2], mat[-2:], mat[:, :3] = 0, 0, 0                      # the band around a dilated text line
+        masks_host.append((mat, Box(up=up, down=up + bh - 1, left=left, right=left + bw - 1)))
+        angles.append(int(rng.choice([*range(350, 360), *range(1, 11)])))
+        heights.append(int(rng.integers(32, 47)))                    # the sampled char height decides the resized height
+        post.append(int(rng.choice([0, 0, 0, 0, 180, 180, 90, 270])))
+    image = Image(mat=ctx.to_device(page))
+    masks = [Mask(mat=ctx.to_device(mat), box=box) for mat, box in masks_host]
+
+    def batched(_):
+        regions = F.TextRegionFlattener.build_flattened_text_regions(image, [None] * n_regions, masks, (), angles, None)
+        regions = F.resize_flattened_text_regions(regions, [(h, None) for h in heights])
+        regions = F.post_rotate_flattened_text_regions(regions, post)
+        out = F.stack_flattened_text_regions(0, 2, regions, F.ColumnPacker)
+        ctx.sync()
+        return out
+
+    def per_region(_):
+        regions = []
+        for mask, angle, height, post_angle in zip(masks, angles, heights, post):
+            result = rotate.distort({'angle': angle}, image=mask.extract_image(image), mask=mask)
+            np_mask = result.mask.mat > 0
+            rows, cols = np.nonzero(np_mask.any(axis=1))[0], np.nonzero(np_mask.any(axis=0))[0]
+            box = Box(up=int(rows[0]), down=int(rows[-1]), left=int(cols[0]), right=int(cols[-1]))
+            region_image = result.image.to_cropped_image(up=box.up, down=box.down, left=box.left, right=box.right)
+            region_mask = box.extract_mask(result.mask)
+            region_image = region_image.to_resized_image(resized_height=height)
+            region_mask = region_mask.to_resized_mask(resized_height=height)
+            if post_angle:
+                result = rotate.distort({'angle': post_angle}, image=region_image, mask=region_mask)
+                region_image, region_mask = result.image, result.mask
+            regions.append((region_image, region_mask))
+        width = max(r.width for r, _ in regions) + 4
+        height = sum(r.height + 4 for r, _ in regions)
+        stacked = Image(mat=ctx.to_device(F.build_background_image_for_stacking(height, width).mat))
+        active = Mask(mat=N.dev_zeros((height, width), np.uint8, ctx=ctx))
+        y = 0
+        for region_image, region_mask in regions:
+            box = Box(up=y + 2, down=y + 2 + region_image.height - 1, left=2, right=2 + region_image.width - 1)
+            box.fill_image(stacked, region_image, image_mask=region_mask)
+            box.fill_mask(active, 1, mask_mask=region_mask)
+            y += region_image.height + 4
+        ctx.sync()
+        return stacked, active
+
+    def measure(fn):
+        fn(0)
+        ctx.sync()
+        ctx.set_timing(True)
+        ctx.reset_timings()
+        each = []
+        for k in range(reps):
+            t0 = time.perf_counter()
+            fn(k + 1)
+            each.append(time.perf_counter() - t0)
+        timings = ctx.timings()
+        ctx.set_timing(False)
+        each.sort()
+        return {'wall_ms': {'median_ms': round(each[reps // 2] * 1e3, 3), 'min_ms': round(each[0] * 1e3, 3),
+                            'max_ms': round(each[-1] * 1e3, 3)},
+                'kernel_ms_per_page': {name: round(ms / reps, 4) for name, (ms, _cnt) in sorted(timings.items())},
+                'dispatches_per_page': {name: round(cnt / reps, 2) for name, (_ms, cnt) in sorted(timings.items())},
+                'dispatches_per_page_total': round(sum(cnt for _ms, cnt in timings.values()) / reps, 2)}
+
+    with N.resident(True):
+        new_image, new_active = batched(0)[:2]
+        old_image, old_active = per_region(0)
+        agree = bool(np.array_equal(new_image.mat, old_image.mat) and np.array_equal(new_active.mat, old_active.mat))
+        record = {'page': f'{size}x{size}', 'regions': n_regions, 'runs': reps, 'stacked_page': list(new_image.shape),
+                  'paths_agree': agree, 'batched': measure(batched), 'per_region': measure(per_region),
+                  'note': 'both paths start from a device-resident page and device-resident masks, leave the stacked page and its '
+                          'active mask on the device and end with one Context.sync; wall_ms includes the host work of each path '
+                          '(records and states for the batched one, per-region element objects, the download of every rotated mask '
+                          'for its external box and the host crops for the other); kernel times are measured with event pairs, '
+                          'which add a few microseconds a dispatch to the wall time of both'}
+    with open(path, 'w') as f:
+        json.dump(record, f, indent=1)
+        f.write('\n')
+    print(json.dumps(record, indent=1))
+
+
+if LEG and sys.argv[1] == 'text_region_flatten':
+    text_region_flatten_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
+                            sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, 'profiles', 'text_region_flatten_kernels.json'))
+    sys.exit(0)
 if LEG:
     text_region_cropping_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
                              sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, 'profiles', 'text_region_cropping_kernels.json'))

@@ -390,6 +390,10 @@ _SIGNATURES['vkx_region_label_deviate_dev'] = [c_void_p, c_void_p, c_void_p, c_i
 _SIGNATURES['vkx_region_label_planes_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
 _SIGNATURES['vkx_region_crop_select_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                              c_void_p]
+_SIGNATURES['vkx_region_warp_dev'] = [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t]
+_SIGNATURES['vkx_region_extent_dev'] = [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_void_p]
+_SIGNATURES['vkx_region_resize_dev'] = [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_size_t]
+_SIGNATURES['vkx_region_stack_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
@@ -2506,3 +2510,79 @@ def region_crop_select(windows, centroid, deviate, ctx=None):
     ctx.sync()
     rows = [[np.array(packed[starts[t * n + i]:starts[t * n + i + 1]]) for i in range(n)] for t in range(2)]
     return np.array(counts), rows[0], rows[1]
+
+
+# --------------------------------------------------------------------------------------------------------------
+# the pixel half of PageTextRegionStep (csrc/region_flatten.hip): the host tables of include/vkx.h as numpy records
+# --------------------------------------------------------------------------------------------------------------
+REGION_WARP_PAIR_DTYPE = np.dtype([('src_image', np.uint64), ('src_mask', np.uint64), ('src_image_step', np.int64),
+                                   ('src_mask_step', np.int64), ('src_h', np.int32), ('src_w', np.int32), ('m', np.float32, (6,)),
+                                   ('up', np.int32), ('left', np.int32), ('dst_h', np.int32), ('dst_w', np.int32),
+                                   ('dst_image_off', np.int64), ('dst_mask_off', np.int64)], align=True)
+REGION_RESIZE_PAIR_DTYPE = np.dtype([('src_image', np.uint64), ('src_mask', np.uint64), ('src_image_step', np.int64),
+                                     ('src_mask_step', np.int64), ('src_h', np.int32), ('src_w', np.int32), ('dst_h', np.int32),
+                                     ('dst_w', np.int32), ('dst_image_off', np.int64), ('dst_mask_off', np.int64)], align=True)
+REGION_STACK_ITEM_DTYPE = np.dtype([('image', np.uint64), ('mask', np.uint64), ('h', np.int32), ('w', np.int32), ('up', np.int32),
+                                    ('left', np.int32)], align=True)
+assert (REGION_WARP_PAIR_DTYPE.itemsize, REGION_RESIZE_PAIR_DTYPE.itemsize, REGION_STACK_ITEM_DTYPE.itemsize) == (96, 64, 32)
+
+
+class DevView(DevArray):
+    """A C-contiguous block inside another DevArray (the packed result of a batched call): keeps its parent alive and
+    returns nothing to the pool itself."""
+
+    __slots__ = ('base',)
+
+    def __init__(self, base, offset, shape, dtype=np.uint8):
+        super().__init__(base.ctx, base.ptr + int(offset), shape, dtype, 0)
+        self.base = base
+        assert 0 <= offset and offset + self.nbytes <= base.nbytes
+
+
+def _records(table, dtype):
+    table = np.ascontiguousarray(table)
+    if table.dtype != dtype or table.ndim != 1:
+        raise TypeError(f'expected a 1-D table of {dtype}')
+    return table
+
+
+def region_warp(pairs, extract, dst):
+    """vkx_region_warp_dev: ``pairs`` REGION_WARP_PAIR_DTYPE records, ``dst`` the packed uint8 DevArray their windows are
+    written into.  ONE launch, asynchronous."""
+    pairs = _records(pairs, REGION_WARP_PAIR_DTYPE)
+    check(lib().vkx_region_warp_dev(dst.ctx.handle, pairs.ctypes.data, len(pairs), int(bool(extract)), c_void_p(dst.ptr),
+                                    dst.nbytes))
+    dst.invalidate_host()
+
+
+def region_extent(masks, offsets, shapes):
+    """vkx_region_extent_dev on the dense masks packed in the uint8 DevArray ``masks`` -> DevArray int32 (n, 4)
+    (up, down, left, right), -1 for an empty mask.  ONE launch, asynchronous: the caller copies back and synchronises."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    shapes = np.ascontiguousarray(shapes, dtype=np.int32).reshape(-1, 2)
+    if len(offsets) != len(shapes):
+        raise ValueError('one offset and one shape a mask')
+    out = masks.ctx.dev_empty((max(len(offsets), 1), 4), np.int32)
+    check(lib().vkx_region_extent_dev(masks.ctx.handle, c_void_p(masks.ptr), masks.nbytes, offsets.ctypes.data, shapes.ctypes.data,
+                                      len(offsets), c_void_p(out.ptr)))
+    return out
+
+
+def region_resize(pairs, dst):
+    """vkx_region_resize_dev: ``pairs`` REGION_RESIZE_PAIR_DTYPE records into the packed uint8 DevArray ``dst``.  ONE launch,
+    asynchronous."""
+    pairs = _records(pairs, REGION_RESIZE_PAIR_DTYPE)
+    check(lib().vkx_region_resize_dev(dst.ctx.handle, pairs.ctypes.data, len(pairs), c_void_p(dst.ptr), dst.nbytes))
+    dst.invalidate_host()
+
+
+def region_stack(items, shape, ctx=None):
+    """vkx_region_stack_dev: the striped page of ``shape`` with the regions of ``items`` (REGION_STACK_ITEM_DTYPE) under
+    their masks -> (image DevArray (h, w, 3), active mask DevArray (h, w)), both written whole.  ONE launch, asynchronous."""
+    ctx = ctx or default_ctx()
+    items = _records(items, REGION_STACK_ITEM_DTYPE)
+    h, w = int(shape[0]), int(shape[1])
+    image, mask = ctx.dev_empty((h, w, 3), np.uint8), ctx.dev_empty((h, w), np.uint8)
+    check(lib().vkx_region_stack_dev(ctx.handle, items.ctypes.data if len(items) else None, len(items), c_void_p(image.ptr),
+                                     c_void_p(mask.ptr), h, w))
+    return image, mask

@@ -2,6 +2,7 @@
 // One lane per destination pixel, 64 consecutive pixels of a row per wavefront; the arithmetic is
 // the integer fixed-point pipeline of OpenCV's imgwarp.cpp (see oracle/vkx_oracle.c for citations).
 #include "vkx_internal.h"
+#include "vkx_warp.h"
 
 namespace {
 
@@ -21,44 +22,8 @@ struct CoordMap {      // cv.remap: coordinates come from two float planes
     }
 };
 
-struct CoordAffine {   // warpAffine: inverse matrix, AB_BITS = 10 fixed point
-    // a rotated / sheared source footprint: 64 destination pixels of ONE row reach a slanted strip of the source (6 degrees:
-    // 8 source rows, ~32 cache lines per tap-load instruction); a wavefront therefore takes 16 columns x 4 rows per instruction
-    // (5 - 6 lines), four wavefronts side by side so that their 48-byte row segments complete cache lines on the way out
-    static constexpr bool kTile2D = true;
-    double m[6];
-    // adelta[x] / bdelta[x] of cv::warpAffine depend on the column only: a lane that walks several rows of its column
-    // computes them once
-    struct Column { int adelta, bdelta; };
-    __device__ __forceinline__ Column column(int x) const
-    {
-        return Column{vkd::cv_round(m[0] * x * 1024), vkd::cv_round(m[3] * x * 1024)};
-    }
-    // X0 / Y0 of cv::warpAffine depend on the row only: lane r of the wavefront computes those of row y0 + r (one double
-    // evaluation per wavefront instead of one per row), every lane reads them back with v_readlane
-    struct Rows { int X0, Y0; };
-    __device__ __forceinline__ Rows rows(int y0, int lane) const
-    {
-        const int y = y0 + (lane & 15);
-        return Rows{vkd::cv_round((m[1] * y + m[2]) * 1024) + 16, vkd::cv_round((m[4] * y + m[5]) * 1024) + 16};
-    }
-    // `row`: the lane's row inside the tile (0 .. 15), per lane: the row terms come from the lane that computed them
-    __device__ __forceinline__ void at(const Column &c, const Rows &r, int row, int, int, int &X, int &Y) const
-    {
-        X = (__builtin_amdgcn_ds_bpermute(row << 2, r.X0) + c.adelta) >> 5;
-        Y = (__builtin_amdgcn_ds_bpermute(row << 2, r.Y0) + c.bdelta) >> 5;
-    }
-    __device__ __forceinline__ void operator()(int x, int y, int &X, int &Y) const
-    {
-        const int adelta = vkd::cv_round(m[0] * x * 1024);
-        const int bdelta = vkd::cv_round(m[3] * x * 1024);
-        const int X0 = vkd::cv_round((m[1] * y + m[2]) * 1024) + 16;
-        const int Y0 = vkd::cv_round((m[4] * y + m[5]) * 1024) + 16;
-        X = (X0 + adelta) >> 5;
-        Y = (Y0 + bdelta) >> 5;
-    }
-};
-
+using vkd::CoordAffine;       // vkx_warp.h: shared with the batched region warp (region_flatten.hip)
+using vkd::make_affine;
 using vkd::CoordPerspective;   // vkx_internal.h: shared with the char-mask raster (char_mask.hip)
 
 typedef unsigned long long u64_u1 __attribute__((aligned(1)));
@@ -310,24 +275,6 @@ int launch_f32(vkx_ctx *ctx, const float *src, int sh, int sw, ptrdiff_t sstride
     { VKX_TIMED(ctx, "k_sample_f32"); k_sample_f32<Coord><<<grid, block, 0, ctx->stream>>>(src, sh, sw, sstride, dst, dh, dw, dstride, coord); }
     VKX_LAUNCH_CHECK();
     return VKX_OK;
-}
-
-// cv::warpAffine's in-place inversion of the forward 2x3 matrix (double).
-CoordAffine make_affine(const double Mf[6])
-{
-    CoordAffine c;
-    double M[6];
-    for (int i = 0; i < 6; i++) M[i] = Mf[i];
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0 ? 1. / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D;
-    M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5];
-    const double b2 = -M[3] * M[2] - M[4] * M[5];
-    M[2] = b1; M[5] = b2;
-    for (int i = 0; i < 6; i++) c.m[i] = M[i];
-    return c;
 }
 
 // cv::invert of a 3x3 double matrix (cofactors times 1/det; zeros when singular) and the block width of

@@ -8,6 +8,7 @@
 // 4 x 4 taps per channel, int32 accumulation with the (sum + 2^21) >> 22 rounding for uint8, float32 left-to-right
 // sums for float32.  Bound by HBM/L2 reads of the source (each source row is reused by ~4/scale destination rows).
 #include "vkx_internal.h"
+#include "vkx_resize_cubic.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -19,49 +20,11 @@
 
 namespace {
 
-// cvRound of a host float: ties to even, "integer indefinite" (INT_MIN) for NaN and out-of-range values -- a LANCZOS4
-// coefficient can be NaN (fraction rounding up to exactly 1.0f makes one tap 0 / 0), and saturate_cast<short> of that
-// is -32768 in cv2, not whatever a plain (int) cast of NaN yields.
-int cv_round_host(float v)
-{
-    if (!(v >= -2147483648.f && v < 2147483648.f)) return INT_MIN;
-    return (int)std::nearbyint((double)v);
-}
-
-struct AxisTable {
-    std::vector<int> ofs;      // floor of the source coordinate
-    std::vector<float> coef;   // [n][4]
-    std::vector<short> icoef;  // [n][4], cvRound(coef * 2048)
-};
-
-void cubic_coeffs(float x, float c[4])
-{
-    const float A = -0.75f;
-    c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
-    c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
-    c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
-    c[3] = 1.f - c[0] - c[1] - c[2];
-}
-
-void build_axis(int ssize, int dsize, AxisTable *t)
-{
-    t->ofs.resize(dsize); t->coef.resize((size_t)dsize * 4); t->icoef.resize((size_t)dsize * 4);
-    const double inv_scale = (double)dsize / ssize;
-    const double scale = 1. / inv_scale;
-    for (int d = 0; d < dsize; d++) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        const int s0 = (int)std::floor(f);
-        f -= s0;
-        t->ofs[d] = s0;
-        cubic_coeffs(f, &t->coef[(size_t)d * 4]);
-        for (int k = 0; k < 4; k++) {
-            const int r = cv_round_host(t->coef[(size_t)d * 4 + k] * 2048.f);
-            t->icoef[(size_t)d * 4 + k] = (short)(r < -32768 ? -32768 : (r > 32767 ? 32767 : r));
-        }
-    }
-}
-
-__device__ __forceinline__ int clip_index(int x, int n) { return x < 0 ? 0 : (x >= n ? n - 1 : x); }
+using vkd::cv_round_host;
+using vkd::AxisTable;
+using vkd::cubic_coeffs;
+using vkd::build_axis;
+using vkd::clip_index;
 
 template <int CN>
 __global__ void __launch_bounds__(256) k_resize_cubic_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
@@ -72,31 +35,8 @@ __global__ void __launch_bounds__(256) k_resize_cubic_u8(const uint8_t *__restri
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= dw || dy >= dh) return;
-    const int x0 = xofs[dx], y0 = yofs[dy];
-    int sx[4], ax[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) { sx[j] = clip_index(x0 - 1 + j, sw) * CN; ax[j] = xa[dx * 4 + j]; }
-    unsigned acc[CN];
-#pragma unroll
-    for (int c = 0; c < CN; c++) acc[c] = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint8_t *row = src + (ptrdiff_t)clip_index(y0 - 1 + k, sh) * sstride;
-        const int b = yb[dy * 4 + k];
-#pragma unroll
-        for (int c = 0; c < CN; c++) {
-            unsigned hsum = 0; // int32 with wrap, like the int accumulators of the reference implementation
-#pragma unroll
-            for (int j = 0; j < 4; j++) hsum += (unsigned)((int)row[sx[j] + c] * ax[j]);
-            acc[c] += (unsigned)__mul24((int)hsum, b);      // |hsum| < 2^20: same low 32 bits as the 32-bit product
-        }
-    }
-    uint8_t *out = dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN;
-#pragma unroll
-    for (int c = 0; c < CN; c++) {
-        const int r = ((int)(acc[c] + (1u << 21))) >> 22;
-        out[c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-    }
+    vkd::cubic_pixel_u8<CN>([&](int y, int b) { return (int)src[(ptrdiff_t)y * sstride + b]; }, sh, sw, xofs[dx], yofs[dy],
+                            xa + dx * 4, yb + dy * 4, dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN);
 }
 
 __global__ void __launch_bounds__(256) k_resize_cubic_f32(const float *__restrict__ src, int sh, int sw, ptrdiff_t sstride,

@@ -125,6 +125,7 @@ struct vkx_ctx {
     vkx_scratch rl_deviate, rl_planes;        // text-region labels (region_label.hip): the staged inputs of the two launches
     vkx_scratch rc_tables, rc_bitmap;         // text-region cropping (region_crop.hip): the staged tables; the preserved-char
                                               // bitmaps of the workgroups when they do not fit LDS
+    vkx_scratch rf_tables;                    // text-region flattening (region_flatten.hip): the staged records and tap tables of the last call
     vkx_scratch glass_win;                    // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows
     bool pz_tabs_ready = false;
@@ -310,9 +311,10 @@ __device__ __forceinline__ int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 2
 // the quirk entry included, so the table never needs to be materialised.
 // PTR: `const uint8_t *` or the same in an explicit address space (a kernel that holds its planes as global-address-space
 // pointers keeps FLAT instructions out of its code that way).
-template <int CN, typename PTR = const uint8_t *>
-__device__ __forceinline__ void sample_u8(PTR src, int sh, int sw, ptrdiff_t sstride, int X, int Y, uint8_t *out)
+template <int CN, class Tap>
+__device__ __forceinline__ void sample_taps_u8(Tap tap, int sh, int sw, int X, int Y, uint8_t *out)
 {
+    // tap(y, x, k): channel k of source pixel (y, x), asked for pixels inside the source only
     const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
     const int fx = X & 31, fy = Y & 31;
     if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) {
@@ -321,17 +323,21 @@ __device__ __forceinline__ void sample_u8(PTR src, int sh, int sw, ptrdiff_t sst
         return;
     }
     const bool x0 = sx >= 0, x1 = sx + 1 < sw, y0 = sy >= 0, y1 = sy + 1 < sh;
-    const PTR r0 = src + (ptrdiff_t)sy * sstride + (ptrdiff_t)sx * CN;
-    const PTR r1 = r0 + sstride;
     const int w00 = (32 - fy) * (32 - fx), w01 = (32 - fy) * fx, w10 = fy * (32 - fx), w11 = fy * fx;
 #pragma unroll
     for (int k = 0; k < CN; k++) {
-        const int v0 = (x0 && y0) ? r0[k] : 0;
-        const int v1 = (x1 && y0) ? r0[CN + k] : 0;
-        const int v2 = (x0 && y1) ? r1[k] : 0;
-        const int v3 = (x1 && y1) ? r1[CN + k] : 0;
+        const int v0 = (x0 && y0) ? tap(sy, sx, k) : 0;
+        const int v1 = (x1 && y0) ? tap(sy, sx + 1, k) : 0;
+        const int v2 = (x0 && y1) ? tap(sy + 1, sx, k) : 0;
+        const int v3 = (x1 && y1) ? tap(sy + 1, sx + 1, k) : 0;
         out[k] = (uint8_t)((v0 * w00 + v1 * w01 + v2 * w10 + v3 * w11 + 512) >> 10);
     }
+}
+// ... on a plane in memory.  The batched region warp (region_flatten.hip) reads its taps through a mask instead.
+template <int CN, typename PTR = const uint8_t *>
+__device__ __forceinline__ void sample_u8(PTR src, int sh, int sw, ptrdiff_t sstride, int X, int Y, uint8_t *out)
+{
+    sample_taps_u8<CN>([&](int y, int x, int k) { return (int)src[(ptrdiff_t)y * sstride + (ptrdiff_t)x * CN + k]; }, sh, sw, X, Y, out);
 }
 
 template <typename PTR = const float *>

@@ -156,6 +156,30 @@ class Mask(LazyMat, Shapable):
         assert self.box
         return attrs.evolve(self, box=None)
 
+    def to_external_box(self):
+        """The box of the active pixels in mask coordinates (reference mask.py:614-633); a device-resident mask is scanned
+        where it is (vkx_region_extent_dev: one launch, four integers back)."""
+        if self.on_device:
+            from vkit_amd import _native
+            arr = self.arr
+            extent_dev = _native.region_extent(arr, [0], [arr.shape])
+            extent = arr.ctx.pinned_empty((1, 4), np.int32)
+            arr.ctx.copy_out(extent_dev.ptr, extent)
+            arr.ctx.sync()
+            up, down, left, right = (int(v) for v in extent[0])
+            if up < 0:
+                raise RuntimeError('to_external_box: empty np_mask.')
+            return Box(up=up, down=down, left=left, right=right)
+        np_mask = self.np_mask
+        np_vert_nonzero = np.nonzero(np.amax(np_mask, axis=1))[0]
+        if len(np_vert_nonzero) == 0:
+            raise RuntimeError('to_external_box: empty np_mask.')
+        np_hori_nonzero = np.nonzero(np.amax(np_mask, axis=0))[0]
+        if len(np_hori_nonzero) == 0:
+            raise RuntimeError('to_external_box: empty np_mask.')
+        return Box(up=int(np_vert_nonzero[0]), down=int(np_vert_nonzero[-1]), left=int(np_hori_nonzero[0]),
+                   right=int(np_hori_nonzero[-1]))
+
     def to_score_map(self):
         return ScoreMap(mat=self.np_mask.astype(np.float32), box=self.box)
 

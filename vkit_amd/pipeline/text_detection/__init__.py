@@ -32,7 +32,16 @@ from .page_cropping import (  # noqa: F401
     PageCroppingStepOutput,
     page_cropping_step_factory,
 )
-from .page_text_region import PageTextRegionStepOutput  # noqa: F401
+from .page_text_region import (  # noqa: F401
+    ColumnPacker,
+    FlattenedTextRegion,
+    PageTextRegionStepOutput,
+    TextRegionFlattener,
+    build_background_image_for_stacking,
+    post_rotate_flattened_text_regions,
+    resize_flattened_text_regions,
+    stack_flattened_text_regions,
+)
 from .page_text_region_label import (  # noqa: F401
     PageCharRegressionLabel,
     PageCharRegressionLabelTag,

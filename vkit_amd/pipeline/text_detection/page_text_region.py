@@ -1,11 +1,30 @@
-"""The output of the reference's PageTextRegionStep (vkit/pipeline/text_detection/page_text_region.py:177-186), the input of
-PageTextRegionLabelStep.  Data only: the step that produces it (shapely, STRtree, rectpack) is outside the accelerated path,
-so its output enters here as a plain container, as the inputs of page_assembler.py do."""
-from typing import Any, Optional, Sequence, Tuple
+"""The pixel half of the reference's PageTextRegionStep (vkit/pipeline/text_detection/page_text_region.py) and the step's
+output container.
+
+``PageTextRegionStepOutput`` (:177-186) is the input of PageTextRegionLabelStep and PageTextRegionCroppingStep.  The step as
+a whole needs shapely, rectpack, pyclipper and cv.findContours and stays outside the accelerated path; what is here is
+everything of it that is pixel work, batched over all text regions of a page (csrc/region_flatten.hip):
+
+* ``TextRegionFlattener.build_flattened_text_regions`` (:560-656): cut, rotate and trim every region -- three launches and
+  one synchronisation (the read of the rotated masks' extents) whatever the number of regions;
+* ``resize_flattened_text_regions`` / ``post_rotate_flattened_text_regions``, the batched forms of
+  ``FlattenedTextRegion.to_resized_flattened_text_region`` and ``.to_post_rotated_flattened_text_region`` (:109-166): one
+  launch each, no synchronisation;
+* ``build_background_image_for_stacking`` and ``stack_flattened_text_regions`` (:732-856): one launch, no synchronisation.
+
+The polygon geometry that decides the masks and the angles is the caller's (the host's).  Results are device resident inside
+``_native.resident(True)`` or when an input was; otherwise they come back as numpy arrays, by one copy a call.
+"""
+import math
+import statistics
+from typing import Any, List, Optional, Sequence, Tuple
 
 import attrs
+import numpy as np
 
-from vkit_amd.element import Image, Mask, Polygon
+from vkit_amd import _native
+from vkit_amd.element import Box, Image, Mask, Polygon
+from vkit_amd.mechanism.distortion.geometric.affine import RotateConfig, RotateState, rotate
 
 
 @attrs.define
@@ -18,3 +37,441 @@ class PageTextRegionStepOutput:
     shape_before_rotate: Tuple[int, int]
     rotate_angle: int
     debug: Optional[Any]
+
+
+_UNSET = object()
+
+
+@attrs.define
+class FlattenedTextRegion:
+    is_typical: bool
+    text_region_polygon: Polygon
+    bounding_extended_text_region_mask: Mask
+    flattening_rotate_angle: int
+    shape_before_trim: Tuple[int, int]
+    rotated_trimmed_box: Box
+    shape_before_resize: Tuple[int, int]
+    post_rotate_angle: int
+    flattened_image: Image
+    flattened_mask: Mask
+    flattened_char_polygons: Optional[Sequence[Polygon]]
+    # the reference's field ``text_region_image``: ``bounding_extended_text_region_mask.extract_image(page image)``, made on
+    # first access (the flattening itself reads the page under the mask inside its warp kernel)
+    _text_region_image: Any = attrs.field(default=_UNSET, alias='text_region_image', repr=False)
+    _page_image: Optional[Image] = attrs.field(default=None, alias='page_image', repr=False, eq=False)
+
+    @property
+    def text_region_image(self) -> Image:
+        if self._text_region_image is _UNSET:
+            assert self._page_image is not None
+            self._text_region_image = self.bounding_extended_text_region_mask.extract_image(self._page_image)
+        return self._text_region_image
+
+    @property
+    def shape(self):
+        return self.flattened_image.shape
+
+    @property
+    def height(self):
+        return self.flattened_image.height
+
+    @property
+    def width(self):
+        return self.flattened_image.width
+
+    @property
+    def area(self):
+        return self.flattened_image.area
+
+    def get_char_height_meidan(self):
+        assert self.flattened_char_polygons
+        return statistics.median(
+            char_polygon.get_rectangular_height() for char_polygon in self.flattened_char_polygons)
+
+    def to_resized_flattened_text_region(self, resized_height: Optional[int] = None, resized_width: Optional[int] = None):
+        return resize_flattened_text_regions([self], [(resized_height, resized_width)])[0]
+
+    def to_post_rotated_flattened_text_region(self, post_rotate_angle: int):
+        assert self.post_rotate_angle == 0
+        return _rotate_flattened_text_regions([self], [post_rotate_angle])[0]
+
+
+# ---- planes of a batched call: where they come from, where they go -------------------------------------------------
+class _Sources:
+    """The source planes of one batched call as device pointers: device arrays are used where they are, host arrays are
+    packed and uploaded by one copy."""
+
+    def __init__(self, arrays):
+        owners = [a.ctx for a in arrays if isinstance(a, _native.DevArray)]
+        self.ctx = owners[0] if owners else _native.default_ctx()
+        for ctx in owners:
+            if ctx is not self.ctx:
+                ctx.sync()
+        self.resident = _native.resident_mode() or bool(owners)
+        self.ptr = [0] * len(arrays)
+        host = [(k, np.ascontiguousarray(a)) for k, a in enumerate(arrays) if not isinstance(a, _native.DevArray)]
+        offsets, total = _layout([a.nbytes for _, a in host])
+        self.keep = [a for a in arrays if isinstance(a, _native.DevArray)]
+        if host:
+            packed = np.empty(total, np.uint8)
+            for (_, a), off in zip(host, offsets):
+                packed[off:off + a.nbytes] = a.reshape(-1).view(np.uint8)
+            block = self.ctx.to_device(packed)
+            self.keep.append(block)
+            for (k, _), off in zip(host, offsets):
+                self.ptr[k] = block.ptr + off
+        for k, a in enumerate(arrays):
+            if isinstance(a, _native.DevArray):
+                self.ptr[k] = a.ptr
+
+
+def _layout(sizes):
+    offsets, total = [], 0
+    for size in sizes:
+        offsets.append(total)
+        total += (int(size) + 255) & ~255
+    return offsets, max(total, 256)
+
+
+class _Packed:
+    """The packed destination of one batched call and the planes cut out of it (device views, or numpy views of its one
+    download)."""
+
+    def __init__(self, ctx, shapes, resident):
+        self.shapes = [tuple(int(v) for v in s) for s in shapes]
+        self.offsets, total = _layout([math.prod(s) for s in self.shapes])
+        self.dev = ctx.dev_empty((total,), np.uint8)
+        self.resident = resident
+        self._host = None
+
+    def plane(self, k):
+        off, shape = self.offsets[k], self.shapes[k]
+        if self.resident:
+            return _native.DevView(self.dev, off, shape)
+        if self._host is None:
+            self._host = np.array(self.dev.host())
+        return self._host[off:off + math.prod(shape)].reshape(shape)
+
+
+def _arr(element):
+    arr = element.arr
+    if np.dtype(arr.dtype) != np.uint8:
+        raise TypeError('uint8 planes only')
+    return arr
+
+
+def _check_image(arr):
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError('the pixel half of PageTextRegionStep takes RGB images (height, width, 3)')
+
+
+def _rotate_state(angle, shape):
+    config = RotateConfig(angle=angle)
+    return config, RotateState(config, shape, None)
+
+
+def _rotate_polygons(config, shape, polygons):
+    """the polygons of rotate.distort on the host (the existing affine_polygons path, clipped to the result shape)"""
+    return rotate.distort(config, shapable_or_shape=shape, polygons=polygons).polygons
+
+
+# ---- TextRegionFlattener -----------------------------------------------------------------------------------------
+class TextRegionFlattener:
+    """``build_flattened_text_regions`` of the reference's class (:560-656).  The geometric methods that lead to its
+    arguments (polygon dilation, minimum-area rectangles, the KD-tree of the main angles, the mask algebra of
+    ``get_bounding_extended_text_region_masks``) are the caller's."""
+
+    @classmethod
+    def build_flattened_text_regions(cls, image: Image, text_region_polygons: Sequence[Polygon],
+                                     bounding_extended_text_region_masks: Sequence[Mask], typical_indices: Sequence[int],
+                                     flattening_rotate_angles: Sequence[int],
+                                     grouped_char_polygons: Optional[Sequence[Sequence[Polygon]]]):
+        typical_indices_set = set(typical_indices)
+        # (the reference zips the three sequences: the shortest decides)
+        n = min(len(text_region_polygons), len(bounding_extended_text_region_masks), len(flattening_rotate_angles))
+        if n == 0:
+            return []
+        page = _arr(image)
+        _check_image(page)
+        masks = list(bounding_extended_text_region_masks[:n])
+        src = _Sources([page] + [_arr(m) for m in masks])
+        ctx = src.ctx
+        page_h, page_w = page.shape[:2]
+
+        states, boxes = [], []
+        for mask, angle in zip(masks, flattening_rotate_angles):
+            box = mask.box
+            assert box
+            assert 0 <= box.up and box.down < page_h and 0 <= box.left and box.right < page_w
+            boxes.append(box)
+            states.append(_rotate_state(angle, box.shape))
+
+        # launch 1: the rotated masks, whole; launch 2: their extents; the one synchronisation: the extents on the host
+        full = _Packed(ctx, [(s.dsize[1], s.dsize[0]) for _, s in states], True)
+        pairs = np.zeros(n, _native.REGION_WARP_PAIR_DTYPE)
+        for k, (box, (_, state)) in enumerate(zip(boxes, states)):
+            p = pairs[k]
+            p['src_image'] = src.ptr[0] + (box.up * page_w + box.left) * 3
+            p['src_image_step'] = page_w * 3
+            p['src_mask'], p['src_mask_step'] = src.ptr[1 + k], box.width
+            p['src_h'], p['src_w'] = box.height, box.width
+            p['m'] = state.trans_mat.reshape(6)
+            p['dst_h'], p['dst_w'] = full.shapes[k]
+            p['dst_image_off'], p['dst_mask_off'] = -1, full.offsets[k]
+        _native.region_warp(pairs, True, full.dev)
+        extents_dev = _native.region_extent(full.dev, full.offsets, full.shapes)
+        extents = ctx.pinned_empty((n, 4), np.int32)
+        ctx.copy_out(extents_dev.ptr, extents)
+        ctx.sync()
+        if (extents[:, 0] < 0).any():
+            raise RuntimeError('to_external_box: empty np_mask.')
+
+        # launch 3: image and mask again, only the trimmed windows.  Image.to_cropped_image takes `down or height - 1` (and
+        # `right or width - 1`): a box that ends in row or column 0 leaves the image untrimmed on that axis while the mask
+        # is trimmed, so the two windows of a region can differ; such a region takes two records.
+        records, shapes, slots = [], [], []
+        for k in range(n):
+            up, down, left, right = (int(v) for v in extents[k])
+            full_h, full_w = full.shapes[k]
+            image_down, image_right = down or full_h - 1, right or full_w - 1
+            mask_shape = (down - up + 1, right - left + 1)
+            image_shape = (image_down - up + 1, image_right - left + 1)
+            shapes += [image_shape + (3,), mask_shape]
+            if image_shape == mask_shape:
+                records.append((k, up, left, mask_shape, 2 * k, 2 * k + 1))
+            else:
+                records.append((k, up, left, image_shape, 2 * k, None))
+                records.append((k, up, left, mask_shape, None, 2 * k + 1))
+        out = _Packed(ctx, shapes, src.resident)
+        trimmed = np.zeros(len(records), _native.REGION_WARP_PAIR_DTYPE)
+        for p, (k, up, left, shape, image_slot, mask_slot) in zip(trimmed, records):
+            for name in ('src_image', 'src_image_step', 'src_mask', 'src_mask_step', 'src_h', 'src_w', 'm'):
+                p[name] = pairs[k][name]
+            p['up'], p['left'], p['dst_h'], p['dst_w'] = up, left, shape[0], shape[1]
+            p['dst_image_off'] = -1 if image_slot is None else out.offsets[image_slot]
+            p['dst_mask_off'] = -1 if mask_slot is None else out.offsets[mask_slot]
+        _native.region_warp(trimmed, True, out.dev)
+
+        flattened_text_regions: List[FlattenedTextRegion] = []
+        for k in range(n):
+            box, (config, state) = boxes[k], states[k]
+            up, down, left, right = (int(v) for v in extents[k])
+            trimmed_char_polygons = None
+            if grouped_char_polygons is not None:
+                relative = [polygon.to_relative_polygon(origin_y=box.up, origin_x=box.left)
+                            for polygon in grouped_char_polygons[k]]
+                rotated = _rotate_polygons(config, box.shape, relative) if relative else None
+                if rotated:
+                    trimmed_char_polygons = [polygon.to_relative_polygon(origin_y=up, origin_x=left) for polygon in rotated]
+            flattened_image = Image(mat=out.plane(2 * k))
+            flattened_text_regions.append(FlattenedTextRegion(
+                is_typical=(k in typical_indices_set),
+                text_region_polygon=text_region_polygons[k],
+                page_image=image,
+                bounding_extended_text_region_mask=masks[k],
+                flattening_rotate_angle=flattening_rotate_angles[k],
+                shape_before_trim=full.shapes[k],
+                rotated_trimmed_box=Box(up=up, down=down, left=left, right=right),
+                shape_before_resize=flattened_image.shape,
+                post_rotate_angle=0,
+                flattened_image=flattened_image,
+                flattened_mask=Mask(mat=out.plane(2 * k + 1)),
+                flattened_char_polygons=trimmed_char_polygons,
+            ))
+        return flattened_text_regions
+
+
+# ---- the batched region methods ------------------------------------------------------------------------------------
+def _region_sources(regions):
+    arrays = []
+    for region in regions:
+        image, mask = _arr(region.flattened_image), _arr(region.flattened_mask)
+        _check_image(image)
+        assert not region.flattened_mask.box
+        arrays += [image, mask]
+    return _Sources(arrays)
+
+
+def resize_flattened_text_regions(flattened_text_regions: Sequence[FlattenedTextRegion],
+                                  resized_shapes: Sequence[Tuple[Optional[int], Optional[int]]]):
+    """``region.to_resized_flattened_text_region(resized_height, resized_width)`` for every region and its
+    ``(resized_height, resized_width)`` of ``resized_shapes``, in one launch."""
+    from vkit_amd.element.opt import generate_resized_shape
+    regions = list(flattened_text_regions)
+    assert len(regions) == len(resized_shapes)
+    if not regions:
+        return []
+    src = _region_sources(regions)
+    records, shapes = [], []
+    for k, (region, (resized_height, resized_width)) in enumerate(zip(regions, resized_shapes)):
+        targets = []
+        for element in (region.flattened_image, region.flattened_mask):
+            # image and mask are resized by calls of their own, each from its own shape
+            targets.append(tuple(generate_resized_shape(height=element.height, width=element.width,
+                                                        resized_height=resized_height, resized_width=resized_width)))
+        shapes += [targets[0] + (3,), targets[1]]
+        same = region.flattened_image.shape == region.flattened_mask.shape and targets[0] == targets[1]
+        if same:
+            records.append((k, region.flattened_image.shape, targets[0], True, True))
+        else:
+            records.append((k, region.flattened_image.shape, targets[0], True, False))
+            records.append((k, region.flattened_mask.shape, targets[1], False, True))
+    out = _Packed(src.ctx, shapes, src.resident)
+    pairs = np.zeros(len(records), _native.REGION_RESIZE_PAIR_DTYPE)
+    for p, (k, (sh, sw), (dh, dw), with_image, with_mask) in zip(pairs, records):
+        p['src_image'], p['src_image_step'] = src.ptr[2 * k], sw * 3
+        p['src_mask'], p['src_mask_step'] = src.ptr[2 * k + 1], sw
+        p['src_h'], p['src_w'], p['dst_h'], p['dst_w'] = sh, sw, dh, dw
+        p['dst_image_off'] = out.offsets[2 * k] if with_image else -1
+        p['dst_mask_off'] = out.offsets[2 * k + 1] if with_mask else -1
+    _native.region_resize(pairs, out.dev)
+    results = []
+    for k, (region, (resized_height, resized_width)) in enumerate(zip(regions, resized_shapes)):
+        polygons = None
+        if region.flattened_char_polygons is not None:
+            polygons = [polygon.to_conducted_resized_polygon(region.shape, resized_height=resized_height,
+                                                             resized_width=resized_width)
+                        for polygon in region.flattened_char_polygons]
+        results.append(attrs.evolve(region, flattened_image=Image(mat=out.plane(2 * k)),
+                                    flattened_mask=Mask(mat=out.plane(2 * k + 1)), flattened_char_polygons=polygons))
+    return results
+
+
+def _rotate_flattened_text_regions(regions, angles):
+    """rotate.distort of image, mask and char polygons of every region by its angle (no trim), in one launch"""
+    src = _region_sources(regions)
+    states = []
+    for region, angle in zip(regions, angles):
+        assert region.flattened_image.shape == region.flattened_mask.shape
+        states.append(_rotate_state(angle, region.shape))
+    shapes = []
+    for _, state in states:
+        shapes += [(state.dsize[1], state.dsize[0], 3), (state.dsize[1], state.dsize[0])]
+    out = _Packed(src.ctx, shapes, src.resident)
+    pairs = np.zeros(len(regions), _native.REGION_WARP_PAIR_DTYPE)
+    for k, (region, (_, state)) in enumerate(zip(regions, states)):
+        p = pairs[k]
+        p['src_image'], p['src_image_step'] = src.ptr[2 * k], region.width * 3
+        p['src_mask'], p['src_mask_step'] = src.ptr[2 * k + 1], region.width
+        p['src_h'], p['src_w'] = region.shape
+        p['m'] = state.trans_mat.reshape(6)
+        p['dst_h'], p['dst_w'] = shapes[2 * k + 1]
+        p['dst_image_off'], p['dst_mask_off'] = out.offsets[2 * k], out.offsets[2 * k + 1]
+    _native.region_warp(pairs, False, out.dev)
+    results = []
+    for k, (region, angle, (config, state)) in enumerate(zip(regions, angles, states)):
+        polygons = region.flattened_char_polygons
+        if polygons is not None:
+            polygons = _rotate_polygons(config, region.shape, polygons) if polygons else polygons
+        results.append(attrs.evolve(region, post_rotate_angle=angle, flattened_image=Image(mat=out.plane(2 * k)),
+                                    flattened_mask=Mask(mat=out.plane(2 * k + 1)), flattened_char_polygons=polygons))
+    return results
+
+
+def post_rotate_flattened_text_regions(flattened_text_regions: Sequence[FlattenedTextRegion], angles: Sequence[int]):
+    """``region.to_post_rotated_flattened_text_region(angle)`` for every region with a non-zero angle, in one launch; a region
+    whose angle is 0 is returned as it is."""
+    regions = list(flattened_text_regions)
+    assert len(regions) == len(angles)
+    picked = [k for k, angle in enumerate(angles) if angle != 0]
+    for k in picked:
+        assert regions[k].post_rotate_angle == 0
+    if picked:
+        rotated = _rotate_flattened_text_regions([regions[k] for k in picked], [angles[k] for k in picked])
+        for k, region in zip(picked, rotated):
+            regions[k] = region
+    return regions
+
+
+# ---- stacking ------------------------------------------------------------------------------------------------------
+def build_background_image_for_stacking(height: int, width: int):
+    """Channel k of pixel (y, x) is 255 exactly when k == (y + x) % 3 (the reference's three row patterns, :732-745)."""
+    if _native.resident_mode():
+        image, _ = _native.region_stack(np.zeros(0, _native.REGION_STACK_ITEM_DTYPE), (height, width))
+        return Image(mat=image)
+    phase = (np.arange(height)[:, None] + np.arange(width)[None, :]) % 3
+    return Image(mat=((phase[:, :, None] == np.arange(3)) * 255).astype(np.uint8))
+
+
+class ColumnPacker:
+    """The packer ``stack_flattened_text_regions`` falls back to without rectpack: rectangles one below the other in the order
+    they were added, all at x = 0.  The reference's only bin is (widest rectangle) x (sum of the heights), so the column
+    always fits.  The calls are the four of rectpack's packer that the reference uses."""
+
+    def __init__(self):
+        self.rects, self.bins, self.placed = [], [], []
+
+    def add_rect(self, width, height, rid=None):
+        self.rects.append((width, height, rid))
+
+    def add_bin(self, width, height):
+        self.bins.append((width, height))
+
+    def pack(self):
+        y = 0
+        self.placed = []
+        for width, height, rid in self.rects:
+            self.placed.append((0, 0, y, width, height, rid))
+            y += height
+
+    def rect_list(self):
+        return list(self.placed)
+
+
+def default_rect_packer_factory():
+    try:
+        from rectpack import newPacker
+    except ImportError:
+        return ColumnPacker()
+    return newPacker(rotation=False)
+
+
+def stack_flattened_text_regions(page_pad: int, flattened_text_regions_pad: int,
+                                 flattened_text_regions: Sequence[FlattenedTextRegion], rect_packer_factory=None):
+    """The reference's function (:748-856) with its packer as an argument: any object with ``add_rect``, ``add_bin``, ``pack``
+    and ``rect_list``.  One launch writes the striped page, the regions under their masks and the active mask."""
+    regions = list(flattened_text_regions)
+    page_double_pad = 2 * page_pad
+    double_pad = 2 * flattened_text_regions_pad
+    rect_packer = (rect_packer_factory or default_rect_packer_factory)()
+
+    bin_width = bin_height = 0
+    for ftr_idx, region in enumerate(regions):
+        rect_packer.add_rect(width=region.width + double_pad, height=region.height + double_pad, rid=ftr_idx)
+        bin_width = max(bin_width, region.width)
+        bin_height += region.height
+    rect_packer.add_bin(width=bin_width + double_pad, height=bin_height + double_pad)
+    rect_packer.pack()
+
+    padded_boxes: List[Optional[Box]] = [None] * len(regions)
+    for bin_idx, x, y, width, height, ftr_idx in rect_packer.rect_list():
+        assert bin_idx == 0
+        padded_boxes[ftr_idx] = Box(up=y, down=y + height - 1, left=x, right=x + width - 1)
+    assert all(box is not None for box in padded_boxes)
+
+    page_height = max(box.down for box in padded_boxes) + 1 + page_double_pad
+    page_width = max(box.right for box in padded_boxes) + 1 + page_double_pad
+
+    src = _region_sources(regions)
+    items = np.zeros(len(regions), _native.REGION_STACK_ITEM_DTYPE)
+    text_region_boxes: List[Box] = []
+    char_polygons: List[Polygon] = []
+    char_polygon_text_region_box_indices: List[int] = []
+    for k, (padded_box, region) in enumerate(zip(padded_boxes, regions)):
+        assert region.height + double_pad == padded_box.height
+        assert region.width + double_pad == padded_box.width
+        assert region.flattened_image.shape == region.flattened_mask.shape
+        up = padded_box.up + flattened_text_regions_pad + page_pad
+        left = padded_box.left + flattened_text_regions_pad + page_pad
+        text_region_boxes.append(Box(up=up, down=up + region.height - 1, left=left, right=left + region.width - 1))
+        item = items[k]
+        item['image'], item['mask'] = src.ptr[2 * k], src.ptr[2 * k + 1]
+        item['h'], item['w'], item['up'], item['left'] = region.height, region.width, up, left
+        if region.flattened_char_polygons:
+            for char_polygon in region.flattened_char_polygons:
+                char_polygons.append(char_polygon.to_shifted_polygon(offset_y=up, offset_x=left))
+                char_polygon_text_region_box_indices.append(k)
+    image, active_mask = _native.region_stack(items, (page_height, page_width), ctx=src.ctx)
+    if not src.resident:
+        image, active_mask = np.array(image.host()), np.array(active_mask.host())
+    return Image(mat=image), Mask(mat=active_mask), text_region_boxes, char_polygons, char_polygon_text_region_box_indices
