@@ -977,7 +977,7 @@ int vkx_region_crop_select_dev(vkx_ctx *ctx, const int32_t *windows_host, int n_
 
 /* ---- the pixel half of PageTextRegionStep (pipeline/text_detection/page_text_region.py) ---------------------------------
  * Four batched entry points, each ONE launch for all text regions of a page and no synchronisation; their per-region records
- * are HOST tables.  A record addresses its source planes by device pointer and row step (bytes from a row to the next, at
+ * are HOST tables (a fifth, vkx_region_extend_masks_dev below, builds the masks they start from).  A record addresses its source planes by device pointer and row step (bytes from a row to the next, at
  * least one row, unused with a single row: the pitch contract of this header), so a source may be a rectangle inside a
  * page plane or a plane of its own; what a call writes is dense and lies at a byte offset of one packed buffer `dst` of
  * `dst_bytes` bytes.  Refused (VKX_ERR_INVALID, nothing launched): a NULL pointer, a count outside 1 .. 4096 (0 .. 4096 for
@@ -1031,6 +1031,33 @@ typedef struct vkx_region_stack_item {
 } vkx_region_stack_item;
 int vkx_region_stack_dev(vkx_ctx *ctx, const vkx_region_stack_item *items_host, int n_items, uint8_t *page_image,
                          uint8_t *page_mask, int h, int w);
+/* vkx_region_extend_masks_dev: TextRegionFlattener.get_bounding_extended_text_region_masks (:477-558), the masks that
+ * build_flattened_text_regions starts from, for all text regions of a page: three launches whatever n_regions, into fresh
+ * planes.  text_mask: DEVICE uint8 [page_h][page_w] with its row step (the pitch contract of this header), the union T of the
+ * rasters of all text-region polygons (vkx_paint_polys_fresh_dev, mask only); read as != 0.  Per region one HOST record: its box
+ * BB (inclusive, inside the page) and three (offset, count) ranges of (x, y) pairs in the HOST int32 table pts_host, page
+ * coordinates: the original polygon O, the (possibly dilated) polygon D and the bounding rectangular polygon R.  With o, d, r the
+ * cv.fillPoly rasters of the three (pixel for pixel vkx_fill_poly_mask_u8's: LINE_8 outline plus even-odd spans), every pixel p
+ * of BB gets
+ *     out(p) = (d(p) and not (r(p) and T(p) and not o(p))) or (r(p) and not T(p))
+ * as uint8 0 / 1 in the dense plane [BB.h][BB.w] at dst_off of the packed buffer `dst`; every byte of it is written once, `dst`
+ * needs no memset.  The host tables travel through the page-locked ring: the call does not synchronise while no polygon has
+ * more than 64 vertices; with a larger one it waits for the crossing-overflow flag, and more than 64 crossings of one polygon
+ * on a scanline are VKX_ERR_UNSUPPORTED (as in vkx_paint_polys_dev).  Refused (VKX_ERR_INVALID, nothing launched): a NULL
+ * pointer, n_regions outside 1 .. 4096, a BB outside the page or with a side outside 1 .. 32767, a polygon of fewer than 1
+ * point or with a vertex outside BB (the reference asserts that a filling polygon's box lies inside the target's box,
+ * element/box.py:227-228), a destination outside `dst`, destinations that overlap one another, text_mask overlapping `dst`, a
+ * row step shorter than a row or negative. */
+typedef struct vkx_region_masks_rec {
+    int32_t up, down, left, right;      /* BB, inclusive */
+    int32_t o_off, o_cnt;               /* the ranges of O, D, R in pts_host, in points */
+    int32_t d_off, d_cnt;
+    int32_t r_off, r_cnt;
+    int64_t dst_off;
+} vkx_region_masks_rec;
+int vkx_region_extend_masks_dev(vkx_ctx *ctx, const vkx_region_masks_rec *regions_host, int n_regions, const int32_t *pts_host,
+                                const uint8_t *text_mask, ptrdiff_t text_mask_step, int page_h, int page_w, uint8_t *dst,
+                                size_t dst_bytes);
 
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx

@@ -394,6 +394,8 @@ _SIGNATURES['vkx_region_warp_dev'] = [c_void_p, c_void_p, c_int, c_int, c_void_p
 _SIGNATURES['vkx_region_extent_dev'] = [c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_void_p]
 _SIGNATURES['vkx_region_resize_dev'] = [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_region_stack_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int]
+_SIGNATURES['vkx_region_extend_masks_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_ssize, c_int, c_int, c_void_p,
+                                              ctypes.c_size_t]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
@@ -2586,3 +2588,30 @@ def region_stack(items, shape, ctx=None):
     check(lib().vkx_region_stack_dev(ctx.handle, items.ctypes.data if len(items) else None, len(items), c_void_p(image.ptr),
                                      c_void_p(mask.ptr), h, w))
     return image, mask
+
+
+# the bounding extended text-region masks (csrc/region_masks.hip): vkx_region_masks_rec of include/vkx.h
+REGION_MASKS_REC_DTYPE = np.dtype([('up', np.int32), ('down', np.int32), ('left', np.int32), ('right', np.int32),
+                                   ('o_off', np.int32), ('o_cnt', np.int32), ('d_off', np.int32), ('d_cnt', np.int32),
+                                   ('r_off', np.int32), ('r_cnt', np.int32), ('dst_off', np.int64)], align=True)
+assert REGION_MASKS_REC_DTYPE.itemsize == 48
+
+
+def region_extend_masks(records, points_xy, text_mask, dst, text_mask_step=None):
+    """vkx_region_extend_masks_dev: ``records`` REGION_MASKS_REC_DTYPE (a box and the point ranges of the original, the dilated
+    and the bounding rectangular polygon of every region), ``points_xy`` the int32 (N, 2) table of (x, y) page coordinates they
+    index, ``text_mask`` the uint8 DevArray (page_h, page_w) of all text-region polygons (``text_mask_step`` bytes from a row
+    to the next: its width by default), ``dst`` the packed uint8 DevArray the dense masks are written into.  THREE launches
+    whatever the number of regions; asynchronous while no polygon has more than 64 vertices."""
+    records = _records(records, REGION_MASKS_REC_DTYPE)
+    points_xy = np.ascontiguousarray(points_xy, dtype=np.int32).reshape(-1, 2)
+    for off, cnt in (('o_off', 'o_cnt'), ('d_off', 'd_cnt'), ('r_off', 'r_cnt')):
+        if len(records) and int((records[off].astype(np.int64) + records[cnt]).max()) > len(points_xy):
+            raise ValueError('a point range outside the point table')
+    if text_mask.ctx is not dst.ctx:
+        raise ValueError('the text mask and the destination live on one context')
+    page_h, page_w = text_mask.shape
+    check(lib().vkx_region_extend_masks_dev(dst.ctx.handle, records.ctypes.data, len(records), points_xy.ctypes.data,
+                                            c_void_p(text_mask.ptr), page_w if text_mask_step is None else int(text_mask_step),
+                                            page_h, page_w, c_void_p(dst.ptr), dst.nbytes))
+    dst.invalidate_host()

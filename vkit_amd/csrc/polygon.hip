@@ -11,37 +11,18 @@
 #include "vkx_internal.h"
 #include "vkx_host_stage.h"
 #include <string.h>
-#include "vkx_cell.h"
-
-#include <algorithm>
+#include "vkx_poly_edges.h"
 
 namespace {
-
-struct PolyEdge {
-    int xa, ya, xb, yb;        // contour order
-    int lx, ly, dmaj, dmin;    // Bresenham from the left end
-    int sy, ymajor;
-    int step_base;             // prefix of (dmaj + 1) over the edges
-    int y0, y1;                // scanline range of the edge (y0 == y1: horizontal, not in the edge table)
-    int poly, pad;             // batched paint: 1-based paint order of the polygon this edge belongs to
-    long long x0_fix, dx_fix;  // 16.16 x at y0, dx per scanline
-};
 
 __global__ void __launch_bounds__(256) k_poly_outline(const PolyEdge *__restrict__ edges, int nedges, int total_steps,
                                                       uint8_t *__restrict__ mask, int h, int w, ptrdiff_t stride)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= total_steps) return;
-    int lo = 0, hi = nedges - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (edges[mid].step_base <= t) lo = mid; else hi = mid - 1;
-    }
-    const PolyEdge e = edges[lo];
-    const int k = t - e.step_base;
-    const int m = vkc::bres_minor(k, e.dmaj, e.dmin);
-    const int x = e.ymajor ? e.lx + m : e.lx + k;
-    const int y = e.ymajor ? e.ly + e.sy * k : e.ly + e.sy * m;
+    const PolyEdge e = vkp::edge_of_step(edges, nedges, t);
+    int x, y;
+    vkp::edge_pixel(e, t, x, y);
     if ((unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h) mask[(ptrdiff_t)y * stride + x] = 1;
 }
 
@@ -88,36 +69,6 @@ __global__ void __launch_bounds__(256) k_poly_spans(const PolyEdge *__restrict__
     }
 }
 
-// Edge table of one closed contour (cv::fillPoly -> CollectPolyEdges + the LINE_8 outline).
-void build_edges(const int32_t *pts, int npts, int poly, PolyEdge *edges, long long *steps, int *ymin, int *ymax)
-{
-    for (int i = 0; i < npts; i++) {
-        const int a = (i + npts - 1) % npts;
-        PolyEdge &e = edges[i];
-        e.xa = pts[2 * a]; e.ya = pts[2 * a + 1];
-        e.xb = pts[2 * i]; e.yb = pts[2 * i + 1];
-        int lx = e.xa, ly = e.ya, rx = e.xb, ry = e.yb;
-        if (rx < lx) { std::swap(lx, rx); std::swap(ly, ry); }
-        const int dx = rx - lx, dy = ry - ly, ady = dy < 0 ? -dy : dy;
-        e.lx = lx; e.ly = ly; e.sy = dy < 0 ? -1 : 1;
-        e.ymajor = ady > dx;
-        e.dmaj = e.ymajor ? ady : dx;
-        e.dmin = e.ymajor ? dx : ady;
-        e.step_base = (int)*steps;
-        *steps += e.dmaj + 1;
-        e.y0 = std::min(e.ya, e.yb); e.y1 = std::max(e.ya, e.yb);
-        e.poly = poly; e.pad = 0;
-        if (e.ya != e.yb) {
-            const long long xa = (long long)e.xa << 16, xb = (long long)e.xb << 16;
-            e.dx_fix = (xb - xa) / (long long)(e.yb - e.ya);
-            e.x0_fix = e.ya < e.yb ? xa : xb;
-            *ymin = std::min(*ymin, e.y0); *ymax = std::max(*ymax, e.y1);
-        } else {
-            e.dx_fix = 0; e.x0_fix = 0;
-        }
-    }
-}
-
 // ---- batched ordered paint: many polygons, later ones win ------------------------------------------------------
 struct PaintItem { // one (polygon, scanline) pair
     int edge_begin, edge_end; // the polygon's edges
@@ -129,24 +80,14 @@ __global__ void __launch_bounds__(256) k_paint_outline(const PolyEdge *__restric
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= total_steps) return;
-    int lo = 0, hi = nedges - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (edges[mid].step_base <= t) lo = mid; else hi = mid - 1;
-    }
-    const PolyEdge e = edges[lo];
-    const int k = t - e.step_base;
-    const int m = vkc::bres_minor(k, e.dmaj, e.dmin);
-    const int x = e.ymajor ? e.lx + m : e.lx + k;
-    const int y = e.ymajor ? e.ly + e.sy * k : e.ly + e.sy * m;
+    const PolyEdge e = vkp::edge_of_step(edges, nedges, t);
+    int x, y;
+    vkp::edge_pixel(e, t, x, y);
     // (several label plane sets painted by one call live in bands of h rows of one raster: e.pad is the band, the polygon is clipped to it)
     if ((unsigned)x < (unsigned)w && (unsigned)(y - e.pad * h) < (unsigned)h) atomicMax(&owner[(size_t)y * w + x], e.poly);
 }
 
-constexpr int kPaintCross = 64; // crossings of one polygon on one scanline handled by the batched path
-
-// One wave per (polygon, scanline): lanes test the polygon's edges, crossings are ranked by counting (no sort
-// loop: rank = number of crossings that precede it, ties by edge index), spans are painted lane-parallel.
+// One wave per (polygon, scanline): the crossings of vkp::wave_crossings, spans are painted lane-parallel.
 __global__ void __launch_bounds__(256) k_paint_spans(const PolyEdge *__restrict__ edges,
                                                      const PaintItem *__restrict__ items, int n_items,
                                                      int *__restrict__ owner, int h, int w, int *__restrict__ overflow)
@@ -156,42 +97,23 @@ __global__ void __launch_bounds__(256) k_paint_spans(const PolyEdge *__restrict_
     __shared__ int count_all[4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int it = blockIdx.x * 4 + wave;
-    long long *xs = xs_all[wave], *sorted = sorted_all[wave];
+    const long long *sorted = sorted_all[wave];
     if (lane == 0) count_all[wave] = 0;
     __syncthreads();
     const bool live = it < n_items;
     PaintItem item = {0, 0, 0, 0};
     if (live) item = items[it];
-    for (int i = item.edge_begin + lane; i < item.edge_end; i += 64) {
-        const PolyEdge &e = edges[i];
-        if (e.y0 != e.y1 && e.y0 <= item.y && item.y < e.y1) {
-            const int slot = atomicAdd(&count_all[wave], 1);
-            // tie-break on the edge index keeps the ranking a permutation
-            if (slot < kPaintCross) xs[slot] = e.x0_fix + (long long)(item.y - e.y0) * e.dx_fix;
-        }
-    }
-    __syncthreads();
-    int n = count_all[wave];
+    int n = vkp::wave_crossings(edges, item.edge_begin, item.edge_end, item.y, xs_all[wave], &count_all[wave], lane);
     if (n > kPaintCross) {
         if (lane == 0) atomicExch(overflow, 1);
         n = 0;
     }
-    if (lane < n) {
-        const long long v = xs[lane];
-        int rank = 0;
-        for (int j = 0; j < n; j++) {
-            const long long u = xs[j];
-            rank += (u < v) || (u == v && j < lane);
-        }
-        sorted[rank] = v;
-    }
-    __syncthreads();
+    vkp::wave_rank(xs_all[wave], sorted_all[wave], n, lane);
     if (!live || (unsigned)item.y >= (unsigned)h) return;
     int *row = owner + (size_t)item.y * w;
     for (int a = 0; a + 1 < n; a += 2) {
-        long long x1 = (sorted[a] + 65535) >> 16, x2 = sorted[a + 1] >> 16;
-        if (x1 < 0) x1 = 0;
-        if (x2 >= w) x2 = w - 1;
+        long long x1, x2;
+        vkp::span_of(sorted, a, w, x1, x2);
         for (long long x = x1 + lane; x <= x2; x += 64) atomicMax(&row[x], item.order);
     }
 }

@@ -3,8 +3,12 @@ output container.
 
 ``PageTextRegionStepOutput`` (:177-186) is the input of PageTextRegionLabelStep and PageTextRegionCroppingStep.  The step as
 a whole needs shapely, rectpack, pyclipper and cv.findContours and stays outside the accelerated path; what is here is
-everything of it that is pixel work, batched over all text regions of a page (csrc/region_flatten.hip):
+everything of it that is pixel work, batched over all text regions of a page (csrc/region_masks.hip,
+csrc/region_flatten.hip):
 
+* ``TextRegionFlattener.get_bounding_extended_text_region_masks`` (:477-558): the page's text mask by the fresh mask paint,
+  then the three rasters and the mask algebra of every region -- three launches, no synchronisation while no polygon has
+  more than 64 vertices;
 * ``TextRegionFlattener.build_flattened_text_regions`` (:560-656): cut, rotate and trim every region -- three launches and
   one synchronisation (the read of the rotated masks' extents) whatever the number of regions;
 * ``resize_flattened_text_regions`` / ``post_rotate_flattened_text_regions``, the batched forms of
@@ -12,7 +16,8 @@ everything of it that is pixel work, batched over all text regions of a page (cs
   launch each, no synchronisation;
 * ``build_background_image_for_stacking`` and ``stack_flattened_text_regions`` (:732-856): one launch, no synchronisation.
 
-The polygon geometry that decides the masks and the angles is the caller's (the host's).  Results are device resident inside
+The polygon geometry that decides the polygons and the angles (shapely, pyclipper, findContours, the KD-tree) is the caller's
+(the host's); the masks built from them flow into the flattening on the device.  Results are device resident inside
 ``_native.resident(True)`` or when an input was; otherwise they come back as numpy arrays, by one copy a call.
 """
 import math
@@ -177,9 +182,55 @@ def _rotate_polygons(config, shape, polygons):
 
 # ---- TextRegionFlattener -----------------------------------------------------------------------------------------
 class TextRegionFlattener:
-    """``build_flattened_text_regions`` of the reference's class (:560-656).  The geometric methods that lead to its
-    arguments (polygon dilation, minimum-area rectangles, the KD-tree of the main angles, the mask algebra of
-    ``get_bounding_extended_text_region_masks``) are the caller's."""
+    """``get_bounding_extended_text_region_masks`` (:477-558) and ``build_flattened_text_regions`` (:560-656) of the
+    reference's class.  The geometric methods that lead to their arguments (polygon dilation, minimum-area rectangles, the
+    KD-tree of the main angles) are the caller's."""
+
+    @classmethod
+    def get_bounding_extended_text_region_masks(cls, shape: Tuple[int, int], text_region_polygons: Sequence[Polygon],
+                                                dilated_text_region_polygons: Sequence[Polygon],
+                                                bounding_rectangular_polygons: Sequence[Polygon],
+                                                typical_indices: Sequence[int], main_angles: Sequence[int]):
+        """One box-attached mask a text region: the (possibly dilated) region trimmed by the other text regions under its
+        bounding rectangle, united with the non-text part of that rectangle.  Device views inside ``_native.resident(True)``,
+        numpy arrays from one download otherwise."""
+        typical_indices_set = set(typical_indices)
+        n = len(text_region_polygons)
+        if n == 0:
+            return []
+        ctx = _native.default_ctx()
+        height, width = (int(v) for v in shape)
+
+        # the text mask of the page: every text-region polygon, painted into a fresh device plane
+        text_mask = ctx.dev_empty((height, width), np.uint8)
+        originals = [polygon.to_np_array() for polygon in text_region_polygons]
+        _native.paint_polys(originals, mask=text_mask, fresh=True)
+
+        boxes: List[Box] = []
+        tables = []
+        records = np.zeros(n, _native.REGION_MASKS_REC_DTYPE)
+        at = 0
+        for idx in range(n):
+            dilated_text_region_polygon = dilated_text_region_polygons[idx]
+            bounding_rectangular_polygon = bounding_rectangular_polygons[idx]
+            if typical_indices_set and idx not in typical_indices_set:
+                # Patch bounding rectangular polygon if is nontypical.
+                bounding_rectangular_polygon = dilated_text_region_polygon.to_bounding_rectangular_polygon(
+                    shape=shape, angle=main_angles[idx])
+            # (the rectangle may leave the dilated polygon's box a little: the union of the two)
+            box = Box.from_boxes((dilated_text_region_polygon.bounding_box, bounding_rectangular_polygon.bounding_box))
+            boxes.append(box)
+            rec = records[idx]
+            rec['up'], rec['down'], rec['left'], rec['right'] = box.up, box.down, box.left, box.right
+            for name, points in (('o', originals[idx]), ('d', dilated_text_region_polygon.to_np_array()),
+                                 ('r', bounding_rectangular_polygon.to_np_array())):
+                rec[name + '_off'], rec[name + '_cnt'] = at, len(points)
+                tables.append(points)
+                at += len(points)
+        out = _Packed(ctx, [box.shape for box in boxes], _native.resident_mode())
+        records['dst_off'] = out.offsets
+        _native.region_extend_masks(records, np.concatenate(tables, axis=0), text_mask, out.dev)
+        return [Mask(mat=out.plane(k), box=box) for k, box in enumerate(boxes)]
 
     @classmethod
     def build_flattened_text_regions(cls, image: Image, text_region_polygons: Sequence[Polygon],
