@@ -498,7 +498,10 @@ int vkx_mls_project(vkx_ctx *ctx, const float *src_handles, const float *dst_han
  * cv.fillPoly(zeros((h, w), uint8), [pts], 1): PolygonInternals.np_mask element/polygon.py:70-77
  * (Bresenham LINE_8 outline + even-odd scanline spans).  pts: HOST int32 [npts, 2] as (x, y), all
  * inside the mask.  *_dev: mask is a device plane that is OR-ed into; host variant: mask is
- * overwritten with the 0/1 raster. */
+ * overwritten with the 0/1 raster.  The raster is the one of vkx_paint_polys* and vkx_region_extend_masks_dev (one
+ * definition, different stores); a polygon with more than 512 crossings on one scanline is refused (VKX_ERR_UNSUPPORTED).
+ * _dev: asynchronous on the ctx stream up to 512 vertices (pts_host is consumed before the call returns); with more the
+ * call waits for the overflow flag. */
 int vkx_fill_poly_mask_u8_dev(vkx_ctx *ctx, const int32_t *pts_host, int npts, uint8_t *mask, int h, int w,
                               ptrdiff_t mask_stride);
 int vkx_fill_poly_mask_u8(vkx_ctx *ctx, const int32_t *pts_host, int npts, uint8_t *mask, int h, int w,
@@ -1037,7 +1040,7 @@ int vkx_region_stack_dev(vkx_ctx *ctx, const vkx_region_stack_item *items_host, 
  * rasters of all text-region polygons (vkx_paint_polys_fresh_dev, mask only); read as != 0.  Per region one HOST record: its box
  * BB (inclusive, inside the page) and three (offset, count) ranges of (x, y) pairs in the HOST int32 table pts_host, page
  * coordinates: the original polygon O, the (possibly dilated) polygon D and the bounding rectangular polygon R.  With o, d, r the
- * cv.fillPoly rasters of the three (pixel for pixel vkx_fill_poly_mask_u8's: LINE_8 outline plus even-odd spans), every pixel p
+ * cv.fillPoly rasters of the three (the raster of vkx_fill_poly_mask_u8: LINE_8 outline plus even-odd spans), every pixel p
  * of BB gets
  *     out(p) = (d(p) and not (r(p) and T(p) and not o(p))) or (r(p) and not T(p))
  * as uint8 0 / 1 in the dense plane [BB.h][BB.w] at dst_off of the packed buffer `dst`; every byte of it is written once, `dst`

@@ -99,3 +99,54 @@ def test_polygon_fill_and_extract_operators(N):
     want = mat[box.up:box.down + 1, box.left:box.right + 1].copy()
     want[~raster] = 0
     np.testing.assert_array_equal(extracted.mat, want)
+
+
+# ---- combs: 2 * teeth crossings a scanline, around the one-pass boundary of the crossing ranking and at the capacities
+def _comb(teeth):
+    from text_region_masks_restate import comb
+    return (16, 4 * teeth + 9), comb(3, 2, 9, 13, teeth)
+
+
+@pytest.mark.parametrize('teeth', [32, 33, 256])
+def test_fill_poly_comb_up_to_512_crossings(N, teeth):
+    shape, pts = _comb(teeth)
+    got = _check(N, shape, pts)
+    assert (np.diff(got[5].astype(np.int8)) == 1).sum() == teeth      # that many runs on a row through the teeth
+
+
+def test_fill_poly_comb_beyond_512_crossings_is_refused(N):
+    shape, pts = _comb(257)
+    with pytest.raises(N.VkxError, match='512 edge crossings'):
+        N.fill_poly_mask(shape, pts)
+    _check(N, shape, _comb(256)[1])                                   # the context goes on
+
+
+def test_paint_polys_comb_at_and_beyond_64_crossings(N):
+    """a 32-tooth comb (64 crossings) over a rectangle equals the ordered paint of the oracle's rasters; a 33-tooth comb is
+    refused, and the paint after it on the same context is correct (the ownership raster is zero again after the error exit)"""
+    ctx = N.default_ctx()
+    shape, pts = _comb(33)
+    rect = np.array([(1, 1), (shape[1] - 2, 1), (shape[1] - 2, 11), (1, 11)], np.int32)
+    values = [3.5, 7.25]
+
+    def want(polygons):
+        mask, score = np.zeros(shape, np.uint8), np.zeros(shape, np.float32)
+        for polygon, value in zip(polygons, values):
+            inside = O.fill_poly(shape, polygon).astype(bool)
+            mask[inside] = 1
+            score[inside] = value
+        return mask, score
+
+    def paint(polygons):
+        mask, score = N.dev_zeros(shape, np.uint8, ctx), N.dev_zeros(shape, np.float32, ctx)
+        N.paint_polys(polygons, values=values, mask=mask, score=score, ctx=ctx)
+        return np.array(mask.host()), np.array(score.host())
+
+    polygons = [rect, _comb(32)[1]]
+    for got, ref in zip(paint(polygons), want(polygons)):
+        np.testing.assert_array_equal(got, ref)
+    with pytest.raises(N.VkxError, match='64 edge crossings'):
+        paint([rect, pts])
+    polygons = [_comb(32)[1], rect + np.asarray([1, 3], np.int32)]           # (still inside the plane, as the oracle requires)
+    for got, ref in zip(paint(polygons), want(polygons)):
+        np.testing.assert_array_equal(got, ref)

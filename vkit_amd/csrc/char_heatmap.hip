@@ -17,6 +17,7 @@
 // (char, pixel) pair is visited once, so the count needs no deduplication.
 #include "vkx_cell.h"
 #include "vkx_internal.h"
+#include "vkx_poly_raster.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,16 +31,9 @@ constexpr int kMaxRadius = 1024;
 constexpr int kMaxSide = 1 << 24;          // page sides below 2^24: the float32 integer points of the reference are exact
 constexpr int kOneBits = 0x3f800000;       // 1.0f: the initial min
 
-struct Edge {                 // one edge of the char's integer quad, vertex (i + 3) & 3 -> vertex i
-    long long x0_fix, dx_fix; // 16.16 x at y0 and per scanline (spans; y0 == y1: horizontal, no crossing)
-    int y0, y1;
-    int lx, ly, dmaj, dmin;   // LINE_8 from the left end (cv::LineIterator)
-    int sy, ymajor;
-};
-
 struct CharHeat {             // what the setup pass leaves for the raster
     vkd::CoordPerspective coord;
-    Edge e[4];
+    vkp::Edge e[4];           // of the char's integer quad, vertex (i + 3) & 3 -> vertex i (vkp::quad_covers)
     int up, left, bh, bw;     // the bounding box in page coordinates
 };
 
@@ -65,59 +59,8 @@ __global__ void __launch_bounds__(256) k_char_heatmap_setup(const double *__rest
     C.coord = vkd::make_perspective(H, C.bh, C.bw);        // warpPerspective(template, H, (bbox.width, bbox.height))
     int vx[4], vy[4];
     for (int k = 0; k < 4; k++) { vx[k] = (int)rel[2 * k]; vy[k] = (int)rel[2 * k + 1]; }
-    for (int i = 0; i < 4; i++) {
-        const int a = (i + 3) & 3;
-        Edge &e = C.e[i];
-        int lx = vx[a], ly = vy[a], rx = vx[i], ry = vy[i];
-        if (rx < lx) { lx = vx[i]; ly = vy[i]; rx = vx[a]; ry = vy[a]; }
-        const int dx = rx - lx, dy = ry - ly, ady = dy < 0 ? -dy : dy;
-        e.lx = lx; e.ly = ly; e.sy = dy < 0 ? -1 : 1;
-        e.ymajor = ady > dx;
-        e.dmaj = e.ymajor ? ady : dx;
-        e.dmin = e.ymajor ? dx : ady;
-        e.y0 = min(vy[a], vy[i]); e.y1 = max(vy[a], vy[i]);
-        if (vy[a] != vy[i]) {
-            const long long xa = (long long)vx[a] << 16, xb = (long long)vx[i] << 16;
-            e.dx_fix = (xb - xa) / (long long)(vy[i] - vy[a]);
-            e.x0_fix = vy[a] < vy[i] ? xa : xb;
-        } else {
-            e.dx_fix = 0; e.x0_fix = 0;
-        }
-    }
+    for (int i = 0; i < 4; i++) C.e[i] = vkp::make_edge(vx[(i + 3) & 3], vy[(i + 3) & 3], vx[i], vy[i]);
     heat[g] = C;
-}
-
-// cv.fillPoly(zeros(bh, bw), [quad], 1) at (x, y), as the oracle's closed form (vko_fill_poly_closed_form): the LINE_8
-// outline of every edge, or inside an even-odd span [ceil(xa), floor(xb)] of the row's crossings (at most 4 for a quad).
-__device__ __forceinline__ bool in_fill_poly(const Edge (&E)[4], int x, int y)
-{
-    long long xs[4];
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const bool hit = E[i].y0 != E[i].y1 && E[i].y0 <= y && y < E[i].y1;
-        xs[i] = hit ? E[i].x0_fix + (long long)(y - E[i].y0) * E[i].dx_fix : LLONG_MAX;
-        n += hit;
-    }
-    // sort 4 (unused slots hold LLONG_MAX and sort last)
-#define VKX_CX(a, b) { const long long lo = xs[a] < xs[b] ? xs[a] : xs[b], hi = xs[a] < xs[b] ? xs[b] : xs[a]; xs[a] = lo; xs[b] = hi; }
-    VKX_CX(0, 1) VKX_CX(2, 3) VKX_CX(0, 2) VKX_CX(1, 3) VKX_CX(1, 2)
-#undef VKX_CX
-    const long long X = x;
-    if (n >= 2 && ((xs[0] + 65535) >> 16) <= X && X <= (xs[1] >> 16)) return true;
-    if (n >= 4 && ((xs[2] + 65535) >> 16) <= X && X <= (xs[3] >> 16)) return true;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const Edge &e = E[i];
-        if (e.ymajor) {
-            const int k = (y - e.ly) * e.sy;
-            if (k >= 0 && k <= e.dmaj && x == e.lx + vkc::bres_minor(k, e.dmaj, e.dmin)) return true;
-        } else {
-            const int k = x - e.lx;
-            if (k >= 0 && k <= e.dmaj && y == e.ly + e.sy * vkc::bres_minor(k, e.dmaj, e.dmin)) return true;
-        }
-    }
-    return false;
 }
 
 // one workgroup per 32 x 8 tile of a char box; tile_start[g] .. tile_start[g + 1] are char g's tiles
@@ -127,17 +70,12 @@ __global__ void __launch_bounds__(256) k_char_heatmap_raster(const CharHeat *__r
                                                              int *__restrict__ count)
 {
     const int t = blockIdx.x;
-    int lo = 0, hi = n - 1;               // the last char whose first tile is <= t
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tile_start[mid] <= t) lo = mid;
-        else hi = mid - 1;
-    }
+    const int lo = vkd::last_at_most(n, t, [&](int g) { return tile_start[g]; });     // the char of tile t
     const CharHeat &C = heat[lo];
     const int tiles_x = (C.bw + kTileW - 1) / kTileW, lt = t - tile_start[lo];
     const int ry = (lt / tiles_x) * kTileH + (threadIdx.x / kTileW), rx = (lt % tiles_x) * kTileW + (threadIdx.x % kTileW);
     if (ry >= C.bh || rx >= C.bw) return;
-    if (!in_fill_poly(C.e, rx, ry)) return;
+    if (!vkp::quad_covers(C.e, rx, ry)) return;
     int X, Y;
     C.coord(rx, ry, X, Y);
     const float v = vkd::sample_f32(tmpl, E, E, E, X, Y);

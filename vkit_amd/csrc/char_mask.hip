@@ -189,12 +189,7 @@ __global__ void __launch_bounds__(256) k_char_mask_raster(const CharIn *__restri
                                                           int n, int R, int w, const SetDev *__restrict__ sets)
 {
     const int t = blockIdx.x;
-    int lo = 0, hi = n - 1;               // the last char whose first tile is <= t
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tile_start[mid] <= t) lo = mid;
-        else hi = mid - 1;
-    }
+    const int lo = vkd::last_at_most(n, t, [&](int g) { return tile_start[g]; });     // the char of tile t
     const CharGeo &G = geo[lo];
     const int tiles_x = (G.bw + kTile - 1) / kTile, lt = t - tile_start[lo];
     const int ry = (lt / tiles_x) * kTile + (threadIdx.x >> 4), rx = (lt % tiles_x) * kTile + (threadIdx.x & 15);

@@ -1,122 +1,51 @@
-// cv.fillPoly(mask, [pts], 1) for one polygon of any vertex count on gfx950
+// The polygon rasters of the C ABI on gfx950: cv.fillPoly(mask, [pts], 1) for one polygon of any vertex count
 // (reference: PolygonInternals.np_mask, element/polygon.py:70-77; used by Polygon.fill_* and by the active mask
-// of image-grid distortions, grid_rendering/interface.py:177-192).
+// of image-grid distortions, grid_rendering/interface.py:177-192) and the ordered paint of the polygons of a page.
 //
-//   k_poly_outline  one lane per (edge, major step): pixel of the 8-connected Bresenham line walked from the
-//                   edge's left end (cv::LineIterator), closed form of the error recurrence.
-//   k_poly_spans    one workgroup per scanline: lanes collect the 16.16 fixed-point crossings of the half-open
-//                   edges (y0 <= y < y1) into LDS, sort them, and fill the even-odd spans
-//                   [ceil(xa), floor(xb)] cooperatively.
+// The raster is vkx_poly_raster.h's (vkp::k_outline, vkp::k_spans, the host-side vkp::Raster), shared with region_masks.hip.
+// What is here: the two sinks -- a byte store of 1 for the single polygon, atomicMax of the paint order into an ownership raster
+// for the paint --, the paint's resolve kernel and the entry points.
 // Vertices are host data (a few to a few thousand points); the edge table is built on the host and staged.
 #include "vkx_internal.h"
 #include "vkx_host_stage.h"
 #include <string.h>
-#include "vkx_poly_edges.h"
+#include "vkx_poly_raster.h"
 
 namespace {
 
-__global__ void __launch_bounds__(256) k_poly_outline(const PolyEdge *__restrict__ edges, int nedges, int total_steps,
-                                                      uint8_t *__restrict__ mask, int h, int w, ptrdiff_t stride)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= total_steps) return;
-    const PolyEdge e = vkp::edge_of_step(edges, nedges, t);
-    int x, y;
-    vkp::edge_pixel(e, t, x, y);
-    if ((unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h) mask[(ptrdiff_t)y * stride + x] = 1;
-}
-
-constexpr int kMaxCross = 512;
-
-__global__ void __launch_bounds__(256) k_poly_spans(const PolyEdge *__restrict__ edges, int nedges, int ymin,
-                                                    uint8_t *__restrict__ mask, int h, int w, ptrdiff_t stride,
-                                                    int *__restrict__ overflow)
-{
-    __shared__ long long xs[kMaxCross];
-    __shared__ int count;
-    const int y = ymin + blockIdx.x;
-    if (threadIdx.x == 0) count = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nedges; i += 256) {
-        const PolyEdge &e = edges[i];
-        if (e.y0 != e.y1 && e.y0 <= y && y < e.y1) {
-            const int slot = atomicAdd(&count, 1);
-            if (slot < kMaxCross) xs[slot] = e.x0_fix + (long long)(y - e.y0) * e.dx_fix;
-        }
+struct ByteSink {              // vkx_fill_poly_mask_u8_dev: mask[y][x] = 1 inside [h, w]
+    uint8_t *mask;
+    int h, w;
+    ptrdiff_t stride;
+    struct Row {
+        uint8_t *p;
+        int w;
+        __device__ void operator()(int x) const { p[x] = 1; }
+    };
+    __device__ void pixel(const vkp::PolyEdge &, int x, int y) const
+    {
+        if ((unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h) mask[(ptrdiff_t)y * stride + x] = 1;
     }
-    __syncthreads();
-    int n = count;
-    if (n > kMaxCross) {
-        if (threadIdx.x == 0) atomicExch(overflow, 1);
-        n = kMaxCross;
-    }
-    if (threadIdx.x == 0) {
-        for (int a = 1; a < n; a++) {
-            const long long v = xs[a];
-            int b = a - 1;
-            while (b >= 0 && xs[b] > v) { xs[b + 1] = xs[b]; b--; }
-            xs[b + 1] = v;
-        }
-    }
-    __syncthreads();
-    if ((unsigned)y >= (unsigned)h) return;
-    uint8_t *row = mask + (ptrdiff_t)y * stride;
-    for (int a = 0; a + 1 < n; a += 2) {
-        long long x1 = (xs[a] + 65535) >> 16, x2 = xs[a + 1] >> 16;
-        if (x1 < 0) x1 = 0;
-        if (x2 >= w) x2 = w - 1;
-        for (long long x = x1 + threadIdx.x; x <= x2; x += 256) row[x] = 1;
-    }
-}
-
-// ---- batched ordered paint: many polygons, later ones win ------------------------------------------------------
-struct PaintItem { // one (polygon, scanline) pair
-    int edge_begin, edge_end; // the polygon's edges
-    int y, order;             // scanline, 1-based paint order
+    __device__ Row row(const vkp::Item &item) const { return Row{mask + (ptrdiff_t)item.y * stride, (unsigned)item.y < (unsigned)h ? w : 0}; }
 };
 
-__global__ void __launch_bounds__(256) k_paint_outline(const PolyEdge *__restrict__ edges, int nedges, int total_steps,
-                                                       int *__restrict__ owner, int h, int w)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= total_steps) return;
-    const PolyEdge e = vkp::edge_of_step(edges, nedges, t);
-    int x, y;
-    vkp::edge_pixel(e, t, x, y);
-    // (several label plane sets painted by one call live in bands of h rows of one raster: e.pad is the band, the polygon is clipped to it)
-    if ((unsigned)x < (unsigned)w && (unsigned)(y - e.pad * h) < (unsigned)h) atomicMax(&owner[(size_t)y * w + x], e.poly);
-}
-
-// One wave per (polygon, scanline): the crossings of vkp::wave_crossings, spans are painted lane-parallel.
-__global__ void __launch_bounds__(256) k_paint_spans(const PolyEdge *__restrict__ edges,
-                                                     const PaintItem *__restrict__ items, int n_items,
-                                                     int *__restrict__ owner, int h, int w, int *__restrict__ overflow)
-{
-    __shared__ long long xs_all[4][kPaintCross];
-    __shared__ long long sorted_all[4][kPaintCross];
-    __shared__ int count_all[4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int it = blockIdx.x * 4 + wave;
-    const long long *sorted = sorted_all[wave];
-    if (lane == 0) count_all[wave] = 0;
-    __syncthreads();
-    const bool live = it < n_items;
-    PaintItem item = {0, 0, 0, 0};
-    if (live) item = items[it];
-    int n = vkp::wave_crossings(edges, item.edge_begin, item.edge_end, item.y, xs_all[wave], &count_all[wave], lane);
-    if (n > kPaintCross) {
-        if (lane == 0) atomicExch(overflow, 1);
-        n = 0;
+// ---- batched ordered paint: many polygons, later ones win ------------------------------------------------------
+// Several label plane sets painted by one call live in bands of h rows of one ownership raster of `rows` rows: the target of a
+// polygon is its band (its items are clipped to the band on the host, its outline here), its tag the 1-based paint order.
+struct PaintSink {
+    int *owner;
+    int h, w, rows;
+    struct Row {
+        int *p;
+        int w, order;
+        __device__ void operator()(int x) const { atomicMax(&p[x], order); }
+    };
+    __device__ void pixel(const vkp::PolyEdge &e, int x, int y) const
+    {
+        if ((unsigned)x < (unsigned)w && (unsigned)(y - e.pad * h) < (unsigned)h) atomicMax(&owner[(size_t)y * w + x], e.poly);
     }
-    vkp::wave_rank(xs_all[wave], sorted_all[wave], n, lane);
-    if (!live || (unsigned)item.y >= (unsigned)h) return;
-    int *row = owner + (size_t)item.y * w;
-    for (int a = 0; a + 1 < n; a += 2) {
-        long long x1, x2;
-        vkp::span_of(sorted, a, w, x1, x2);
-        for (long long x = x1 + lane; x <= x2; x += 64) atomicMax(&row[x], item.order);
-    }
-}
+    __device__ Row row(const vkp::Item &item) const { return Row{owner + (size_t)item.y * w, (unsigned)item.y < (unsigned)rows ? w : 0, item.tag}; }
+};
 
 // FRESH: the output planes are uninitialised memory -- every pixel is written (0 outside every polygon), so the caller needs no
 // memset of its own.  Either way the owner word is cleared as it is read: the raster is all zero again when the kernel is done and
@@ -178,17 +107,14 @@ static int paint_sets_dev(vkx_ctx *ctx, const vkx_paint_set *sets, int n_sets, i
             total_polys += S.n_polys;
         }
     }
-    VKX_REQUIRE(total_pts < 0x3fffffff, "too many vertices");
+    vkp::Raster<vkp::kPaintCross> raster;
+    VKX_REQUIRE(raster.reserve(total_pts), "too many vertices");
     if (total_polys == 0 && !fresh) return VKX_OK;
-    std::vector<PolyEdge> edges((size_t)total_pts);
-    std::vector<PaintItem> items;
     std::vector<float> values((size_t)total_polys);
-    std::vector<int32_t> shifted;
     PaintOut out;
     memset(&out, 0, sizeof(out));
-    long long steps = 0;
-    bool may_overflow = false, any_values = false;
-    size_t e_base = 0, v_base = 0;
+    bool any_values = false;
+    size_t v_base = 0;
     for (int k = 0; k < n_sets; k++) {
         const vkx_paint_set &S = sets[k];
         out.mask[k] = S.mask; out.mask_stride[k] = S.mask_stride;
@@ -196,31 +122,18 @@ static int paint_sets_dev(vkx_ctx *ctx, const vkx_paint_set *sets, int n_sets, i
         out.value_off[k] = (int)v_base;
         if (S.n_polys == 0) continue;
         const int set_pts = S.poly_offsets_host[S.n_polys];
-        const int y_off = k * h;
-        const int32_t *pts = S.pts_host;
-        if (y_off) {            // the band: the set's vertices moved down by k h rows
-            shifted.resize((size_t)set_pts * 2);
-            for (int i = 0; i < set_pts; i++) { shifted[2 * (size_t)i] = S.pts_host[2 * (size_t)i]; shifted[2 * (size_t)i + 1] = S.pts_host[2 * (size_t)i + 1] + y_off; }
-            pts = shifted.data();
-        }
+        const int y_off = k * h;            // the band: the set's vertices moved down by k h rows
         for (int p = 0; p < S.n_polys; p++) {
             const int b = S.poly_offsets_host[p], e = S.poly_offsets_host[p + 1];
             VKX_REQUIRE(b <= e && e <= set_pts, "bad polygon offsets");
-            may_overflow = may_overflow || e - b > kPaintCross;
             if (b == e) continue;
-            int ymin = INT_MAX, ymax = INT_MIN;
-            build_edges(pts + 2 * (size_t)b, e - b, p + 1, edges.data() + e_base + b, &steps, &ymin, &ymax);
-            VKX_REQUIRE(steps < 0x7fffffff, "polygon outlines too long");
-            for (size_t i = e_base + b; i < e_base + e; i++) edges[i].pad = k;
-            for (int y = std::max(ymin, y_off); y < std::min(ymax, y_off + h); y++)
-                items.push_back(PaintItem{(int)e_base + b, (int)e_base + e, y, p + 1});
+            VKX_REQUIRE(raster.add(S.pts_host + 2 * (size_t)b, e - b, p + 1, k, y_off, y_off + h, 0, y_off), "polygon outlines too long");
         }
         if (S.values_host) { memcpy(values.data() + v_base, S.values_host, sizeof(float) * (size_t)S.n_polys); any_values = true; }
-        e_base += (size_t)set_pts;
         v_base += (size_t)S.n_polys;
     }
     vkx_tables tab(ctx);         // behind the overflow flag's 256 bytes of ctx->misc
-    const size_t e_off = tab.add(sizeof(PolyEdge) * edges.size()), i_off = tab.add(sizeof(PaintItem) * items.size());
+    raster.layout(tab);
     const size_t v_off = tab.add(sizeof(float) * values.size());
     int rc = vkx_scratch_reserve(ctx, &ctx->misc, 256 + vkx_align256(tab.bytes));
     if (rc) return rc;
@@ -231,33 +144,21 @@ static int paint_sets_dev(vkx_ctx *ctx, const vkx_paint_set *sets, int n_sets, i
     if (rc) return rc;
     unsigned char *misc = (unsigned char *)ctx->misc.ptr;
     int *overflow = (int *)misc;
-    PolyEdge *d_edges = (PolyEdge *)(misc + 256 + e_off);
-    PaintItem *d_items = (PaintItem *)(misc + 256 + i_off);
     float *d_values = (float *)(misc + 256 + v_off);
     int *owner = (int *)ctx->paint_owner.ptr;
     // The edge / item / value tables travel through the context's page-locked ring as ONE asynchronous copy: the call returns
     // with its kernels queued (a page paints four label planes: two stream synchronisations and a flag read-back per call were
-    // 0.45 ms of a 2.2 ms page).  A polygon of at most kPaintCross vertices cannot cross a scanline more often than the span
-    // kernel holds, so only calls with larger polygons read the overflow flag back (and synchronise for it).
+    // 0.45 ms of a 2.2 ms page) unless a polygon could overflow (vkp::Raster).
     vkx_device_guard guard(ctx);
     if (tab.bytes) {
         if ((rc = tab.take())) return rc;
-        if (!edges.empty()) memcpy(tab.at<PolyEdge>(e_off), edges.data(), sizeof(PolyEdge) * edges.size());
-        if (!items.empty()) memcpy(tab.at<PaintItem>(i_off), items.data(), sizeof(PaintItem) * items.size());
+        raster.stage(tab);
         if (!values.empty()) memcpy(tab.at<float>(v_off), values.data(), sizeof(float) * values.size());
         if ((rc = tab.copy_to(misc + 256))) return rc;
     }
-    if (may_overflow) VKX_HIP(hipMemsetAsync(overflow, 0, sizeof(int), ctx->stream));      // (only such calls can set it, and only they read it)
     if (ctx->paint_owner_zeroed < owner_bytes) VKX_HIP(hipMemsetAsync(owner, 0, ctx->paint_owner.cap, ctx->stream));
     ctx->paint_owner_zeroed = 0;          // dirty until the resolve kernel of THIS call has been queued (an error exit in between re-zeroes next time)
-    if (steps > 0) {
-        { VKX_TIMED(ctx, "k_paint_outline"); k_paint_outline<<<vkx_blocks((size_t)steps, 256), 256, 0, ctx->stream>>>(d_edges, (int)total_pts, (int)steps, owner, h, w); }
-        VKX_LAUNCH_CHECK();
-    }
-    if (!items.empty()) {
-        { VKX_TIMED(ctx, "k_paint_spans"); k_paint_spans<<<vkx_blocks(items.size(), 4), 256, 0, ctx->stream>>>(d_edges, d_items, (int)items.size(), owner, h * n_sets, w, overflow); }
-        VKX_LAUNCH_CHECK();
-    }
+    if ((rc = raster.launch(ctx, misc + 256, overflow, PaintSink{owner, h, w, h * n_sets}, "k_paint_outline", "k_paint_spans", false))) return rc;
     {
         dim3 grid(vkx_blocks(w, 64), vkx_blocks(h, 4), n_sets);
         VKX_TIMED(ctx, "k_paint_resolve");
@@ -266,15 +167,7 @@ static int paint_sets_dev(vkx_ctx *ctx, const vkx_paint_set *sets, int n_sets, i
         VKX_LAUNCH_CHECK();
         ctx->paint_owner_zeroed = ctx->paint_owner.cap;
     }
-    if (!may_overflow) return VKX_OK;
-    int flag = 0;
-    VKX_HIP(hipMemcpyAsync(&flag, overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    VKX_HIP(hipStreamSynchronize(ctx->stream));
-    if (flag) {
-        vkx_set_error("a polygon has more than %d edge crossings on one scanline", kPaintCross);
-        return VKX_ERR_UNSUPPORTED;
-    }
-    return VKX_OK;
+    return raster.finish(ctx, overflow, "a polygon");
 }
 
 static int paint_polys_dev(vkx_ctx *ctx, const int32_t *pts_host, const int32_t *poly_offsets_host, int n_polys,
@@ -343,38 +236,25 @@ VKX_EXPORT int vkx_fill_poly_mask_u8_dev(vkx_ctx *ctx, const int32_t *pts_host, 
     VKX_REQUIRE(ctx && pts_host && mask, "NULL argument");
     VKX_REQUIRE(npts > 0 && h > 0 && w > 0, "bad shape");
     VKX_REQUIRE_PITCH(stride, w, h);
-    std::vector<PolyEdge> edges((size_t)npts);
-    long long steps = 0;
-    int ymin = INT_MAX, ymax = INT_MIN;
     for (int i = 0; i < npts; i++) {
         const int xb = pts_host[2 * i], yb = pts_host[2 * i + 1];
         VKX_REQUIRE(xb >= 0 && xb < w && yb >= 0 && yb < h, "polygon vertex outside the mask");
     }
-    build_edges(pts_host, npts, 0, edges.data(), &steps, &ymin, &ymax);
-    VKX_REQUIRE(steps < 0x7fffffff, "polygon outline too long");
-    const size_t ebytes = sizeof(PolyEdge) * edges.size();
-    int rc = vkx_scratch_reserve(ctx, &ctx->misc, ebytes + 256);
+    vkp::Raster<vkp::kPolyCross> raster;
+    VKX_REQUIRE(raster.reserve(npts), "too many vertices");
+    VKX_REQUIRE(raster.add(pts_host, npts, 0, 0), "polygon outline too long");
+    vkx_tables tab(ctx);         // behind the overflow flag's 256 bytes of ctx->misc
+    raster.layout(tab);
+    int rc = vkx_scratch_reserve(ctx, &ctx->misc, 256 + vkx_align256(tab.bytes));
     if (rc) return rc;
     unsigned char *misc = (unsigned char *)ctx->misc.ptr;
     int *overflow = (int *)misc;
-    PolyEdge *d_edges = (PolyEdge *)(misc + 256);
-    VKX_HIP(hipMemsetAsync(overflow, 0, sizeof(int), ctx->stream));
-    VKX_HIP(hipMemcpyAsync(d_edges, edges.data(), ebytes, hipMemcpyHostToDevice, ctx->stream));
-    VKX_HIP(hipStreamSynchronize(ctx->stream)); // `edges` lives on this frame
-    { VKX_TIMED(ctx, "k_poly_outline"); k_poly_outline<<<vkx_blocks((size_t)steps, 256), 256, 0, ctx->stream>>>(d_edges, npts, (int)steps, mask, h, w, stride); }
-    VKX_LAUNCH_CHECK();
-    if (ymin < ymax) {
-        { VKX_TIMED(ctx, "k_poly_spans"); k_poly_spans<<<ymax - ymin, 256, 0, ctx->stream>>>(d_edges, npts, ymin, mask, h, w, stride, overflow); }
-        VKX_LAUNCH_CHECK();
-        int flag = 0;
-        VKX_HIP(hipMemcpyAsync(&flag, overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        VKX_HIP(hipStreamSynchronize(ctx->stream));
-        if (flag) {
-            vkx_set_error("polygon has more than %d edge crossings on one scanline", kMaxCross);
-            return VKX_ERR_UNSUPPORTED;
-        }
-    }
-    return VKX_OK;
+    vkx_device_guard guard(ctx);
+    if ((rc = tab.take())) return rc;
+    raster.stage(tab);
+    if ((rc = tab.copy_to(misc + 256))) return rc;
+    if ((rc = raster.launch(ctx, misc + 256, overflow, ByteSink{mask, h, w, stride}, "k_poly_outline", "k_poly_spans", false))) return rc;
+    return raster.finish(ctx, overflow, "polygon");
 }
 
 // Host-memory variant: zero-initialised mask of shape [h, w] with the polygon set to 1.

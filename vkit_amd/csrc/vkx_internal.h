@@ -303,6 +303,18 @@ __device__ __forceinline__ int reflect101(int p, int len)
     } while ((unsigned)p >= (unsigned)len);
     return p;
 }
+// The last of n >= 1 entries whose prefix is <= t: prefix(i) ascending, prefix(0) <= t.  (Which tile, edge or char owns item t of
+// a launch laid out by a prefix sum; fused.hip and nprand.hip keep their own copies.)
+template <class Prefix>
+__device__ __forceinline__ int last_at_most(int n, int t, Prefix prefix)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (prefix(mid) <= t) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
 __device__ __forceinline__ int sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 __device__ __forceinline__ int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
