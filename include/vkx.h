@@ -597,8 +597,8 @@ int vkx_np_draw_batch_dev(vkx_ctx *ctx, const vkx_np_job *jobs_host, int n_jobs,
 /* Tile buffer of a VKX_NP_NORMAL_TILES job of n samples: `bytes` in all; a 16-byte header (uint32 tiles, uint32 slot elements,
  * uint64 samples the tiles hold), at table_offset [n_tiles + 1] x (uint32 index of the tile's first sample, uint32 first valid
  * element of its slot), at slots_offset n_tiles slots of slot_elems int16.  Sample i of the plane, with
- * table[t].first <= i < table[t + 1].first, is slot t's element table[t].skip + i - table[t].first; samples i + 1 and i + 2 follow
- * it in the same slot (a slot ends with the first two samples of its successor).  Any output pointer may be NULL. */
+ * table[t].first <= i < table[t + 1].first, is slot t's element table[t].skip + i - table[t].first; samples i + 1 .. i + 3 follow
+ * it in the same slot (a slot ends with the first three samples of its successor).  Any output pointer may be NULL. */
 int vkx_np_tiles_layout(int64_t n, int64_t *n_tiles, int64_t *slot_elems, int64_t *table_offset, int64_t *slots_offset, int64_t *bytes);
 /* dst int16 [n] (device, 8-byte aligned) = the plane a finished tile buffer stands for; asynchronous on the ctx stream */
 int vkx_np_tiles_expand_dev(vkx_ctx *ctx, const void *tiles, int64_t n, int16_t *dst);

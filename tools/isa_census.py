@@ -26,7 +26,7 @@ def phase_table():
              ('unsigned long long ta[CGROUP]', 'C gather'), ('static_assert(CGROUP == 2, "phase D', 'D h-blur'),
              ('// ---- E:', 'E setup + noise load'), ('uint32_t P = epx;', 'E v-blur'),
              ('if (hue_on) P = vkd::hue_shift_packed(lsdiv, lhdiv, lsel, hue_delta, r, g, b);', 'E hue'),
-             ('if (noise || (STREAK && streak_on))', 'E noise add'),
+             ("// channel by channel on the lane's own pixel", 'E noise add (per pixel)'),
              ('// 4 adjacent pixels = 12 bytes', 'E pack + store')]
     table = []
     with open(SRC) as f:
@@ -40,7 +40,10 @@ def phase_table():
     end = next(i for i in range(start, len(lines)) if lines[i].startswith('template <bool STREAK>'))
     table.append((end + 1, 'kernel wrapper'))
     table.sort()
-    return table, (start + 1, end + 1)
+    # the packed noise add is a helper above the tile body: its lines are a phase of their own
+    first = next(i for i, l in enumerate(lines) if 'uint32_t add_noise_u8x4(' in l)
+    last = next(i for i in range(first, len(lines)) if lines[i].startswith('}'))
+    return table, (start + 1, end + 1), (first + 1, last + 1)
 
 
 def classify(op):
@@ -69,7 +72,8 @@ def main():
     m = re.search(r'^(_ZN12_GLOBAL__N_113k_chain_fusedILb0[^:\n]*):', text, re.M)
     body = text[m.start():]
     body = body[:body.index('.end_amdhsa_kernel')]
-    table, (tile_first, tile_last) = phase_table()
+    table, (tile_first, tile_last), (add_first, add_last) = phase_table()
+    table.append((tile_last, 'E noise add (packed)'))       # (listed after the phases of the tile body)
     files = {int(n): name for n, name in re.findall(r'\.file\s+(\d+)\s+"[^"]*"\s+"([^"]+)"', text)}
     files[0] = 'fused.hip'
 
@@ -93,6 +97,8 @@ def main():
                 # div_pair / mad_u24 / helpers above the tile body keep the phase of their caller
                 if tile_first <= line < tile_last:
                     cur = phase_of(line)
+                elif add_first <= line <= add_last:
+                    cur = 'E noise add (packed)'
             elif fname == 'vkx_color.h':
                 cur = 'E hue'
             continue

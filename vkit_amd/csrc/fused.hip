@@ -386,6 +386,26 @@ __device__ __forceinline__ int cvt_i32_sat(float v)
     return r;
 }
 
+// Four channel bytes + their four int16 noise samples (n01 = samples 0 | 1 << 16, n23 = samples 2 | 3 << 16), every sum clipped
+// to 0 .. 255: the bytes as two pairs of 16-bit halves, two packed adds and two packed clips.  The sum is numpy's int16 sum
+// (photometric/noise.py adds the plane to the image as int16): it WRAPS beyond 32767 -- 255 + 32767 comes out as 0 --, so the
+// packed add carries no clamp.
+__device__ __forceinline__ uint32_t add_noise_u8x4(uint32_t px, uint32_t n01, uint32_t n23)
+{
+    typedef unsigned short pk16 __attribute__((ext_vector_type(2)));
+    // (both byte sources the same register: with a constant 0 as the first one the selectors were moved into VGPRs, row by row)
+    pk16 lo = __builtin_bit_cast(pk16, __builtin_amdgcn_perm(px, px, 0x0c010c00u));
+    pk16 hi = __builtin_bit_cast(pk16, __builtin_amdgcn_perm(px, px, 0x0c030c02u));
+    lo += __builtin_bit_cast(pk16, n01);
+    hi += __builtin_bit_cast(pk16, n23);
+    // (the compiler has no pattern for the packed clip: as v_pk_max_i16 + v_pk_min_i16 it took four instructions and two moves of
+    //  the {255, 255} constant per row; vector operands only)
+    uint32_t lo8, hi8;       // two clipped bytes each, in bits 0 .. 15
+    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(lo8) : "v"(__builtin_bit_cast(uint32_t, lo)));
+    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(hi8) : "v"(__builtin_bit_cast(uint32_t, hi)));
+    return __builtin_amdgcn_perm(hi8, lo8, 0x05040100u);
+}
+
 // INTERIOR: the tile's whole 64 x 64 window lies inside the image and its candidates fit one LDS chunk -- the common
 // case (about 89 % of the tiles of a 2048^2 page).  Border handling (row / column validity, BORDER_REFLECT_101 lane tables,
 // the global-memory fallback for candidates beyond the chunk) compiles away; the arithmetic is the same.
@@ -898,10 +918,13 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
 
     }
 
-    // ---- E: vertical pass, hue shift, noise, store.  Wavefront w takes output rows w, w + 8, ...
-    // This wavefront's output rows are cy = wave + 8 i, column = lane - R.  All their noise (exactly 6 bytes per
-    // pixel: a dword + a short) is requested up front, so eight rows of HBM latency overlap; asking earlier (before
-    // phase A) would pin 16 VGPRs through the register-heavy phases and spill.
+    // ---- E: vertical pass, hue shift, pack, noise, store.  Wavefront w takes output rows w, w + 8, ...
+    // This wavefront's output rows are cy = wave + 8 i, column = lane - R.  All their noise is requested up front, so
+    // eight rows of HBM latency overlap; asking earlier (before phase A) would pin 16 VGPRs through the register-heavy
+    // phases and spill.  Without the streak stage the noise is added to the PACKED row: of a whole 4-pixel group (12
+    // channel bytes = 3 dwords, built by the lanes with (column & 3) < 3) a lane fetches the 4 int16 samples of the dword
+    // it stores with one 8-byte load, and the fourth lane of the group fetches nothing.  The ragged tail columns of a
+    // border tile and the streak instance fetch the 3 samples of the lane's own pixel (a dword + a short: exactly 6 bytes).
     // The descriptor fields only this phase needs are read here, through a pointer the optimiser cannot trace back:
     // hoisted to the top of the kernel they would sit in SGPRs through phases A - D and spill.
     // (a global-address-space pointer: no FLAT instruction anywhere in this kernel -- flat loads tick both memory counters
@@ -921,30 +944,43 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
         if (nrows_here) *(u32x2 *)(lnrow + 2 * nrow_y) = nrec;
         if (tiled) __syncthreads();
     }
-    const uint32_t k3 = (uint32_t)(ocx * 3);
+    const int full4 = (tw >> 2) << 2;          // columns covered by whole 4-pixel (12-byte) groups
+    // whole groups: the lane's dword of its 4-pixel group = row samples g4 .. g4 + 3 (row bytes g4 .. g4 + 3 of the tile)
+    const bool grouped = !STREAK && (INTERIOR || ocx < full4);
+    const uint32_t g4 = (uint32_t)((ocx >> 2) * 12 + (ocx & 3) * 4);
+    const uint32_t k3 = grouped ? g4 : (uint32_t)(ocx * 3);      // the first sample this lane fetches
+    const bool nlane = ocol && !(grouped && (ocx & 3) == 3);
     u32x2 nrow = {0u, 0u};           // lane r < 8: the parked record of this wavefront's row r
     if (tiled) nrow = *(const u32x2 *)(lnrow + 2 * (wave + NWAVES * (lane & 7)));
 #pragma unroll
     for (int i = 0; i < ROWS_PER_WAVE; i++) {
         nzA[i] = 0; nzB[i] = 0;
         const int cy = wave + NWAVES * i;
-        if (noise && ocol && cy < th) {
+        if (noise && nlane && cy < th) {
             const int16_t VKX_GLOBAL *np_;
             if (tiled) {
-                // (the row's base is a scalar: the loads take it as their SGPR base, the lane's 6 ocx bytes as the offset)
+                // (the row's base is a scalar: the loads take it as their SGPR base, the lane's sample offset as the offset)
                 const int16_t VKX_GLOBAL *rowp = noise + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)nrow.x, i);
                 const uint32_t sd = (uint32_t)__builtin_amdgcn_readlane((int)nrow.y, i);
                 uint32_t off = k3;
                 if ((sd & 0xffffu) < 3u * W) {       // the row runs into the next generator tile (6 % of the rows)
                     asm volatile("" ::: "memory");   // (a real branch: as a select the common rows would pay for the rare ones)
+                    // a fetch that begins before the boundary stays in this slot: it ends at most three samples past it, and a
+                    // slot ends with the first three samples of its successor (k_np_tiles_finish)
                     off += k3 >= (sd & 0xffffu) ? (uint32_t)((int)sd >> 16) : 0u;
                 }
                 np_ = rowp + off;
             } else {
-                np_ = noise + (ptrdiff_t)(y0 + cy) * nstride + (ptrdiff_t)(x0 + ocx) * 3;
+                np_ = noise + (ptrdiff_t)(y0 + cy) * nstride + (ptrdiff_t)x0 * 3 + (ptrdiff_t)k3;
             }
-            nzA[i] = *(const u32_u1 VKX_GLOBAL *)np_;
-            nzB[i] = *(const u16_u1 VKX_GLOBAL *)(np_ + 2);
+            if (grouped) {
+                const unsigned long long v = *(const u64_u1 VKX_GLOBAL *)np_;
+                nzA[i] = (uint32_t)v;
+                nzB[i] = (uint32_t)(v >> 32);
+            } else {
+                nzA[i] = *(const u32_u1 VKX_GLOBAL *)np_;
+                nzB[i] = *(const u16_u1 VKX_GLOBAL *)(np_ + 2);
+            }
         }
     }
     // vertical taps two at a time: the tile row cy = wave + 8 i has the parity of the wavefront, so the pairing of the taps
@@ -959,8 +995,7 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
     const bool hue_on = __builtin_amdgcn_readfirstlane(ite.hue_on) != 0;
     const int hue_delta = __builtin_amdgcn_readfirstlane(ite.hue_delta);
     const int right4 = min(lane + 1, 63) << 2;       // ds_bpermute address of the right-hand neighbour
-    const uint32_t dcol4 = (uint32_t)(x0 * 3 + (ocx >> 2) * 12 + (ocx & 3) * 4);   // this lane's dword of a 4-pixel group
-    const int full4 = (tw >> 2) << 2;          // columns covered by whole 4-pixel (12-byte) groups
+    const uint32_t dcol4 = (uint32_t)(x0 * 3) + g4;  // this lane's dword of a 4-pixel group
     const bool streak_on = STREAK && ite.streak_on != 0;
     const int sxm = streak_on ? (x0 + ocx) % ite.streak_step : 0;        // this lane's column phase in the stripe period
     const int sxd = streak_on ? (x0 + ocx) % ite.streak_dash_step : 0;
@@ -1020,12 +1055,15 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
                                                       (int)((P >> 16) & 0xff));
             }
         }
-        if (noise || (STREAK && streak_on)) {
+        // channel by channel on the lane's own pixel: the streak instance, and the ragged tail columns of a border tile (no lane
+        // of a whole group takes its right-hand neighbour from among them)
+        if ((STREAK || !INTERIOR) && ((noise && !grouped) || (STREAK && streak_on))) {
             int r = (int)(P & 0xff), g = (int)((P >> 8) & 0xff), b = (int)((P >> 16) & 0xff);
             if (noise) {
-                r = vkd::clamp_u8(r + (int)(int16_t)(nzA[i] & 0xffff));
-                g = vkd::clamp_u8(g + (int)(int16_t)(nzA[i] >> 16));
-                b = vkd::clamp_u8(b + (int)(int16_t)(nzB[i] & 0xffff));
+                // (the int16 sum of the reference: it wraps beyond 32767, as in add_noise_u8x4)
+                r = vkd::clamp_u8((int)(int16_t)(r + (int)(nzA[i] & 0xffff)));
+                g = vkd::clamp_u8((int)(int16_t)(g + (int)(nzA[i] >> 16)));
+                b = vkd::clamp_u8((int)(int16_t)(b + (int)(nzB[i] & 0xffff)));
             }
             if (STREAK && streak_on) {
                 // stripe masks: vertical x % (t + g) < t, horizontal y % (t + g) < t, dash gaps cut them; vertical stripes
@@ -1058,7 +1096,9 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
             const int m = ocx & 3;
             if (INTERIOR || ocx < full4) {     // an interior tile is whole 4-pixel groups
                 if (m < 3) {
-                    const uint32_t wv = (P >> (8 * m)) | (Pn << (24 - 8 * m));   // one store for all three lanes
+                    uint32_t wv = (P >> (8 * m)) | (Pn << (24 - 8 * m));   // one store for all three lanes
+                    // noise on the packed group: the dword's four channel bytes + the four samples fetched for them
+                    if (!STREAK && noise) wv = add_noise_u8x4(wv, nzA[i], nzB[i]);
                     // dh * dstride < 2^32 (checked on the host): scalar row offset + lane offset on the scalar base
                     const uint32_t off = (uint32_t)gy * (uint32_t)dstride + dcol4;
                     *(u32_u1 VKX_GLOBAL *)(dst + (size_t)off) = wv;

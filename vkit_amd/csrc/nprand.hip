@@ -848,7 +848,8 @@ __global__ void __launch_bounds__(256) k_np_draw(const NpJob *__restrict__ jobs,
 // scatter them is gone: what follows only copies (k_np_apply), or nothing follows at all (VKX_NP_NORMAL_TILES: the chain
 // kernel reads the slots).  kDrawWaves wavefronts share the ziggurat tables: 8 x 9.0 KB + 6 KB per workgroup, two workgroups
 // (16 wavefronts at 112 VGPRs) per CU.
-constexpr int kSlot = kTile + 16;        // elements per slot: the tile's samples, two lent by the next tile, 16-byte group rounding
+constexpr int kSlot = kTile + 16;        // elements per slot: the tile's samples, three lent by the next tile, 16-byte group rounding
+constexpr int kLent = 3;                 // a reader's 4-sample fetch that begins in a tile ends at most three samples into the next
 #ifndef VKX_NP_DRAW_WAVES
 #define VKX_NP_DRAW_WAVES 8
 #endif
@@ -1010,7 +1011,7 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
     for (int j = j0; j < j1; j++) {
         plan[j].prefix = run;
         // consumers of tile buffers assume that a row segment of 64 pixels (192 samples) meets at most two tiles and that a tile
-        // can lend its predecessor two samples: a tile inside the wanted range that yields fewer (of 3 072 draws: never observed,
+        // can lend its predecessor three samples: a tile inside the wanted range that yields fewer (of 3 072 draws: never observed,
         // ~1e-3000) hands the stream to the host like any other refusal
         short_tile = short_tile || ((long long)run < job.n && j + 1 < T && plan[j].count < 192u);
         run += plan[j].count;
@@ -1323,8 +1324,9 @@ __global__ void __launch_bounds__(256) k_np_tiles_expand(const uint2 *__restrict
 }
 
 // VKX_NP_NORMAL_TILES, after the walk: one lane per tile writes the tile's table entry (index of its first sample, first valid
-// slot element) and lends the tile the first two samples of its successor, so that the three samples of a pixel never
-// straddle two slots; the job's last tile also writes the sentinel entry and the header.
+// slot element) and lends the tile the first three samples of its successor, so that neither the three samples of a pixel nor
+// the four samples of a packed dword of the chain kernel straddle two slots; the job's last tile also writes the sentinel
+// entry and the header.
 __global__ void __launch_bounds__(256) k_np_tiles_finish(const NpJob *__restrict__ jobs, const TileInfo *__restrict__ info,
                                                          const TilePlan *__restrict__ plan)
 {
@@ -1344,8 +1346,11 @@ __global__ void __launch_bounds__(256) k_np_tiles_finish(const NpJob *__restrict
     if (t + 1 < job.n_tiles) {
         const TilePlan pn = plan[tile + 1];
         const int16_t *nxt = rec + kSlot + skip_of(tile + 1, pn);
-        rec[skip + p.count] = nxt[0];
-        rec[skip + p.count + 1] = nxt[1];
+        // skip + count <= kTile (a raw draw yields at most one sample), so the lent samples end inside the slot; the successor
+        // holds at least three samples of its own wherever the plane goes on (the prefix scan flags a tile below 192)
+        static_assert(kLent <= 16 && kSlot >= kTile + kLent, "a slot has room for its tile's samples and the lent ones");
+#pragma unroll
+        for (int k = 0; k < kLent; k++) rec[skip + p.count + k] = nxt[k];
     } else {
         job.table[t + 1] = make_uint2((uint32_t)(p.prefix + p.count), 0u);
         uint32_t *header = (uint32_t *)job.table - 4;
