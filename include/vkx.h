@@ -17,9 +17,13 @@
  *     uint8 planes and in ELEMENTS for float32 / int16 / int32 planes (`*_stride_el`).  A stride is at least
  *     one row (width x channels); a shorter or negative one is VKX_ERR_INVALID before anything is launched, except
  *     on a single-row plane, whose stride is never used.  This holds for stride arguments and for the planes of
- *     vkx_elem, vkx_layer(_f32), vkx_paint_set and vkx_noise_plane; vkx_chain_item has limits of its own.  Entry points that cannot run in place (resize, remap, warps, blurs and
- *     filter2d, gather, the JPEG round trip, zoom_in_blur, channel-count conversions, the channel permutation)
- *     refuse a source and destination whose byte ranges overlap.
+ *     vkx_elem, vkx_layer(_f32), vkx_paint_set, vkx_noise_plane and vkx_chain_item (src_stride, dst_stride, and noise_stride_el
+ *     of a plane noise).  Entry points that cannot run in place (resize, remap, warps, blurs and
+ *     filter2d, gather, the JPEG round trip, zoom_in_blur, channel-count conversions, the channel permutation, the chain: the
+ *     src and dst of one vkx_chain_item) refuse a source and destination whose byte ranges overlap.  The chain checks every
+ *     item of a batch before it queues anything.  What remains particular to vkx_chain_item: the fused kernel takes a source
+ *     pitch below 2^24 bytes and planes whose byte offsets fit 32 bits (sh * src_stride + 8 and dh * dst_stride up to 2^32 - 1);
+ *     items beyond that run through the per-stage kernels, with the same pixels.
  *   - Integer and byte results are bit-exact with oracle/ (the CPU restatement of the
  *     reference's numpy/OpenCV arithmetic); float32 results (ScoreMap) are bit-exact too,
  *     the stated tolerance against cv2 itself is 2 ulp.

@@ -12,6 +12,12 @@ its cases compare every layout with the dense host call, a differential check (t
 the dense path to the oracle).  Every plane sits between guards of more than a row plus 4 KB: bytes of a
 source outside its window are random, so a kernel that reads outside gives other values; bytes of a destination outside
 its window are 0xA5 and must stay so.  Source planes must come back unchanged.
+
+Entry points whose strides travel in descriptor structs (chain items, remap elements, layers, paint sets, noise planes) are
+DescCase cases: the same layouts and schedules, one group per plane a descriptor names, and every run checks that the
+descriptors it passed carried the strides of those layouts.  The chain cases run the fused kernel (whole 4-pixel groups,
+ragged tails of 1, 2 and 3 columns, streak instance, remap alone, tiled noise drawn in the same call) and the staged kernels
+(a 9-tap blur, which the fused plan declines) on laid-out sources, destinations and noise planes, two items per call.
 """
 import ctypes
 import os
@@ -112,10 +118,13 @@ class Case:
     """name, entry point (without _dev), planes {name: (data or None, shape, dtype, role)}, call(fn, P) -> rc or
     (rc, host outputs), want {plane or output name: array}."""
 
-    def __init__(self, name, entry, planes, call, want, layouts=LAYOUTS, groups=None, refuse=None, host=False):
+    def __init__(self, name, entry, planes, call, want, layouts=LAYOUTS, groups=None, refuse=None, host=False, extra=(),
+                 dev_name=None):
         self.name, self.entry, self.planes, self.call, self.want = name, entry, planes, call, want
         self.layouts, self.host, self.refuse = layouts, host, refuse or {}
         self.groups = groups or [(n,) for n in planes if not planes[n][3].startswith('fixed')]
+        self.extra = [dict(e) for e in extra]             # further schedules {group: layout}
+        self.dev_name = dev_name or entry + '_dev'        # the device entry point (vkx_fill_u8_dev_host_layers has no host twin)
 
     def schedules(self):
         dense = {g: 'dense' for g in self.groups}
@@ -129,6 +138,47 @@ class Case:
             rot = self.layouts[1:]
             yield {g: rot[i % len(rot)] for i, g in enumerate(self.groups)}
             yield {g: (rot[(i + 2) % len(rot)] if i else 'dense') for i, g in enumerate(self.groups)}
+        for e in self.extra:
+            yield {**dense, **e}
+
+
+class DescCase(Case):
+    """A case of an entry point whose strides travel in descriptor structs (vkx_chain_item, vkx_elem, vkx_layer(_f32),
+    vkx_paint_set, vkx_noise_plane).  `descriptors` {struct name of vkx.h: [{stride field: plane name} per record]} states which
+    plane's layout each strided field of each record takes; the call hands the arrays it passes to note(), and run() checks
+    that every stated field holds the stride of its plane's layout.  tests/stride_table.py descriptor_gaps() counts such a case
+    as coverage of its entry point only if the stated fields are all the strided fields of the struct."""
+
+    def __init__(self, *a, descriptors, **k):
+        super().__init__(*a, **k)
+        self.descriptors = descriptors
+
+    def unlaid(self, notes, bufs):
+        problems = []
+        seen = dict(notes)
+        for struct, records in self.descriptors.items():
+            arr = seen.get(struct)
+            if arr is None or len(arr) != len(records):
+                problems.append(f'{struct}: the call noted {None if arr is None else len(arr)} records, the case states {len(records)}')
+                continue
+            for i, fields in enumerate(records):
+                for f, plane in fields.items():
+                    if int(getattr(arr[i], f)) != bufs[plane].stride:
+                        problems.append(f'{struct}[{i}].{f} = {getattr(arr[i], f)} is not the stride of {plane} ({bufs[plane].stride})')
+        return problems
+
+
+_NOTES, _AFTER = [], []
+
+
+def note(struct, array):
+    """a call states the descriptor array it passes (DescCase)"""
+    _NOTES.append((struct, array))
+
+
+def after(fn):
+    """a call leaves work for after the synchronisation: fn() -> list of problems (frees, flags and timings to read)"""
+    _AFTER.append(fn)
 
 
 def run(ctx, rng, case, sched, host=False, fn=None):
@@ -138,14 +188,23 @@ def run(ctx, rng, case, sched, host=False, fn=None):
             lay[n] = lname
     bufs = {}
     for n, (data, shape, dtype, role) in case.planes.items():
-        bufs[n] = Buf(ctx, rng, data, shape, dtype, 'in' if role == 'fixed' else role, lay.get(n, 'dense'), host=host)
+        data = data.value() if isinstance(data, _Later) else data
+        shape = tuple(v.value() if isinstance(v, _Later) else v for v in shape)      # (a tile buffer's size comes from the library)
+        # 'host_in': a plane the DEVICE entry point reads from host memory (the layers of vkx_fill_u8_dev_host_layers)
+        bufs[n] = Buf(ctx, rng, data, shape, dtype, 'in' if role in ('fixed', 'host_in') else role, lay.get(n, 'dense'),
+                      host=host or role == 'host_in')
     if fn is None:
-        fn = getattr(__import__('vkit_amd._native', fromlist=['lib']).lib(), case.entry + ('' if host else '_dev'))
+        fn = getattr(__import__('vkit_amd._native', fromlist=['lib']).lib(), case.entry if host else case.dev_name)
+    del _NOTES[:], _AFTER[:]
     res = case.call(fn, bufs)
     rc, outs = (res if isinstance(res, tuple) else (res, {}))
-    if not host:
-        ctx.sync()
+    ctx.sync()
     results, problems = dict(outs), []
+    for hook in list(_AFTER):
+        problems += hook() or []
+    if isinstance(case, DescCase):
+        problems += case.unlaid(_NOTES, bufs)
+    del _NOTES[:], _AFTER[:]
     for n, b in bufs.items():
         got, pr = b.finish()
         problems += [f'{n}: {p}' for p in pr]
@@ -277,7 +336,7 @@ def build_cases():
     u8, f32, i16, i32 = np.uint8, np.float32, np.int16, np.int32
 
     def add(*a, **k):
-        cases.append(Case(*a, **k))
+        cases.append(DescCase(*a, **k) if 'descriptors' in k else Case(*a, **k))
 
     # ---- resize: every interpolation code, uint8 1 / 3 / 4 channels and float32, both ways, the exact half, integer area
     small = [((37, 53), (29, 41)), ((37, 53), (61, 83)), ((38, 54), (19, 27)), ((36, 54), (12, 18)), ((5, 70), (3, 9))]
@@ -470,7 +529,9 @@ def build_cases():
         for c in range(4):
             L.value_const[c] = 17 * (c + 3)
         L.mode = 0
+        note('vkx_layer', arr)
         return arr
+    two_layers = [{'mask_stride': 'm0', 'value_stride': 'v0'}, {'alpha_stride_el': 'a1'}]
 
     for cn in (1, 3, 4):
         h, w = 61, 97
@@ -486,7 +547,12 @@ def build_cases():
                   'a1': (a1, a1.shape, f32, 'in')}
         add(f'fill_u8 cn{cn}', 'vkx_fill_u8', planes,
             lambda fn, P, cn=cn, b0=b0, b1=b1, h=h, w=w: fn(H, P['dst'].p, h, w, cn, P['dst'].stride, u8_layers(P, cn, (b0, b1)), 2),
-            {'dst': want}, host=(cn == 3))
+            {'dst': want}, host=(cn == 3), descriptors={'vkx_layer': two_layers})
+        # the same composite with the layer planes in HOST memory, gathered by the entry point itself
+        add(f'fill_u8 host layers cn{cn}', 'vkx_fill_u8_dev_host_layers',
+            {**planes, **{n: planes[n][:3] + ('host_in',) for n in ('m0', 'v0', 'a1')}},
+            lambda fn, P, cn=cn, b0=b0, b1=b1, h=h, w=w: fn(H, P['dst'].p, h, w, cn, P['dst'].stride, u8_layers(P, cn, (b0, b1)), 2),
+            {'dst': want}, dev_name='vkx_fill_u8_dev_host_layers', descriptors={'vkx_layer': two_layers})
         if cn == 3:
             base2 = _img(rng, h, w, cn)
             want2 = later(_filled, O, base2, fills)
@@ -495,11 +561,14 @@ def build_cases():
                 layers = (N.VkxLayer * 4)()
                 two = u8_layers(P, 3, (b0, b1))
                 layers[0], layers[1], layers[2], layers[3] = two[0], two[1], two[0], two[1]
+                del _NOTES[:]
+                note('vkx_layer', layers)
                 dsts = (ctypes.c_void_p * 2)(P['dst'].p, P['dst2'].p)
                 begin = np.array([0, 2, 4], np.int32)
                 return fn(H, dsts, 2, h, w, 3, P['dst'].stride, layers, begin.ctypes.data)
             add('fill_u8_batch', 'vkx_fill_u8_batch', {**planes, 'dst2': (base2, base2.shape, u8, 'inout')}, batch,
-                {'dst': want, 'dst2': want2}, groups=[('dst', 'dst2'), ('m0',), ('v0',), ('a1',)])
+                {'dst': want, 'dst2': want2}, groups=[('dst', 'dst2'), ('m0',), ('v0',), ('a1',)],
+                descriptors={'vkx_layer': two_layers * 2})
     hf, wf = 50, 70
     basef = rng.random((hf, wf), dtype=np.float32)
     bf = (4, 9, 30, 41)
@@ -515,9 +584,11 @@ def build_cases():
         L[0].alpha, L[0].alpha_stride_el, L[0].alpha_scalar = P['a'].p, P['a'].stride, 1.0
         L[0].value, L[0].value_stride_el = P['v'].p, P['v'].stride
         L[0].mode = 0
+        note('vkx_layer_f32', L)
         return fn(H, P['dst'].p, hf, wf, P['dst'].stride, L, 1)
     add('fill_f32', 'vkx_fill_f32', {'dst': (basef, basef.shape, f32, 'inout'), 'm': (mf, mf.shape, u8, 'in'),
-                                     'a': (af, af.shape, f32, 'in'), 'v': (vf, vf.shape, f32, 'in')}, fill_f32, {'dst': wantf})
+                                     'a': (af, af.shape, f32, 'in'), 'v': (vf, vf.shape, f32, 'in')}, fill_f32, {'dst': wantf},
+        descriptors={'vkx_layer_f32': [{'mask_stride': 'm', 'alpha_stride_el': 'a', 'value_stride_el': 'v'}]})
 
     # ---- streaks (in place)
     for cn in (1, 3, 4):
@@ -605,7 +676,339 @@ def build_cases():
         add(f'cvt_color {code}', 'vkx_cvt_color_u8', {'src': (src, src.shape, u8, 'in'), 'dst': (None, out_shape, u8, 'out')},
             lambda fn, P, code=code, h=h, w=w: fn(H, P['src'].p, h, w, P['src'].stride, code, P['dst'].p, P['dst'].stride),
             {'dst': want}, host=(code in (4, 5)))
+    _descriptor_cases(add, N, O, H)
     return cases
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# entry points whose planes travel in descriptors or that paint: the chain, the multi-element remaps, the grid map, the polygon
+# raster and paint, the batched noise planes
+
+CHAIN_ENTRIES = ('vkx_chain_rgb_batch_dev', 'vkx_chain_rgb_batch_np_dev')
+CHAIN_GRIDS = ((150, 171, 40), (131, 158, 41), (121, 112, 42))      # synthetic_grid(h, w, 16, 5.0, seed); the third: a 1-column tail
+CHAIN_PAIRS = ((0, 1), (2, 0))                                      # the two items of a call
+NP_STD = 11.0
+# name -> blur ksize, hue, noise ('plane' / 'tiles' / None), streak, runs in k_chain_fused, blur radius of the fused plan
+CHAIN_VARIANTS = {
+    'grouped': (5, True, 'plane', False, True, 2),          # phase E on packed 4-pixel groups
+    'streak': (5, True, 'plane', True, True, 2),            # streak instance: per-pixel phase E
+    'remap only': (0, False, None, False, True, 0),
+    # vkx_gaussian_blur_u8_dev takes 9 taps (the 'gaussian_blur cn3 130x257 k9' case); the fused plan stops at 7 (RMAX, fused.hip)
+    'blur9 staged': (9, True, 'plane', False, False, None),
+    'np tiles': (5, True, 'tiles', False, True, 2),
+}
+
+
+def tile_census(dv, dshape, radius):
+    """(interior, border) tiles of a result that hold lattice cells, as k_chain_setup bins them for a blur of `radius`
+    (test_gpu_chain_noise_groups._tile_census with the tile side of the radius: the 64-pixel window minus the halo, in whole
+    4-pixel groups), and the columns of the ragged tail of the last tile column."""
+    side = (64 - 2 * radius) & ~3
+    dh, dw = dshape
+    tiles_y, tiles_x = -(-dh // side), -(-dw // side)
+    reached = np.zeros((tiles_y, tiles_x), bool)
+    quads = np.stack([dv[:-1, :-1], dv[:-1, 1:], dv[1:, 1:], dv[1:, :-1]], 2).reshape(-1, 4, 2)
+    for q in quads:
+        xmin, xmax, ymin, ymax = int(q[:, 0].min()), int(q[:, 0].max()), int(q[:, 1].min()), int(q[:, 1].max())
+        tx0, ty0 = max(xmin - radius, 0) // side, max(ymin - radius, 0) // side
+        tx1, ty1 = min((xmax + radius) // side, tiles_x - 1), min((ymax + radius) // side, tiles_y - 1)
+        if tx0 <= tx1 and ty0 <= ty1:
+            reached[ty0:ty1 + 1, tx0:tx1 + 1] = True
+    interior = border = 0
+    for ty in range(tiles_y):
+        for tx in range(tiles_x):
+            wx0, wy0 = tx * side - radius, ty * side - radius
+            inside = wx0 >= 0 and wy0 >= 0 and wx0 + 64 <= dw and wy0 + 64 <= dh
+            interior += bool(reached[ty, tx] and inside)
+            border += bool(reached[ty, tx] and not inside)
+    return interior, border, (dw % side) & 3
+
+
+_CHAIN = None
+
+
+def chain_inputs():
+    """per lattice of CHAIN_GRIDS: source image, vertices, result shape, the extreme-value noise plane, and the seed of its stream"""
+    global _CHAIN
+    if _CHAIN is None:
+        from test_gpu_parity import synthetic_grid
+        from test_gpu_chain_noise_groups import _extreme_plane
+        rng = np.random.default_rng(20261018)
+        _CHAIN = []
+        for k, (h, w, seed) in enumerate(CHAIN_GRIDS):
+            sv, dv, dshape = synthetic_grid(h, w, 16, 5.0, seed=seed)
+            _CHAIN.append(dict(image=rng.integers(0, 256, (h, w, 3), dtype=np.uint8), sv=sv, dv=dv, dshape=dshape,
+                               plane=_extreme_plane(tuple(dshape) + (3,), k), seed=9100 + k))
+    return _CHAIN
+
+
+_CHAIN_WANT = {}
+
+
+def chain_want(O, g, variant):
+    """the oracle chain remap -> gaussian_blur -> color_shift_rgb -> add_noise_i16 -> line_streak of lattice g"""
+    key = (g, variant)
+    if key not in _CHAIN_WANT:
+        c = chain_inputs()[g]
+        ksize, hue, noise, streak, _fused, _r = CHAIN_VARIANTS[variant]
+        if ('remap', g) not in _CHAIN_WANT:
+            _CHAIN_WANT['remap', g] = O.remap(c['image'], *O.grid_to_map(c['sv'], c['dv'], c['dshape']))
+        out = _CHAIN_WANT['remap', g]
+        if ksize > 1:
+            if ('hued', g, ksize) not in _CHAIN_WANT:
+                _CHAIN_WANT['hued', g, ksize] = O.color_shift_rgb(O.gaussian_blur(out, ksize, 1.0), 37)
+            out = _CHAIN_WANT['hued', g, ksize]
+        if noise == 'plane':
+            out = O.add_noise_i16(out, c['plane'])
+        elif noise == 'tiles':
+            shape = tuple(c['dshape']) + (3,)
+            out = O.add_noise_i16(out, np.round(np.random.default_rng(c['seed']).normal(0, NP_STD, shape)).astype(np.int16))
+        if streak:
+            out = O.line_streak(out, 2, 9, 3, 5, (10, 200, 30), 0.6, True, True)
+        _CHAIN_WANT[key] = out
+    return _CHAIN_WANT[key]
+
+
+def tiles_bytes(n):
+    """bytes of the tile buffer of a VKX_NP_NORMAL_TILES job of n samples (vkx_np_tiles_layout: no device needed)"""
+    from vkit_amd import _native as N
+    return N.np_tiles_layout(n)[4]
+
+
+def chain_planes(pair, variant, noise_kinds=None):
+    """the planes of a chain call on the lattices `pair`: s / d / n (plane noise) / t (tile buffer, dense by definition) per item"""
+    noise = CHAIN_VARIANTS[variant][2]
+    planes = {}
+    for i, g in enumerate(pair):
+        c = chain_inputs()[g]
+        dh, dw = c['dshape']
+        kind = noise_kinds[i] if noise_kinds else noise
+        planes[f's{i}'] = (c['image'], c['image'].shape, np.uint8, 'in')
+        planes[f'd{i}'] = (None, (dh, dw, 3), np.uint8, 'out')
+        if kind == 'plane':
+            planes[f'n{i}'] = (c['plane'], (dh, dw, 3), np.int16, 'in')
+        elif kind == 'tiles':
+            planes[f't{i}'] = (None, (1, _Later(tiles_bytes, dh * dw * 3)), np.uint8, 'fixed_out')
+        planes[f'sv{i}'] = (c['sv'], c['sv'].shape, np.int32, 'fixed')
+        planes[f'dv{i}'] = (c['dv'], c['dv'].shape, np.int32, 'fixed')
+    return planes
+
+
+def chain_call(fn, P, pair, variant, with_jobs=False, check_kernel=True):
+    """vkx_chain_rgb_batch_dev(items) or vkx_chain_rgb_batch_np_dev(items, jobs): one item per lattice of `pair`, its noise
+    whatever planes P holds for it (n: a plane, t: a tile buffer with its job)"""
+    from vkit_amd import _native as N
+    ksize, hue, _noise, streak, fused, _r = CHAIN_VARIANTS[variant]
+    arr = (N.VkxChainItem * len(pair))()
+    jobs = []
+    for i, g in enumerate(pair):
+        c = chain_inputs()[g]
+        it = arr[i]
+        it.src, it.dst, it.src_stride, it.dst_stride = P[f's{i}'].p, P[f'd{i}'].p, P[f's{i}'].stride, P[f'd{i}'].stride
+        it.sh, it.sw = c['image'].shape[:2]
+        it.dh, it.dw = c['dshape']
+        it.src_vertices, it.dst_vertices = P[f'sv{i}'].p, P[f'dv{i}'].p
+        it.rows, it.cols = c['sv'].shape[:2]
+        if f'n{i}' in P:
+            it.noise, it.noise_stride_el = P[f'n{i}'].p, P[f'n{i}'].stride
+        elif f't{i}' in P:
+            it.noise, it.noise_tiled = P[f't{i}'].p, 1
+            jobs.append(N.np_job(N.NP_NORMAL_TILES, N.np_stream(np.random.default_rng(c['seed'])), it.dh * it.dw * 3, NP_STD,
+                                 dst=P[f't{i}'].p))
+        it.blur_sigma, it.blur_ksize = 1.0, ksize
+        it.hue_delta, it.hue_enabled = 37, int(hue)
+        if streak:
+            it.streak_enabled, it.streak_thickness, it.streak_gap, it.streak_dash_thickness, it.streak_dash_gap = 1, 2, 9, 3, 5
+            it.streak_enable_vert = it.streak_enable_hori = 1
+            it.streak_color[0], it.streak_color[1], it.streak_color[2] = 10, 200, 30
+            it.streak_alpha = 0.6
+    note('vkx_chain_item', arr)
+    ctx = N.default_ctx()
+    ctx.set_timing(1)
+    ctx.reset_timings()
+    if with_jobs:
+        job_arr = (N.VkxNpJob * len(jobs))(*jobs)
+        results = (N.VkxNpResult * len(jobs))()
+        rc = fn(_Handle(), arr, len(pair), job_arr, len(jobs), results)
+    else:
+        rc = fn(_Handle(), arr, len(pair))
+
+    def done():
+        launches = {name: count for name, (_ms, count) in ctx.timings().items() if count}
+        ctx.set_timing(0)
+        problems = []
+        if rc == 0 and check_kernel and ('k_chain_fused' in launches) != fused:
+            problems.append(f'k_chain_fused {"did not run" if fused else "ran"}: {sorted(launches)}')
+        if rc == 0 and with_jobs:
+            problems += [f'stream {k} was flagged {results[k].flags}' for k in range(len(jobs)) if results[k].flags]
+        return problems
+    after(done)
+    return rc
+
+
+POLY_H, POLY_W = 24, 40
+# two overlapping quads, a bow tie, one polygon leaving the plane on each side (vertices at negative coordinates and beyond
+# w / h), one wholly outside, one empty
+POLYGONS = {
+    'quad a': [(3, 2), (20, 3), (18, 14), (4, 12)], 'quad b': [(10, 6), (30, 8), (28, 20), (12, 18)],
+    'bow tie': [(22, 2), (36, 12), (36, 2), (22, 12)],
+    'left': [(-6, 5), (5, 4), (6, 10), (-4, 12)], 'right': [(34, 14), (47, 13), (45, 20), (35, 19)],
+    'top': [(14, -5), (20, -4), (21, 3), (13, 4)], 'bottom': [(5, 18), (12, 19), (11, 30), (4, 28)],
+    'outside': [(50, 30), (60, 30), (60, 40), (50, 40)], 'empty': [],
+}
+
+
+def poly_tables(names):
+    """(points int32 [n, 2], offsets int32 [len + 1], values float32 [len]) of the polygons `names`, in that order"""
+    pts = np.array([p for n in names for p in POLYGONS[n]], np.int32).reshape(-1, 2)
+    offs = np.cumsum([0] + [len(POLYGONS[n]) for n in names]).astype(np.int32)
+    values = (np.arange(len(names), dtype=np.float32) * 1.75 + 2.5).astype(np.float32)
+    return pts, offs, values
+
+
+def paint_want(names, base_mask=None, base_score=None):
+    """test_gpu_composite._paint_reference (the oracle's fill_poly over each polygon's own box, clipped, the last one wins)
+    over the given planes, or over zeros (the fresh entry points)"""
+    from test_gpu_composite import _paint_reference
+    _pts, _offs, values = poly_tables(names)
+    live = [(np.array(POLYGONS[n], np.int32), values[k]) for k, n in enumerate(names) if POLYGONS[n]]
+    if live:
+        mask, score = _paint_reference((POLY_H, POLY_W), [p for p, _v in live], [v for _p, v in live])
+    else:
+        mask, score = np.zeros((POLY_H, POLY_W), np.uint8), np.zeros((POLY_H, POLY_W), np.float32)
+    painted = mask == 1
+    if base_mask is not None:
+        mask = np.where(painted, 1, base_mask).astype(np.uint8)
+    if base_score is not None:
+        score = np.where(painted, score, base_score).astype(np.float32)
+    return mask, score
+
+
+def _descriptor_cases(add, N, O, H):
+    from test_gpu_parity import synthetic_grid
+    rng = np.random.default_rng(20261019)
+    u8, f32, i16, i32 = np.uint8, np.float32, np.int16, np.int32
+
+    # ---- chain items: every variant on both pairs of lattices; the two items take different layouts in the mixed schedules
+    for variant, (_ksize, _hue, noise, _streak, _fused, _radius) in CHAIN_VARIANTS.items():
+        for pair in CHAIN_PAIRS:
+            tiles = noise == 'tiles'
+            records = [{'src_stride': f's{i}', 'dst_stride': f'd{i}', **({'noise_stride_el': f'n{i}'} if noise == 'plane' else {})}
+                       for i in range(2)]
+            add(f'chain {variant} {pair[0]}+{pair[1]}', 'vkx_chain_rgb_batch_np' if tiles else 'vkx_chain_rgb_batch',
+                chain_planes(pair, variant),
+                lambda fn, P, pair=pair, variant=variant, tiles=tiles: chain_call(fn, P, pair, variant, with_jobs=tiles),
+                {f'd{i}': later(chain_want, O, g, variant) for i, g in enumerate(pair)}, layouts=PAGE,
+                descriptors={'vkx_chain_item': records})
+
+    # ---- lattice and map remaps of four elements: uint8 x1 / x3 / x4 and float32 through one lattice (result 109 x 142: 2 x 3 tiles of 64)
+    sh, sw = 100, 130
+    sv, dv, (dh, dw) = synthetic_grid(sh, sw, 16, 5.0, seed=43)
+    assert dh > 64 and dw > 64
+    mats = {'u1': _img(rng, sh, sw, 1), 'u3': _img(rng, sh, sw, 3), 'u4': _img(rng, sh, sw, 4),
+            'f': rng.random((sh, sw), dtype=np.float32) * 4 - 1}
+    maps = later(lambda: O.grid_to_map(sv, dv, (dh, dw), want_owner=True))
+    mx, my, owner = (later(lambda k=k: maps.value()[k]) for k in range(3))
+    planes = {}
+    for n, m in mats.items():
+        planes[f's_{n}'] = (m, m.shape, m.dtype, 'in')
+        planes[f'd_{n}'] = (None, (dh, dw) + m.shape[2:], m.dtype, 'out')
+    lattice = {'sv': (sv, sv.shape, i32, 'fixed'), 'dv': (dv, dv.shape, i32, 'fixed')}
+
+    def elems(P):
+        arr = (N.VkxElem * len(mats))()
+        for e, (n, m) in zip(arr, mats.items()):
+            e.src, e.dst, e.src_stride, e.dst_stride = P[f's_{n}'].p, P[f'd_{n}'].p, P[f's_{n}'].stride, P[f'd_{n}'].stride
+            e.cn, e.is_f32 = _cn(m), int(m.dtype == np.float32)
+        note('vkx_elem', arr)
+        return arr
+    records = [{'src_stride': f's_{n}', 'dst_stride': f'd_{n}'} for n in mats]
+    want = {f'd_{n}': later(lambda m=m: O.remap(m, mx.value(), my.value())) for n, m in mats.items()}
+    add('grid_remap four elements', 'vkx_grid_remap', {**planes, **lattice},
+        lambda fn, P: fn(H, elems(P), len(mats), sh, sw, P['sv'].p, P['dv'].p, sv.shape[0], sv.shape[1], dh, dw),
+        want, layouts=PAGE, host=True, descriptors={'vkx_elem': records})
+    add('remap_multi four elements', 'vkx_remap_multi',
+        {**planes, 'mx': (mx, (dh, dw), f32, 'in'), 'my': (my, (dh, dw), f32, 'in')},
+        lambda fn, P: fn(H, elems(P), len(mats), sh, sw, P['mx'].p, P['my'].p, P['mx'].stride, dh, dw),
+        want, layouts=PAGE, host=True, groups=[(n,) for n in planes] + [('mx', 'my')], descriptors={'vkx_elem': records})
+    add('grid_to_map with owner', 'vkx_grid_to_map',
+        {'mx': (None, (dh, dw), f32, 'out'), 'my': (None, (dh, dw), f32, 'out'), 'owner': (None, (dh, dw), i32, 'fixed_out'), **lattice},
+        lambda fn, P: fn(H, P['sv'].p, P['dv'].p, sv.shape[0], sv.shape[1], dh, dw, P['mx'].p, P['my'].p, P['mx'].stride, P['owner'].p),
+        {'mx': mx, 'my': my, 'owner': owner}, layouts=PAGE, host=True, groups=[('mx', 'my')])
+
+    # ---- polygon paint and raster on a 24 x 40 plane
+    h, w = POLY_H, POLY_W
+    names = ['quad a', 'quad b', 'bow tie', 'left', 'empty', 'right', 'top', 'bottom', 'outside']
+    pts, offs, values = poly_tables(names)
+    base_mask = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    base_score = rng.random((h, w), dtype=np.float32) * 9 - 3
+    painted = later(paint_want, names, base_mask, base_score)
+    fresh = later(paint_want, names)
+    add('paint_polys', 'vkx_paint_polys', {'mask': (base_mask, (h, w), u8, 'inout'), 'score': (base_score, (h, w), f32, 'inout')},
+        lambda fn, P: fn(H, pts.ctypes.data, offs.ctypes.data, len(names), values.ctypes.data, P['mask'].p, P['mask'].stride,
+                         P['score'].p, P['score'].stride, h, w),
+        {'mask': later(lambda: painted.value()[0]), 'score': later(lambda: painted.value()[1])}, layouts=PAGE, host=True)
+    for what in ('mask', 'score', 'both'):
+        planes = {n: (None, (h, w), t, 'out') for n, t in (('mask', u8), ('score', f32)) if what in (n, 'both')}
+
+        def paint_fresh(fn, P):
+            m, s = P.get('mask'), P.get('score')
+            return fn(H, pts.ctypes.data, offs.ctypes.data, len(names), values.ctypes.data, m.p if m else None, m.stride if m else 0,
+                      s.p if s else None, s.stride if s else 0, h, w)
+        add(f'paint_polys_fresh {what}', 'vkx_paint_polys_fresh', planes, paint_fresh,
+            {n: later(lambda k=k: fresh.value()[k]) for k, n in enumerate(('mask', 'score')) if n in planes}, layouts=PAGE)
+    # three sets in the bands of one ownership raster: set 0 leaves its band at the bottom, set 1 (mask only) at the top, set 2
+    # has no polygon; neither may show in its neighbour
+    set_names = (['quad a', 'bottom', 'right', 'quad b'], ['top', 'bow tie', 'empty', 'left'], [])
+    set_tables = [poly_tables(n) for n in set_names]
+    set_planes = {'m0': (None, (h, w), u8, 'out'), 's0': (None, (h, w), f32, 'out'), 'm1': (None, (h, w), u8, 'out'),
+                  'm2': (None, (h, w), u8, 'out'), 's2': (None, (h, w), f32, 'out')}
+
+    def paint_sets(fn, P):
+        arr = (N.VkxPaintSet * 3)()
+        for k, (S, (p, o, v)) in enumerate(zip(arr, set_tables)):
+            S.n_polys = len(set_names[k])
+            if S.n_polys:
+                S.pts_host, S.poly_offsets_host, S.values_host = p.ctypes.data, o.ctypes.data, v.ctypes.data
+            S.mask, S.mask_stride = P[f'm{k}'].p, P[f'm{k}'].stride
+            if f's{k}' in P:
+                S.score, S.score_stride_el = P[f's{k}'].p, P[f's{k}'].stride
+        note('vkx_paint_set', arr)
+        return fn(H, arr, 3, h, w)
+    set_want = [later(paint_want, n) for n in set_names]
+    add('paint_poly_sets_fresh three sets', 'vkx_paint_poly_sets_fresh', set_planes, paint_sets,
+        {n: later(lambda n=n: set_want[int(n[1])].value()[n[0] == 's']) for n in set_planes}, layouts=PAGE,
+        descriptors={'vkx_paint_set': [{'mask_stride': 'm0', 'score_stride_el': 's0'}, {'mask_stride': 'm1'},
+                                       {'mask_stride': 'm2', 'score_stride_el': 's2'}]})
+    # the raster itself ORs into a 0 / 1 plane; vertices inside the mask (vkx.h): a polygon touching all four borders, a single
+    # point in the last corner, a horizontal segment on the last row.  The last case starts from zeros: the host form overwrites.
+    sparse = (rng.random((h, w)) < 0.1).astype(np.uint8)
+    for what, poly, base, host in (('four borders', [(0, 5), (20, 0), (w - 1, 12), (15, h - 1)], sparse, False),
+                                   ('corner point', [(w - 1, h - 1)], sparse, False),
+                                   ('last row segment', [(5, h - 1), (30, h - 1)], sparse, False),
+                                   ('four borders from zeros', [(0, 5), (20, 0), (w - 1, 12), (15, h - 1)], np.zeros((h, w), u8), True)):
+        pp = np.array(poly, np.int32)
+        add(f'fill_poly_mask {what}', 'vkx_fill_poly_mask_u8', {'mask': (base, (h, w), u8, 'inout')},
+            lambda fn, P, pp=pp: fn(H, pp.ctypes.data, len(pp), P['mask'].p, h, w, P['mask'].stride),
+            {'mask': later(lambda pp=pp, base=base: base | O.fill_poly((h, w), pp))}, layouts=PAGE, host=host)
+
+    # ---- the planes of a noise batch: sample counts 3, 1, 2 and 0 mod 4, the first over three workgroups, the third a single
+    # row; a dense plane must be 8-byte aligned (vkx.h), so the offset layouts are refusals
+    shapes = ((61, 45, 3), (21, 33, 1), (1, 38, 3), (8, 11, 4))
+    seeds = (5, 2 ** 40 + 7, 2 ** 63 + 11, 77)
+
+    def noise_batch(fn, P):
+        arr = (N.VkxNoisePlane * len(shapes))()
+        for k, (pl, shape) in enumerate(zip(arr, shapes)):
+            pl.dst, pl.stride_el, (pl.h, pl.w, pl.cn), pl.seed = P[f'p{k}'].p, P[f'p{k}'].stride, shape, seeds[k]
+        note('vkx_noise_plane', arr)
+        return fn(H, arr, len(shapes), 12.5)
+    add('noise_normal_i16_batch four planes', 'vkx_noise_normal_i16_batch', {f'p{k}': (None, s, i16, 'out') for k, s in enumerate(shapes)},
+        noise_batch, {f'p{k}': later(lambda s=s, seed=seed: O.noise_normal_i16(s, 12.5, seed).reshape(s))
+                      for k, (s, seed) in enumerate(zip(shapes, seeds))},
+        layouts=PAGE, refuse={f'p{k}': ('off1', 'off3') for k in range(len(shapes))},
+        extra=[{('p0',): 'pad', ('p1',): 'roi', ('p2',): 'pad'}, {('p0',): 'roi', ('p2',): 'roi', ('p3',): 'pad'}],
+        descriptors={'vkx_noise_plane': [{'stride_el': f'p{k}'} for k in range(len(shapes))]})
 
 
 _CASES = None
@@ -640,11 +1043,12 @@ def pytest_generate_tests(metafunc):
 @pytest.mark.gpu
 def test_table_matches_stride_table():
     """every device entry point tests/stride_table.py claims has a case, and every host entry point a host case"""
-    entries = {c.entry + '_dev' for c in cases().values()}
+    entries = {c.dev_name for c in cases().values()}
     hosts = {c.entry for c in cases().values() if c.host}
     assert T.COVERED_DEV <= entries, sorted(T.COVERED_DEV - entries)
     assert T.COVERED_HOST <= hosts, sorted(T.COVERED_HOST - hosts)
-    assert {'vkx_' + e for e in _BAD} == T.REFUSAL_TESTED
+    assert {'vkx_' + e for e in _BAD} | set(CHAIN_ENTRIES) == T.REFUSAL_TESTED
+    assert not T.descriptor_gaps(cases().values())
 
 
 @pytest.mark.gpu
@@ -846,4 +1250,73 @@ def test_raster_and_multi_element_entry_points_refuse_bad_strides(entry):
                 failures.append(f'[{bad}={lay}] rc {rc}, expected VKX_ERR_INVALID')
             if written:
                 failures.append(f'[{bad}={lay}] planes written: {written}')
+    assert not failures, f'{entry}:\n' + '\n'.join(failures)
+
+
+# ---- the chain: what its lattices exercise, and the refusals of its items
+
+def test_chain_lattices_hold_interior_and_border_tiles_and_every_tail():
+    """the three lattices of the chain cases, for the 5-tap plan (tile side 60) and the plan without blur (64): interior and
+    border tiles in each, and ragged tails of 1, 2 and 3 columns among them (3 * dw is 2, 1 and 3 mod 4)"""
+    for radius in sorted({v[5] for v in CHAIN_VARIANTS.values() if v[4]}):
+        tails = set()
+        for c in chain_inputs():
+            interior, border, tail = tile_census(c['dv'], c['dshape'], radius)
+            assert interior >= 1 and border >= 1, (radius, c['dshape'], interior, border)
+            tails.add(tail)
+        assert tails == {1, 2, 3}, (radius, tails)
+    assert [c['dshape'] for c in chain_inputs()[:2]] == [(161, 186), (141, 171)]
+    assert {3 * c['dshape'][1] % 4 for c in chain_inputs()} == {1, 2, 3}
+
+
+def _chain_refusal_bufs(ctx, rng, planes, layouts, guard_min=None):
+    return {n: Buf(ctx, rng, d.value() if isinstance(d, _Later) else d, tuple(v.value() if isinstance(v, _Later) else v for v in shape),
+                   t, 'in' if r == 'fixed' else ('inout' if n in (guard_min or {}) else r), layouts.get(n, 'dense'),
+                   guard_min=(guard_min or {}).get(n, 0))
+            for n, (d, shape, t, r) in planes.items()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('entry', CHAIN_ENTRIES)
+def test_chain_items_refuse_bad_strides_and_overlap(entry):
+    """src, dst and the plane noise of the SECOND item in turn with a stride one element short of the row, and negative, then a
+    second item whose dense dst ends inside its src's first row: VKX_ERR_INVALID, and no byte of any plane written -- the
+    first item has not run, and with vkx_chain_rgb_batch_np_dev (whose first item takes the tile buffer of a stream job)
+    nothing was drawn either"""
+    from vkit_amd import _native as N
+    with_jobs = entry.endswith('_np_dev')
+    pair, variant = CHAIN_PAIRS[0], 'grouped'
+    planes = chain_planes(pair, variant, noise_kinds=('tiles' if with_jobs else 'plane', 'plane'))
+    fn = getattr(N.lib(), entry)
+    ctx = N.default_ctx()
+    rng = np.random.default_rng(6)
+    failures = []
+
+    def attempt(tag, bufs, P):
+        del _NOTES[:], _AFTER[:]
+        rc = chain_call(fn, P, pair, variant, with_jobs=with_jobs, check_kernel=False)
+        ctx.sync()
+        for hook in list(_AFTER):
+            hook()
+        del _NOTES[:], _AFTER[:]
+        for b in bufs.values():
+            b.finish()
+        written = [n for n, b in bufs.items() if not b.untouched]
+        if rc != VKX_ERR_INVALID:
+            failures.append(f'[{tag}] rc {rc}, expected VKX_ERR_INVALID')
+        if written:
+            failures.append(f'[{tag}] planes written: {written}')
+    for bad in ('s1', 'd1', 'n1'):
+        for lay in ('short', 'neg'):
+            bufs = _chain_refusal_bufs(ctx, rng, planes, {bad: lay})
+            attempt(f'{bad}={lay}', bufs, bufs)
+    # the construction of test_overlapping_source_and_destination_are_refused on the second item
+    dst_shape = planes['d1'][1]
+    dst_bytes = int(np.prod(dst_shape))
+    bufs = _chain_refusal_bufs(ctx, rng, planes, {}, guard_min={'s1': dst_bytes})
+
+    class Alias:
+        p = bufs['s1'].p + bufs['s1'].row_b - dst_bytes
+        stride = int(np.prod(dst_shape[1:]))
+    attempt('d1 ends in the first row of s1', bufs, dict(bufs, d1=Alias))
     assert not failures, f'{entry}:\n' + '\n'.join(failures)

@@ -14,15 +14,19 @@
 #include <unordered_map>
 #include <vector>
 
-VKX_EXPORT int vkx_chain_rgb_batch_dev(vkx_ctx *ctx, const vkx_chain_item *items, int n_items)
+// Every item of a batch, checked before anything is queued (the draw jobs of vkx_chain_rgb_batch_np_dev included): planes,
+// shapes, the streak parameters, the pitch contract of vkx.h for the source, the destination and a plane noise, and the overlap
+// of an item's source and destination (the chain starts with a remap, which cannot run in place).
+static int chain_check_items(const vkx_chain_item *items, int n_items)
 {
-    VKX_REQUIRE(ctx != nullptr, "ctx is NULL");
-    VKX_REQUIRE(n_items >= 0 && (n_items == 0 || items), "bad item list");
-    size_t max_plane = 0;
     for (int i = 0; i < n_items; i++) {
         const vkx_chain_item &it = items[i];
         VKX_REQUIRE(it.src && it.dst && it.src_vertices && it.dst_vertices, "NULL plane in chain item");
         VKX_REQUIRE(it.sh > 0 && it.sw > 0 && it.dh > 0 && it.dw > 0, "bad shape in chain item");
+        VKX_REQUIRE_PITCH(it.src_stride, (ptrdiff_t)it.sw * 3, it.sh);
+        VKX_REQUIRE_PITCH(it.dst_stride, (ptrdiff_t)it.dw * 3, it.dh);
+        if (it.noise && !it.noise_tiled) VKX_REQUIRE_PITCH(it.noise_stride_el, (ptrdiff_t)it.dw * 3, it.dh);
+        VKX_REQUIRE_DISJOINT(it.src, it.sh, it.src_stride, (size_t)it.sw * 3, it.dst, it.dh, it.dst_stride, (size_t)it.dw * 3);
         if (it.streak_enabled) {
             VKX_REQUIRE(it.streak_thickness + it.streak_gap > 0, "streak thickness + gap must be positive");
             if (it.streak_alpha < 0.0 || it.streak_alpha > 1.0) {
@@ -30,7 +34,18 @@ VKX_EXPORT int vkx_chain_rgb_batch_dev(vkx_ctx *ctx, const vkx_chain_item *items
                 return VKX_ERR_INVALID;
             }
         }
-        const size_t bytes = (size_t)it.dh * it.dw * 3;
+    }
+    return VKX_OK;
+}
+
+VKX_EXPORT int vkx_chain_rgb_batch_dev(vkx_ctx *ctx, const vkx_chain_item *items, int n_items)
+{
+    VKX_REQUIRE(ctx != nullptr, "ctx is NULL");
+    VKX_REQUIRE(n_items >= 0 && (n_items == 0 || items), "bad item list");
+    if (int crc = chain_check_items(items, n_items)) return crc;
+    size_t max_plane = 0;
+    for (int i = 0; i < n_items; i++) {
+        const size_t bytes = (size_t)items[i].dh * items[i].dw * 3;
         if (bytes > max_plane) max_plane = bytes;
     }
     // Preferred: the tile-fused kernel (fused.hip).  VKX_CHAIN_STAGED=1 forces the per-stage kernels (A/B runs).
@@ -130,6 +145,7 @@ VKX_EXPORT int vkx_chain_rgb_batch_np_dev(vkx_ctx *ctx, const vkx_chain_item *it
     if (n_jobs <= 0) return vkx_chain_rgb_batch_dev(ctx, items, n_items);
     int rc = vkx_np_jobs_check(jobs, n_jobs, results_host);
     if (rc) return rc;
+    if ((rc = chain_check_items(items, n_items))) return rc;      // before the draw jobs are queued
     // job -> item by the tile buffer; the jobs of a chunk must be a contiguous run of the job list
     std::unordered_map<const void *, int> item_of;
     for (int i = 0; i < n_items; i++)
@@ -146,18 +162,6 @@ VKX_EXPORT int vkx_chain_rgb_batch_np_dev(vkx_ctx *ctx, const vkx_chain_item *it
     static const int overlap = [] { const char *e = getenv("VKX_CHAIN_OVERLAP"); return e ? atoi(e) : 0; }();
     vkx_chain_plan *raw = nullptr;
     if (pipelined && !staged_only) {
-        for (int i = 0; i < n_items; i++) {      // the checks of vkx_chain_rgb_batch_dev
-            const vkx_chain_item &it = items[i];
-            VKX_REQUIRE(it.src && it.dst && it.src_vertices && it.dst_vertices, "NULL plane in chain item");
-            VKX_REQUIRE(it.sh > 0 && it.sw > 0 && it.dh > 0 && it.dw > 0, "bad shape in chain item");
-            if (it.streak_enabled) {
-                VKX_REQUIRE(it.streak_thickness + it.streak_gap > 0, "streak thickness + gap must be positive");
-                if (it.streak_alpha < 0.0 || it.streak_alpha > 1.0) {
-                    vkx_set_error("alpha=%g is invalid.", it.streak_alpha);
-                    return VKX_ERR_INVALID;
-                }
-            }
-        }
         rc = vkx_chain_plan_build(ctx, items, n_items, &raw);
         if (rc && rc != VKX_ERR_UNSUPPORTED) return rc;
     }

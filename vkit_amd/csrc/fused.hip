@@ -816,7 +816,7 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
                                 } else {
                                     vkd::sample_u8<4>(sp, sh, sw, el.sstride, X[u], Y[u], p4);
                                 }
-                                *(uint32_t VKX_GLOBAL *)d = (uint32_t)p4[0] | ((uint32_t)p4[1] << 8) | ((uint32_t)p4[2] << 16) |
+                                *(u32_u1 VKX_GLOBAL *)d = (uint32_t)p4[0] | ((uint32_t)p4[1] << 8) | ((uint32_t)p4[2] << 16) |
                                                  ((uint32_t)p4[3] << 24);
                             }
                         }
