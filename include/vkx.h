@@ -1066,6 +1066,61 @@ int vkx_region_extend_masks_dev(vkx_ctx *ctx, const vkx_region_masks_rec *region
                                 const uint8_t *text_mask, ptrdiff_t text_mask_step, int page_h, int page_w, uint8_t *dst,
                                 size_t dst_bytes);
 
+/* ---- fill_text_line_to_seal_impression (engine/seal_impression/text_line_slot_filler.py:28-205) --------------------------
+ * vkx_seal_fill_dev builds the text-line score map of EVERY seal impression of a page: three launches whatever the number of
+ * seals and chars, no synchronisation.  The records are HOST tables; the geometry in them (resized width, rotation matrix and
+ * size, destination origin, the out-of-bound skip) is the caller's, every pixel is the call's:
+ *   per char (:73-102) the glyph's score map (float32) resized with cv.resize(interpolation) and clipped to [0, 1]
+ *   (ScoreMap.to_resized_score_map), or -- a glyph without one -- its image (uint8, 1 or 3 channels) as the mask any(image > 0),
+ *   resized as (mask * 255) in uint8 arithmetic and thresholded > 0 (Mask.to_resized_mask); a source whose shape is already
+ *   glyph_h x plane_w is copied as it is.  The result fills rows glyph_up .. of a zero plane of plane_h x plane_w (:78, :88);
+ *   cv.warpAffine(plane, m, (rot_w, rot_h)) (:135-143; bilinear, constant 0 border, pixel for pixel vkx_warp_affine_f32_dev's;
+ *   identity != 0: rotate.distort's nop for an angle of 0, the plane itself), filled at (dst_up, dst_left) of its seal's map
+ *   keeping the maximum (:167-172: `mat < value` replaces, so neither a NaN nor a -0.0 ever does);
+ *   per seal the internal text line's float32 score map, or its uint8 mask plane converted value for value, as a plain
+ *   overwrite of its box after all chars (:181-192), then map * float32(alpha) / max(map) in float32 (:202-203): an all-zero
+ *   map divides 0 by 0 and is NaN throughout, as in the reference.
+ * Interpolations: the five codes a text line samples (VKX_INTER_NEAREST_EXACT, _LINEAR_EXACT, _CUBIC, _LANCZOS4, _AREA); AREA
+ * shrinks only.  A source is a DEVICE plane with its row step in bytes
+ * (the pitch contract of this header: at least one row, unused with a single row), or, with VKX_SEAL_SRC_HOST added to its
+ * kind, a plane inside the HOST block `planes_host`, `src` being its byte offset there: the block travels with the tables as one
+ * staged upload.  The chars of a seal are consecutive in the table (ascending `seal`).  dst: DEVICE float32, `dst_floats` long;
+ * seal i is the dense plane [h][w] at dst_off floats; every element of it is written, dst needs no memset.
+ * Refused (VKX_ERR_INVALID, nothing launched): a NULL pointer, n_chars outside 0 .. 4096, n_seals outside 1 .. 256, a side
+ * outside 1 .. 32767, a row step shorter than its row or negative, glyph rows outside the char plane, a char destination box
+ * or an internal box outside its seal, an unknown interpolation code or source kind, a VKX_INTER_AREA enlargement, a seal
+ * destination outside dst, seal destinations that overlap one another, a device source that overlaps dst, a host source
+ * outside planes_host. */
+#define VKX_SEAL_SRC_F32 0
+#define VKX_SEAL_SRC_U8C1 1
+#define VKX_SEAL_SRC_U8C3 2
+#define VKX_SEAL_SRC_HOST 16
+#define VKX_SEAL_INTERNAL_NONE (-1)
+typedef struct vkx_seal_char {
+    const void *src;                    /* the glyph: float32 [src_h][src_w] or uint8 [src_h][src_w][1 or 3] */
+    int64_t src_step;                   /* bytes */
+    int32_t src_kind;                   /* VKX_SEAL_SRC_* */
+    int32_t src_h, src_w;
+    int32_t glyph_h;                    /* the glyph is resized to glyph_h x plane_w (equal to the source: copied) */
+    int32_t interpolation;              /* VKX_INTER_* */
+    int32_t plane_h, plane_w, glyph_up; /* the char plane (text line height x resized width), the row the glyph starts at */
+    int32_t identity;
+    float m[6];                         /* the forward 2 x 3 matrix of RotateState, row-major */
+    int32_t rot_h, rot_w;               /* the rotated plane */
+    int32_t seal, dst_up, dst_left;     /* its seal and origin there */
+} vkx_seal_char;
+typedef struct vkx_seal_rec {
+    int32_t h, w;
+    int64_t dst_off;                    /* floats */
+    double alpha;
+    const void *internal;               /* the internal text line: float32 score map or uint8 mask plane */
+    int64_t internal_step;              /* bytes */
+    int32_t internal_kind;              /* VKX_SEAL_INTERNAL_NONE, VKX_SEAL_SRC_F32 or VKX_SEAL_SRC_U8C1 (+ VKX_SEAL_SRC_HOST) */
+    int32_t internal_up, internal_left, internal_h, internal_w;
+} vkx_seal_rec;
+int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, int n_chars, const vkx_seal_rec *seals_host, int n_seals,
+                      const void *planes_host, size_t planes_host_bytes, float *dst, size_t dst_floats);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

@@ -1,0 +1,475 @@
+"""vkit_amd.engine.seal_impression on the GPU: fill_text_line_to_seal_impression (csrc/seal_fill.hip) against the goldens of the
+reference's own function and against the numpy restatement, batched against single calls, the C entry point's pitch contract
+and refusals, its launch and synchronisation budget, the ellipse engine's background mask against the goldens, and
+PageAssemblerStep taking seals the reference's way.  Every pixel comparison is exact (float32 as bit patterns, NaN by isnan)."""
+import os
+import sys
+from ctypes import c_void_p
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import seal_impression_restate as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+INDEX, GET = R.golden()
+GOLDEN_ROWS = {row['name']: row for row in INDEX['fills']}
+_restated = {}
+
+
+def restated(name):
+    """the restatement of a shared case, computed once"""
+    if name not in _restated:
+        _restated[name] = R.fill(R.case(name))
+    return _restated[name]
+
+
+amd_items = R.amd_items
+
+
+def polygons_xy(polygons):
+    return [np.array([(p.smooth_x, p.smooth_y) for p in polygon.points], np.float64) for polygon in polygons]
+
+
+def same_polygons(got, want):
+    return len(got) == len(want) and all(a.shape == b.shape and a.tobytes() == b.tobytes() for a, b in zip(got, want))
+
+
+# ---- the public function ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize('device', (False, True), ids=('host', 'device'))
+@pytest.mark.parametrize('name', list(R.CASES))
+def test_public_function_equals_golden_and_restatement(name, device):
+    from vkit_amd.engine.seal_impression import fill_text_line_to_seal_impression
+    row = GOLDEN_ROWS[name]
+    score_map, polygons = fill_text_line_to_seal_impression(*amd_items(R.golden_case(row, GET), device))
+    assert isinstance(score_map.mat, np.ndarray) and score_map.mat.dtype == np.float32 and score_map.is_prob
+    assert R.same_bits(score_map.mat, GET(row['score_map']))
+    assert same_polygons(polygons_xy(polygons), [GET(ref) for ref in row['polygons']])
+    want_map, want_polygons = restated(name)
+    assert R.same_bits(score_map.mat, want_map) and same_polygons(polygons_xy(polygons), want_polygons)
+
+
+@pytest.mark.parametrize('name', list(R.MASK_RESIZE_CASES))
+def test_mask_way_with_a_resize_equals_the_restatement(name):
+    """a glyph without a score map whose mask is resized: (mask * 255) in uint8 arithmetic, > 0, in every interpolation"""
+    from vkit_amd.engine.seal_impression import fill_text_line_to_seal_impression
+    case = R.case(name)
+    score_map, polygons = fill_text_line_to_seal_impression(*amd_items(case))
+    want_map, want_polygons = restated(name)
+    assert R.same_bits(score_map.mat, want_map) and same_polygons(polygons_xy(polygons), want_polygons)
+    assert np.nanmax(want_map) > 0
+
+
+def test_cases_hold_what_they_are_named_for():
+    """the shared cases reach the branches the file is about (on the restatement's own intermediate figures)"""
+    def widths(name):
+        case = R.case(name)
+        out = []
+        for slot_index, line in zip(case['indices'], case['lines']):
+            slot = case['seal']['slots'][slot_index]
+            ref = max(line['chars'], key=lambda c: c['ref_h'])
+            factor = slot['aspect'] / (ref['ref_w'] / ref['ref_h'])
+            for c, s in zip(line['chars'], slot['chars']):
+                out.append((R.char_plan(line, slot, c, s, factor)[0], c))
+        return out
+    assert all(w == 1 for w, _ in widths('width_one'))
+    assert all(w == c['score'].shape[1] and c['score'].shape[0] == c['box'][1] - c['box'][0] + 1 for w, c in widths('copied'))
+    assert any(w != c['score'].shape[1] and c['score'].shape[0] != c['box'][1] - c['box'][0] + 1 for w, c in widths('five_cubic'))
+    assert all(w < c['score'].shape[1] for w, c in widths('five_area'))
+    assert {c['image'].ndim for _, c in widths('mask_way')} == {2, 3} and all(c['score'] is None for _, c in widths('mask_way'))
+    assert all(w != c['image'].shape[1] for name in R.MASK_RESIZE_CASES for w, c in widths(name))
+    # overlapping chars: some pixel is reached by more than one rotated box with a non-zero value
+    case = R.case('overlap')
+    alone = []
+    for k in range(len(case['lines'][0]['chars'])):
+        one = R.make_case(**R.CASES['overlap'])
+        one['lines'][0]['chars'] = [dict(c, score=c['score'] * np.float32(0)) if j != k else c for j, c in enumerate(one['lines'][0]['chars'])]
+        alone.append(R.fill(one)[0] > 0)
+    assert (np.sum(alone, axis=0) > 1).any()
+    # the internal line overwrites pixels the chars had set
+    for name in ('internal_score', 'internal_mask'):
+        case = R.case(name)
+        without = dict(case, internal=None)
+        box = case['seal']['internal_box']
+        assert (R.fill(without)[0][box[0]:box[1] + 1, box[2]:box[3] + 1] > 0).any()
+        assert (case['internal']['score'] is None) == (name == 'internal_mask')
+    assert len(R.case('two_lines_60')['lines']) == 2 and sum(len(line['chars']) for line in R.case('two_lines_60')['lines']) == 60
+
+
+def test_batched_call_equals_single_calls():
+    """two and three seals of different sizes in one call, an all-zero seal and internal lines among them"""
+    from vkit_amd.engine.seal_impression import fill_text_line_to_seal_impression, fill_text_lines_to_seal_impressions
+    for names in (('five_cubic', 'five_lanczos'), ('one_char', 'internal_mask', 'two_lines_60'), ('all_zero', 'internal_score', 'mask_way')):
+        assert len({(R.case(n)['seal']['h'], R.case(n)['seal']['w']) for n in names}) > 1
+        results = fill_text_lines_to_seal_impressions([amd_items(R.case(n)) for n in names])
+        assert len(results) == len(names)
+        for name, (score_map, polygons) in zip(names, results):
+            single_map, single_polygons = fill_text_line_to_seal_impression(*amd_items(R.case(name)))
+            assert R.same_bits(score_map.mat, single_map.mat), name
+            assert same_polygons(polygons_xy(polygons), polygons_xy(single_polygons)), name
+            want_map, want_polygons = restated(name)
+            assert R.same_bits(score_map.mat, want_map), name
+            assert same_polygons(polygons_xy(polygons), want_polygons), name
+    assert fill_text_lines_to_seal_impressions([]) == []
+
+
+def test_resident_mode_keeps_the_score_maps_on_the_device():
+    from vkit_amd import _native as N
+    from vkit_amd.engine.seal_impression import fill_text_lines_to_seal_impressions
+    names = ('five_cubic', 'five_lanczos')
+    with N.resident(True):
+        results = fill_text_lines_to_seal_impressions([amd_items(R.case(n), device=True) for n in names])
+    for name, (score_map, _) in zip(names, results):
+        assert score_map.on_device and score_map.is_prob
+        assert R.same_bits(score_map.mat, restated(name)[0])
+
+
+def test_stops_and_skips_as_the_reference_does(caplog):
+    from vkit_amd.engine.seal_impression import fill_text_line_to_seal_impression
+    import logging
+    for name, message in (('more_chars_than_slots', 'something wrong'), ('slot_index_out_of_range', 'something wrong'),
+                          ('out_of_bound', 'out-of-bound')):
+        caplog.clear()
+        with caplog.at_level(logging.ERROR):
+            _, polygons = fill_text_line_to_seal_impression(*amd_items(R.case(name)))
+        assert len(polygons) == GOLDEN_ROWS[name]['placed'] and message in caplog.text
+
+
+# ---- the C entry point -----------------------------------------------------------------------------------------
+def tables(names, device=True):
+    from vkit_amd.engine.seal_impression.text_line_slot_filler import build_seal_fill_tables
+    return build_seal_fill_tables([amd_items(R.case(n), device=device) for n in names])
+
+
+def raw_call(ctx, chars, seals, planes_host, dst, n_chars=None, n_seals=None, dst_floats=None, chars_ptr=True, seals_ptr=True):
+    from vkit_amd import _native as N
+    planes_host = np.ascontiguousarray(planes_host, np.uint8)
+    return N.lib().vkx_seal_fill_dev(
+        ctx.handle, chars.ctypes.data if chars_ptr and len(chars) else None, len(chars) if n_chars is None else n_chars,
+        seals.ctypes.data if seals_ptr else None, len(seals) if n_seals is None else n_seals,
+        planes_host.ctypes.data if planes_host.size else None, planes_host.size, c_void_p(dst.ptr) if dst is not None else None,
+        dst.size if dst_floats is None else dst_floats)
+
+
+def test_pitch_contract_of_the_entry_point():
+    """device sources laid out with an offset, a padded row step and as a window of a larger plane give the dense layout's bytes"""
+    from vkit_amd import _native as N
+    ctx = N.default_ctx()
+    names = ('five_cubic', 'internal_score', 'mask_way', 'five_lanczos')
+    chars, seals, planes_host, keep, _, floats = tables(names)
+    assert planes_host.size == 0 and len(keep) >= len(chars)
+    dense = ctx.dev_empty((floats,), np.float32)
+    N.seal_fill(chars, seals, dense, planes_host)
+    want = np.array(dense.host())
+    by_ptr = {a.ptr: a for a in keep}
+
+    def relaid(records, field, step_field, layout):
+        held = []
+        out = records.copy()
+        for k in range(len(out)):
+            if field == 'internal' and out[k]['internal_kind'] == N.SEAL_INTERNAL_NONE:
+                continue
+            src = by_ptr[int(out[k][field])]
+            host = np.ascontiguousarray(src.host())
+            row = host.reshape(host.shape[0], -1)              # rows of elements (channels folded in)
+            item = row.dtype.itemsize
+            if layout == 'offset':
+                plane = np.full((row.shape[0] + 2, row.shape[1]), 77, row.dtype)
+                plane[2:] = row
+                at, step = 2 * row.shape[1] * item, row.shape[1] * item
+            elif layout == 'padded':
+                plane = np.full((row.shape[0], row.shape[1] + 5), 77, row.dtype)
+                plane[:, :row.shape[1]] = row
+                at, step = 0, (row.shape[1] + 5) * item
+            else:                                               # a window of a larger plane
+                pad = 3 if row.dtype == np.float32 else 6       # (a whole pixel of a 3-channel row)
+                plane = np.full((row.shape[0] + 3, row.shape[1] + 2 * pad), 77, row.dtype)
+                plane[1:1 + row.shape[0], pad:pad + row.shape[1]] = row
+                step = (row.shape[1] + 2 * pad) * item
+                at = step + pad * item
+            dev = ctx.to_device(plane)
+            held.append(dev)
+            out[k][field], out[k][step_field] = dev.ptr + at, step
+        return out, held
+
+    for layout in ('offset', 'padded', 'window'):
+        chars2, held_a = relaid(chars, 'src', 'src_step', layout)
+        seals2, held_b = relaid(seals, 'internal', 'internal_step', layout)
+        got = ctx.dev_empty((floats,), np.float32)
+        N.seal_fill(chars2, seals2, got, planes_host)
+        assert R.same_bits(np.array(got.host()), want), layout
+        del held_a, held_b
+    # host sources travel in the staged block: the same bytes
+    chars_h, seals_h, planes_h, _, _, _ = tables(names, device=False)
+    assert planes_h.size > 0 and (chars_h['src_kind'] & N.SEAL_SRC_HOST).all()
+    got = ctx.dev_empty((floats,), np.float32)
+    N.seal_fill(chars_h, seals_h, got, planes_h)
+    assert R.same_bits(np.array(got.host()), want)
+    # ... and as stepped planes inside the block: every row padded by 8 bytes
+    chars_p, seals_p, parts, moved, size = chars_h.copy(), seals_h.copy(), [], {}, 0
+    for table, at, step, rows in ((chars_p, 'src', 'src_step', 'src_h'), (seals_p, 'internal', 'internal_step', 'internal_h')):
+        for k in range(len(table)):
+            if table is seals_p and table[k]['internal_kind'] == N.SEAL_INTERNAL_NONE:
+                continue
+            old, row, h = int(table[k][at]), int(table[k][step]), int(table[k][rows])
+            if old not in moved:
+                plane = np.full((h, row + 8), 77, np.uint8)
+                plane[:, :row] = planes_h[old:old + h * row].reshape(h, row)
+                moved[old] = size
+                parts.append(np.pad(plane.reshape(-1), (0, -plane.size % 16)))        # (float32 planes start on 4 bytes)
+                size += parts[-1].size
+            table[k][at], table[k][step] = moved[old], row + 8
+    padded = np.concatenate(parts)
+    N.seal_fill(chars_p, seals_p, got, padded)
+    assert R.same_bits(np.array(got.host()), want)
+    # the last padded row must still lie inside the block
+    last = max(moved.values())
+    sentinel = ctx.to_device(np.full(floats, 5.0, np.float32))
+    assert raw_call(ctx, chars_p, seals_p, padded[:last + 16], sentinel) == -1
+    ctx.sync()
+    assert (np.array(sentinel.host()) == 5.0).all()
+
+
+def test_exact_shrinks_and_integer_area_take_their_own_modes():
+    """raw calls whose sources are exactly twice, or a whole multiple of, the glyph: LINEAR_EXACT on a mask (the 2 x 2 mean of
+    cv.resize), LINEAR_EXACT on float32 (cv.resize routes it to AREA) and AREA with integer factors.  Each equals the call
+    that is handed the oracle's resized plane as a source to copy."""
+    import oracle as O
+    from vkit_amd import _native as N
+    ctx = N.default_ctx()
+    chars, seals, planes_host, keep, _, floats = tables(('five_cubic',))
+    rng = np.random.default_rng(3)
+    for kind, interp, fy, fx in ((N.SEAL_SRC_U8C1, 5, 2, 2), (N.SEAL_SRC_F32, 5, 2, 2), (N.SEAL_SRC_F32, 3, 3, 2), (N.SEAL_SRC_U8C1, 3, 1, 3)):
+        large, small, held = chars.copy(), chars.copy(), []
+        for k in range(len(chars)):
+            gh, pw = int(chars[k]['glyph_h']), int(chars[k]['plane_w'])
+            if kind == N.SEAL_SRC_F32:
+                src = (R.blocky(rng, (fy * gh, fx * pw), 1, 0, 5, np.float32) / np.float32(4)).astype(np.float32)
+                resized = np.clip(O.resize(src, (gh, pw), interp), 0.0, 1.0).astype(np.float32)
+            else:
+                src = R.blocky(rng, (fy * gh, fx * pw), 1, 0, 2, np.uint8) * np.uint8(90)
+                resized = (O.resize((src > 0).astype(np.uint8) * np.uint8(255), (gh, pw), interp) > 0).astype(np.uint8)
+            for table, plane in ((large, src), (small, resized)):
+                dev = ctx.to_device(plane)
+                held.append(dev)
+                table[k]['src'], table[k]['src_step'], table[k]['src_kind'] = dev.ptr, plane.shape[1] * plane.itemsize, kind
+                table[k]['src_h'], table[k]['src_w'], table[k]['interpolation'] = plane.shape[0], plane.shape[1], interp
+        got, want = ctx.dev_empty((floats,), np.float32), ctx.dev_empty((floats,), np.float32)
+        N.seal_fill(large, seals, got, planes_host)
+        N.seal_fill(small, seals, want, planes_host)
+        assert R.same_bits(np.array(got.host()), np.array(want.host())), (kind, interp, fy, fx)
+        assert np.nanmax(np.array(want.host())) > 0
+    del keep
+
+
+def test_abi_refusals():
+    """every refusal of include/vkx.h: VKX_ERR_INVALID and nothing written"""
+    from vkit_amd import _native as N
+    ctx = N.default_ctx()
+    chars, seals, planes_host, keep, _, floats = tables(('five_cubic', 'internal_score'))
+    sentinel = np.full(floats, 123.0, np.float32)
+    dst = ctx.to_device(sentinel)
+    INVALID = -1
+
+    def _download(arr):
+        out = np.empty(arr.shape, arr.dtype)
+        ctx.download(arr.ptr, out)
+        return out
+
+    def refused(c=chars, s=seals, p=planes_host, d=dst, **kw):
+        rc = raw_call(ctx, c, s, p, d, **kw)
+        ctx.sync()
+        return rc == INVALID and _download(dst).tobytes() == sentinel.tobytes()
+
+    def with_char(k=0, **over):
+        c = chars.copy()
+        for key, value in over.items():
+            c[k][key] = value
+        return c
+
+    def with_seal(k=0, **over):
+        s = seals.copy()
+        for key, value in over.items():
+            s[k][key] = value
+        return s
+
+    assert refused(chars_ptr=False) and refused(seals_ptr=False) and refused(d=None, dst_floats=floats)      # NULL pointers
+    assert refused(n_chars=-1) and refused(n_chars=4097)
+    assert refused(n_seals=0) and refused(n_seals=257)
+    assert refused(c=with_char(src=0))
+    for field in ('src_h', 'src_w', 'plane_h', 'plane_w', 'rot_h', 'rot_w', 'glyph_h'):
+        assert refused(c=with_char(**{field: 0})), field
+        assert refused(c=with_char(**{field: 32768})), field
+    assert refused(s=with_seal(h=0)) and refused(s=with_seal(w=32768))
+    assert refused(c=with_char(src_step=int(chars[0]['src_w']) * 4 - 4)) and refused(c=with_char(src_step=-64))
+    internal = int(np.flatnonzero(seals['internal_kind'] != N.SEAL_INTERNAL_NONE)[0])
+    assert refused(s=with_seal(internal, internal_step=int(seals[internal]['internal_w']) * 4 - 4))
+    assert refused(s=with_seal(internal, internal_step=-64))
+    assert refused(c=with_char(dst_up=-1)) and refused(c=with_char(dst_left=int(seals[0]['w']) - int(chars[0]['rot_w']) + 1))
+    assert refused(c=with_char(dst_up=int(seals[0]['h']) - int(chars[0]['rot_h']) + 1))
+    assert refused(s=with_seal(internal, internal_up=int(seals[internal]['h'])))
+    assert refused(c=with_char(interpolation=7)) and refused(c=with_char(interpolation=-1))
+    assert refused(c=with_char(src_kind=3)) and refused(c=with_char(seal=2)) and refused(c=with_char(seal=-1))
+    # an INTER_AREA enlargement
+    assert refused(c=with_char(src_w=1, interpolation=3)) and int(chars[0]['plane_w']) > 1
+    assert refused(c=with_char(src_h=1, src_w=int(chars[0]['plane_w']), interpolation=3)) and int(chars[0]['glyph_h']) > 1
+    # seal destinations outside dst or overlapping
+    assert refused(s=with_seal(1, dst_off=floats - 1)) and refused(s=with_seal(0, dst_off=-1))
+    assert refused(s=with_seal(1, dst_off=int(seals[0]['dst_off']) + 5))
+    assert refused(dst_floats=floats - 1)
+    # a source that overlaps dst
+    assert refused(c=with_char(src=dst.ptr + 64)) and refused(s=with_seal(internal, internal=dst.ptr))
+    # a host source outside the staged block
+    assert refused(c=with_char(src=0, src_kind=N.SEAL_SRC_F32 | N.SEAL_SRC_HOST))
+    # and the unchanged tables still run
+    assert raw_call(ctx, chars, seals, planes_host, dst) == 0
+    ctx.sync()
+    assert _download(dst).tobytes() != sentinel.tobytes()
+    del keep
+
+
+def _count(monkeypatch, ctx, call):
+    from vkit_amd import _native as N
+    syncs = []
+    real = N.Context.sync
+    ctx.sync()
+    with monkeypatch.context() as m:
+        m.setattr(N.Context, 'sync', lambda s: syncs.append(1) or real(s))
+        ctx.set_timing(1)
+        try:
+            ctx.reset_timings()
+            out = call()
+            n_syncs = len(syncs)
+            timings = ctx.timings()
+        finally:
+            ctx.set_timing(0)
+    return out, {name: cnt for name, (_ms, cnt) in timings.items()}, n_syncs
+
+
+def test_launch_and_sync_budget(monkeypatch):
+    """1 char in one seal and 60 chars across 3 seals: the same launches, at most four, no synchronisation"""
+    from vkit_amd import _native as N
+    from vkit_amd.engine.seal_impression import fill_text_lines_to_seal_impressions
+    ctx = N.default_ctx()
+    seen = []
+    with N.resident(True):
+        for names in (('one_char',), ('two_lines_60', 'five_cubic', 'all_zero')):
+            items = [amd_items(R.case(n), device=True) for n in names]
+            fill_text_lines_to_seal_impressions(items)        # warm the scratch slots
+            results, launches, syncs = _count(monkeypatch, ctx, lambda: fill_text_lines_to_seal_impressions(items))
+            seen.append((launches, syncs))
+            for name, (score_map, _) in zip(names, results):
+                assert R.same_bits(score_map.mat, restated(name)[0])
+    assert seen[0] == seen[1] == ({'k_seal_planes': 1, 'k_seal_gather': 1, 'k_seal_scale': 1}, 0), seen
+    assert sum(seen[0][0].values()) <= 4
+
+
+# ---- the ellipse engine ----------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def icon_folder(tmp_path_factory):
+    from PIL import Image as PILImage
+    arrays = dict(np.load(R.GOLDEN + '.npz'))
+    root = tmp_path_factory.mktemp('icons')
+    for name in ('a', 'b'):
+        PILImage.fromarray(arrays['icon_' + name]).save(str(root / (name + '.png')))
+    return str(root)
+
+
+SMALL_RUNS = [run for run in INDEX['runs'] if run['background_mask'] is not None]
+
+
+def test_small_runs_cover_the_branches():
+    assert {tuple(r['shape']) for r in SMALL_RUNS} == {(40, 40), (64, 96), (33, 51)}
+    assert {r['case'] for r in SMALL_RUNS} == {'default', 'thick', 'thick_icon'}
+    assert all(r['border_thickness_empty'] is None for r in SMALL_RUNS if r['case'] == 'default')
+    for shape in ((40, 40), (64, 96), (33, 51)):
+        rows = [r for r in SMALL_RUNS if tuple(r['shape']) == shape]
+        assert any(r['border_thickness_empty'] is not None for r in rows), shape
+        assert any(r['icon_file'] for r in rows) and any(r['with_icon'] and not r['icon_file'] for r in rows), shape
+    assert all(min(r['axes']) >= 1 for r in SMALL_RUNS)
+
+
+@pytest.mark.parametrize('run', SMALL_RUNS, ids=lambda r: f"{r['case']}-{r['shape'][0]}x{r['shape'][1]}-{r['seed']}")
+def test_engine_background_mask_equals_the_golden(run, icon_folder):
+    from numpy.random import default_rng
+    from vkit_amd.engine.seal_impression import seal_impression_ellipse_engine_executor_factory
+    config = dict(run['overrides'])
+    if run['with_icon']:
+        config['icon_image_folders'] = [icon_folder]
+    executor = seal_impression_ellipse_engine_executor_factory.create(config)
+    if run['with_icon']:
+        executor.engine.icon_image_selector.engine.image_files = [os.path.join(icon_folder, 'a.png'), os.path.join(icon_folder, 'b.png')]
+    rng = default_rng(run['seed'])
+    seal = executor.run({'height': run['shape'][0], 'width': run['shape'][1]}, rng)
+    want = GET(run['background_mask'])
+    assert seal.background_mask.mat.dtype == np.uint8 and seal.background_mask.mat.tobytes() == want.tobytes()
+    assert (seal.alpha, list(seal.color)) == (run['alpha'], run['color'])
+    assert rng.bit_generator.state == run['rng_state']
+    box = seal.internal_text_line_box
+    assert (None if box is None else [box.up, box.down, box.left, box.right]) == run['internal_box']
+    assert seal.shape == tuple(run['shape'])
+
+
+# ---- PageAssemblerStep ------------------------------------------------------------------------------------------
+def assembler_input(seals, resources, shape=(96, 128)):
+    from vkit_amd.element import Image
+    from vkit_amd.pipeline.text_detection import page_assembler as T
+    h, w = shape
+    rng = np.random.default_rng(5)
+    background = Image(mat=R.blocky(rng, (h, w), 8, 0, 16, np.uint8)[:, :, None].repeat(3, axis=2) * np.uint8(15))
+    return T.PageAssemblerStepInput(
+        page_layout_step_output=T.PageLayoutStepOutput(T.PageLayout(height=h, width=w)),
+        page_background_step_output=T.PageBackgroundStepOutput(background),
+        page_image_step_output=T.PageImageStepOutput(page_image_collection=T.PageImageCollection(height=h, width=w),
+                                                     page_bottom_layer_image=Image(mat=np.zeros((h, w, 3), np.uint8))),
+        page_barcode_step_output=T.PageBarcodeStepOutput(height=h, width=w),
+        page_text_line_step_output=T.PageTextLineStepOutput(
+            page_text_line_collection=T.PageTextLineCollection(height=h, width=w),
+            page_seal_impression_text_line_collection=T.PageSealImpressionTextLineCollection(
+                height=h, width=w, seal_impressions=seals, seal_impression_resources=resources)),
+        page_non_text_symbol_step_output=T.PageNonTextSymbolStepOutput(),
+        page_text_line_bounding_box_step_output=T.PageTextLineBoundingBoxStepOutput(),
+        page_text_line_label_step_output=T.PageTextLineLabelStepOutput(
+            page_char_polygon_collection=T.PageCharPolygonCollection(height=h, width=w),
+            page_text_line_polygon_collection=T.PageTextLinePolygonCollection(height=h, width=w)))
+
+
+def test_page_assembler_takes_seals_the_references_way():
+    """a 96 x 128 page with two seals given as text lines equals the page given the maps and polygons of the restatement"""
+    from numpy.random import default_rng
+    from vkit_amd.element import Box, Mask, Polygon, ScoreMap
+    from vkit_amd.pipeline.text_detection import page_assembler as T
+    names, angles, origins = ('five_nearest', 'one_char'), (20, 0), ((20, 20), (40, 60))        # 48 x 64 seals
+    new_seals, new_resources, old_seals, old_resources = [], [], [], []
+    for name, angle, (up, left) in zip(names, angles, origins):
+        case = R.case(name)
+        h, w = case['seal']['h'], case['seal']['w']
+        seal, indices, lines, internal = amd_items(case)
+        ring = np.zeros((h, w), np.uint8)
+        ring[2:h - 2, 2:w - 2] = 1
+        ring[6:h - 6, 6:w - 6] = 0
+        seal.background_mask = Mask(mat=ring)
+        box = Box(up=up, down=up + h - 1, left=left, right=left + w - 1)
+        new_seals.append(seal)
+        new_resources.append(T.SealImpressionResource(box=box, angle=angle, text_line_slot_indices=indices, text_lines=lines,
+                                                      internal_text_line=internal))
+        want_map, want_polygons = restated(name)
+        old_seals.append(T.SealImpression(alpha=seal.alpha, color=seal.color, background_mask=Mask(mat=ring.copy())))
+        old_resources.append(T.SealImpressionResource(
+            box=box, angle=angle, text_line_filled_score_map=ScoreMap(mat=want_map.copy()),
+            char_polygons=[Polygon.from_xy_pairs([(float(x), float(y)) for x, y in q]) for q in want_polygons]))
+    step = T.page_assembler_step_factory.create()
+    new_page = step.run(assembler_input(new_seals, new_resources), default_rng(0)).page
+    old_page = step.run(assembler_input(old_seals, old_resources), default_rng(0)).page
+    assert new_page.image.mat.tobytes() == old_page.image.mat.tobytes()
+    background = assembler_input([], []).page_background_step_output.background_image.mat
+    assert new_page.image.mat.tobytes() != background.tobytes()
+    got = polygons_xy(new_page.page_seal_impression_char_polygon_collection.char_polygons)
+    want = polygons_xy(old_page.page_seal_impression_char_polygon_collection.char_polygons)
+    assert got and same_polygons(got, want)
+    # a mixed page: one seal given each way
+    mixed = step.run(assembler_input([new_seals[0], old_seals[1]], [new_resources[0], old_resources[1]]), default_rng(0)).page
+    assert mixed.image.mat.tobytes() == old_page.image.mat.tobytes()
+

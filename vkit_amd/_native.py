@@ -397,6 +397,7 @@ _SIGNATURES['vkx_region_stack_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_vo
 _SIGNATURES['vkx_region_extend_masks_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_ssize, c_int, c_int, c_void_p,
                                               ctypes.c_size_t]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
+_SIGNATURES['vkx_seal_fill_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
 _lib = None
@@ -2614,4 +2615,35 @@ def region_extend_masks(records, points_xy, text_mask, dst, text_mask_step=None)
     check(lib().vkx_region_extend_masks_dev(dst.ctx.handle, records.ctypes.data, len(records), points_xy.ctypes.data,
                                             c_void_p(text_mask.ptr), page_w if text_mask_step is None else int(text_mask_step),
                                             page_h, page_w, c_void_p(dst.ptr), dst.nbytes))
+    dst.invalidate_host()
+
+
+# --------------------------------------------------------------------------------------------------------------
+# fill_text_line_to_seal_impression for every seal of a page (csrc/seal_fill.hip): vkx_seal_char / vkx_seal_rec of include/vkx.h
+# --------------------------------------------------------------------------------------------------------------
+SEAL_SRC_F32, SEAL_SRC_U8C1, SEAL_SRC_U8C3, SEAL_SRC_HOST, SEAL_INTERNAL_NONE = 0, 1, 2, 16, -1
+SEAL_CHAR_DTYPE = np.dtype([('src', np.uint64), ('src_step', np.int64), ('src_kind', np.int32), ('src_h', np.int32),
+                            ('src_w', np.int32), ('glyph_h', np.int32), ('interpolation', np.int32), ('plane_h', np.int32),
+                            ('plane_w', np.int32), ('glyph_up', np.int32), ('identity', np.int32), ('m', np.float32, (6,)),
+                            ('rot_h', np.int32), ('rot_w', np.int32), ('seal', np.int32), ('dst_up', np.int32),
+                            ('dst_left', np.int32)], align=True)
+SEAL_REC_DTYPE = np.dtype([('h', np.int32), ('w', np.int32), ('dst_off', np.int64), ('alpha', np.float64), ('internal', np.uint64),
+                           ('internal_step', np.int64), ('internal_kind', np.int32), ('internal_up', np.int32),
+                           ('internal_left', np.int32), ('internal_h', np.int32), ('internal_w', np.int32)], align=True)
+assert (SEAL_CHAR_DTYPE.itemsize, SEAL_REC_DTYPE.itemsize) == (96, 64)
+
+
+def seal_fill(chars, seals, dst, planes_host=None):
+    """vkx_seal_fill_dev: ``chars`` SEAL_CHAR_DTYPE and ``seals`` SEAL_REC_DTYPE records, ``dst`` the packed float32 DevArray the
+    seals' score maps are written into, ``planes_host`` the uint8 block that the records with SEAL_SRC_HOST address by byte
+    offset.  THREE launches whatever the number of seals and chars, asynchronous."""
+    chars, seals = _records(chars, SEAL_CHAR_DTYPE), _records(seals, SEAL_REC_DTYPE)
+    if dst.dtype != np.float32:
+        raise TypeError('dst must be a float32 DevArray')
+    if planes_host is None:
+        planes_host = np.zeros(0, np.uint8)
+    planes_host = np.ascontiguousarray(planes_host, dtype=np.uint8).reshape(-1)
+    check(lib().vkx_seal_fill_dev(dst.ctx.handle, chars.ctypes.data if len(chars) else None, len(chars), seals.ctypes.data, len(seals),
+                                  planes_host.ctypes.data if planes_host.size else None, planes_host.size, c_void_p(dst.ptr),
+                                  dst.size))
     dst.invalidate_host()

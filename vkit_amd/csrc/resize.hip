@@ -9,6 +9,7 @@
 // sums for float32.  Bound by HBM/L2 reads of the source (each source row is reused by ~4/scale destination rows).
 #include "vkx_internal.h"
 #include "vkx_resize_cubic.h"
+#include "vkx_resize_axes.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -25,6 +26,11 @@ using vkd::AxisTable;
 using vkd::cubic_coeffs;
 using vkd::build_axis;
 using vkd::clip_index;
+using vkd::AxisTable8;
+using vkd::build_axis8;
+using vkd::build_linear_exact_axis;
+using vkd::AreaTab;
+using vkd::build_area_tab;
 
 template <int CN>
 __global__ void __launch_bounds__(256) k_resize_cubic_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
@@ -173,6 +179,8 @@ __global__ void __launch_bounds__(256) k_zoom_finish(const uint8_t *__restrict__
 // ---- the other interpolations PageResizingStep samples (pipeline/text_detection/page_resizing.py:110-181 via
 // utility/opt.py:125-148); arithmetic as restated in oracle/vkx_oracle.c.
 
+}  // namespace
+namespace vkd {   // (declared in vkx_resize_axes.h: seal_fill.hip builds the same tables)
 // interpolateLanczos4 (imgproc): 8 taps s-3 .. s+4
 void lanczos4_coeffs(float x, float c[8])
 {
@@ -195,12 +203,6 @@ void lanczos4_coeffs(float x, float c[8])
     for (int i = 0; i < 8; i++) c[i] *= sum;
 }
 
-struct AxisTable8 {
-    std::vector<int> ofs;
-    std::vector<float> coef;   // [n][8]
-    std::vector<short> icoef;
-};
-
 void build_axis8(int ssize, int dsize, AxisTable8 *t)
 {
     t->ofs.resize(dsize); t->coef.resize((size_t)dsize * 8); t->icoef.resize((size_t)dsize * 8);
@@ -217,6 +219,8 @@ void build_axis8(int ssize, int dsize, AxisTable8 *t)
         }
     }
 }
+}  // namespace vkd
+namespace {
 
 template <int CN>
 __global__ void __launch_bounds__(256) k_resize_lanczos4_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
@@ -294,6 +298,8 @@ __global__ void __launch_bounds__(256) k_resize_nearest_exact(const uint8_t *__r
     for (int c = 0; c < CN; c++) dst[(ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN + c] = p[c];
 }
 
+}  // namespace
+namespace vkd {   // (declared in vkx_resize_axes.h: seal_fill.hip builds the same tables)
 // INTER_LINEAR_EXACT on uint8 (resize_bitExact): per axis (offset, 8.8 weight of the second sample) and the range
 // [mn, mx) of destination indices that interpolate; outside it the first / last source sample is copied
 void build_linear_exact_axis(int ssize, int dsize, std::vector<int> *ofs, std::vector<int> *w1, int *dmin, int *dmax)
@@ -314,6 +320,8 @@ void build_linear_exact_axis(int ssize, int dsize, std::vector<int> *ofs, std::v
     if (mx < mn) mx = mn;
     *dmin = mn; *dmax = mx;
 }
+}  // namespace vkd
+namespace {
 
 template <int CN>
 __global__ void __launch_bounds__(256) k_resize_linear_exact_u8(const uint8_t *__restrict__ src, ptrdiff_t sstride,
@@ -397,13 +405,9 @@ __global__ void __launch_bounds__(256) k_resize_area_fast(const void *__restrict
     }
 }
 
+}  // namespace
+namespace vkd {   // (declared in vkx_resize_axes.h: seal_fill.hip builds the same tables)
 // INTER_AREA, fractional scale (ResizeArea): computeResizeAreaTab's (source index, weight) runs per destination index
-struct AreaTab {
-    std::vector<int> start;    // [dsize + 1] first entry of every destination index
-    std::vector<int> si;
-    std::vector<float> alpha;
-};
-
 void build_area_tab(int ssize, int dsize, double scale, AreaTab *t)
 {
     t->start.assign(dsize + 1, 0); t->si.clear(); t->alpha.clear();
@@ -420,6 +424,8 @@ void build_area_tab(int ssize, int dsize, double scale, AreaTab *t)
     }
     t->start[dsize] = (int)t->si.size();
 }
+}  // namespace vkd
+namespace {
 
 template <int CN, bool F32>
 __global__ void __launch_bounds__(256) k_resize_area(const void *__restrict__ src_, ptrdiff_t sstride, void *__restrict__ dst_, int dh,

@@ -41,6 +41,14 @@ class ScoreMap(LazyMat, Shapable):
         return cls(mat=np.full((height, width), fill_value=value, dtype=np.float32), is_prob=is_prob)
 
     @classmethod
+    def from_unchecked_mat(cls, mat, box: Optional['Box'] = None):
+        """A probability map whose values are taken as they are, as ``assign_mat`` takes them (reference score_map.py: no range
+        check): for a device-resident map, which the check would download, and for one that may hold NaN."""
+        score_map = cls(mat=mat, box=box, is_prob=False)
+        object.__setattr__(score_map, 'is_prob', True)
+        return score_map
+
+    @classmethod
     def from_shapable(cls, shapable: Shapable, value: float = 0.0, is_prob: bool = True):
         return cls.from_shape(shapable.shape, value=value, is_prob=is_prob)
 

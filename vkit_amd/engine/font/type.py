@@ -1,0 +1,148 @@
+"""``CharBox``, ``CharGlyph`` and ``TextLine`` of the reference's font engine (vkit/engine/font/type.py:319-699), reduced to what
+the seal-impression engine and the page assembler read.  They are containers: the arrays come from a font engine that ran
+elsewhere.  ``TextLine`` has the fields of the page assembler's reduced text line (``image``, ``mask``, ``score_map``,
+``glyph_color``, ``box``) and is accepted wherever that one is."""
+from typing import List, Optional, Sequence, Tuple
+
+import attrs
+import numpy as np
+
+from vkit_amd.element import Box, Image, Mask, Polygon, ScoreMap, Shapable
+
+_CV_INTER_CUBIC = 2
+
+
+@attrs.define(frozen=True)
+class CharBox(Shapable):
+    char: str
+    box: Box
+
+    def __attrs_post_init__(self):
+        assert len(self.char) == 1 and not self.char.isspace()
+
+    @property
+    def up(self):
+        return self.box.up
+
+    @property
+    def down(self):
+        return self.box.down
+
+    @property
+    def left(self):
+        return self.box.left
+
+    @property
+    def right(self):
+        return self.box.right
+
+    @property
+    def height(self):
+        return self.box.height
+
+    @property
+    def width(self):
+        return self.box.width
+
+    def to_shifted_char_box(self, offset_y: int = 0, offset_x: int = 0):
+        return attrs.evolve(self, box=self.box.to_shifted_box(offset_y=offset_y, offset_x=offset_x))
+
+
+@attrs.define
+class CharGlyph:
+    image: Image
+    score_map: Optional[ScoreMap]
+    # the size of the font's reference char: what a char polygon is widened to
+    ref_char_height: int
+    ref_char_width: int
+
+    @property
+    def height(self):
+        return self.image.height
+
+    @property
+    def width(self):
+        return self.image.width
+
+    def get_glyph_mask(self, box: Optional[Box] = None, enable_resize: bool = False, cv_resize_interpolation: int = _CV_INTER_CUBIC):
+        """``image > 0`` (any channel of an LCD glyph), resized to ``box`` if allowed and attached to it (reference :423-451)."""
+        mat = self.image.mat
+        if mat.ndim == 2:
+            np_mask = mat > 0
+        elif mat.ndim == 3:
+            np_mask = np.any(mat > 0, axis=2)
+        else:
+            raise NotImplementedError()
+        mask = Mask(mat=np_mask.astype(np.uint8))
+        if box:
+            if mask.shape != box.shape:
+                assert enable_resize
+                mask = mask.to_resized_mask(resized_height=box.height, resized_width=box.width,
+                                            cv_resize_interpolation=cv_resize_interpolation)
+            mask = mask.to_box_attached(box)
+        return mask
+
+
+@attrs.define
+class TextLine:
+    image: Image
+    mask: Mask
+    score_map: Optional[ScoreMap]
+    char_boxes: Sequence[CharBox]
+    # NOTE: char_glyphs might not have the same shapes as char_boxes.
+    char_glyphs: Sequence[CharGlyph]
+    cv_resize_interpolation: int
+    is_hori: bool
+    glyph_color: Tuple[int, int, int] = (0, 0, 0)
+    # a shifted text line is bound to a page
+    shifted: bool = False
+
+    @property
+    def box(self):
+        assert self.mask.box
+        return self.mask.box
+
+    def to_shifted_text_line(self, offset_y: int = 0, offset_x: int = 0):
+        self.shifted = True          # (the reference marks the line it was called on, :484)
+        return attrs.evolve(
+            self,
+            image=self.image.to_shifted_image(offset_y=offset_y, offset_x=offset_x),
+            mask=self.mask.to_shifted_mask(offset_y=offset_y, offset_x=offset_x),
+            score_map=self.score_map.to_shifted_score_map(offset_y=offset_y, offset_x=offset_x) if self.score_map else None,
+            char_boxes=[char_box.to_shifted_char_box(offset_y=offset_y, offset_x=offset_x) for char_box in self.char_boxes],
+        )
+
+    @classmethod
+    def build_char_polygon(cls, up: float, down: float, left: float, right: float):
+        return Polygon.from_xy_pairs([(left, up), (right, up), (right, down), (left, down)])
+
+    def to_char_polygons(self, page_height: int, page_width: int, ref_char_height_ratio: float = 1.0,
+                         ref_char_width_ratio: float = 1.0):
+        """One rectangle a char, widened to the reference char's size inside the page (reference :630-699)."""
+        assert len(self.char_boxes) == len(self.char_glyphs)
+        polygons: List[Polygon] = []
+        for char_box, char_glyph in zip(self.char_boxes, self.char_glyphs):
+            ref_char_height = char_glyph.ref_char_height * ref_char_height_ratio
+            ref_char_width = char_glyph.ref_char_width * ref_char_width_ratio
+            box = char_box.box
+            up, down, left, right = box.up, box.down, box.left, box.right
+            if self.is_hori:
+                if box.height < ref_char_height:
+                    half_inc = (ref_char_height - box.height) / 2
+                    up = max(0, up - half_inc)
+                    down = min(page_height - 1, down + half_inc)
+                if box.width < ref_char_width:
+                    half_inc = (ref_char_width - box.width) / 2
+                    left = max(0, left - half_inc)
+                    right = min(page_width - 1, right + half_inc)
+            else:
+                if box.width < ref_char_height:
+                    half_inc = (ref_char_height - box.width) / 2
+                    left = max(0, left - half_inc)
+                    right = min(page_width - 1, right + half_inc)
+                if box.height < ref_char_width:
+                    half_inc = (ref_char_width - box.height) / 2
+                    up = max(self.box.up, up - half_inc)
+                    down = min(page_height - 1, down + half_inc)
+            polygons.append(self.build_char_polygon(up=up, down=down, left=left, right=right))
+        return polygons

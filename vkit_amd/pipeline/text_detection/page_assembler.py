@@ -11,11 +11,13 @@ all layers are applied on the device in that order by one ``vkx_fill_u8`` call. 
 runs through the ``rotate`` operator (``vkx_warp_affine_*``) like in the reference.
 
 The inputs are the outputs of upstream steps that are outside the accelerated path (layout, fonts, barcodes
-...); they are declared here with the reference's field names, reduced to the fields this step reads.  One
-deviation: ``fill_text_line_to_seal_impression`` (vkit/engine/seal_impression) is upstream rendering, so a
-``SealImpressionResource`` carries its result (``text_line_filled_score_map``, ``char_polygons``) directly.
+...); they are declared here with the reference's field names, reduced to the fields this step reads.  A
+``SealImpressionResource`` is given the reference's way -- ``text_line_slot_indices``, ``text_lines``, ``internal_text_line`` --
+and the step runs ``fill_text_line_to_seal_impression`` itself, as the reference's does (:200): all such seals of a page in
+ONE batched device call (``vkit_amd.engine.seal_impression``), before the rotations.  A resource that already carries the
+result (``text_line_filled_score_map``, ``char_polygons``) is taken as it is.
 """
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import Any, List, Optional, Sequence, Tuple, Union
 
 import attrs
 import numpy as np
@@ -124,8 +126,14 @@ class SealImpression:
 class SealImpressionResource:
     box: Box
     angle: int
-    text_line_filled_score_map: ScoreMap
+    # the precomputed result of fill_text_line_to_seal_impression, or None: the step computes it from the fields below
+    text_line_filled_score_map: Optional[ScoreMap] = None
     char_polygons: Sequence[Polygon] = ()
+    # the reference's fields (vkit/pipeline/text_detection/page_text_line.py: SealImpressionResource); the text lines are
+    # vkit_amd.engine.font.TextLine, the seal impression of the resource vkit_amd.engine.seal_impression.SealImpression
+    text_line_slot_indices: Sequence[int] = ()
+    text_lines: Sequence[Any] = ()
+    internal_text_line: Optional[Any] = None
 
 
 @attrs.define
@@ -291,11 +299,19 @@ class PageAssemblerStep(PipelineStep[PageAssemblerStepConfig, PageAssemblerStepI
         # last, so the composite order is untouched.
         seal_layers = []
         page_seal_impression_char_polygons: List[Polygon] = []
-        for seal_impression, resource in zip(seal_collection.seal_impressions,
-                                             seal_collection.seal_impression_resources):
+        seal_pairs = list(zip(seal_collection.seal_impressions, seal_collection.seal_impression_resources))
+        # the seals given the reference's way: their text-line score maps and char polygons in one batched call
+        unfilled = [k for k, (_, resource) in enumerate(seal_pairs) if resource.text_line_filled_score_map is None]
+        filled = {}
+        if unfilled:
+            from vkit_amd.engine.seal_impression import fill_text_lines_to_seal_impressions
+            filled = dict(zip(unfilled, fill_text_lines_to_seal_impressions([
+                (seal_pairs[k][0], seal_pairs[k][1].text_line_slot_indices, seal_pairs[k][1].text_lines,
+                 seal_pairs[k][1].internal_text_line) for k in unfilled])))
+        for k, (seal_impression, resource) in enumerate(seal_pairs):
+            text_line_filled_score_map, char_polygons = filled.get(k, (resource.text_line_filled_score_map, resource.char_polygons))
             rotated = rotate.distort({'angle': resource.angle}, mask=seal_impression.background_mask,
-                                     score_map=resource.text_line_filled_score_map,
-                                     polygons=resource.char_polygons or None)
+                                     score_map=text_line_filled_score_map, polygons=char_polygons or None)
             background_mask, text_score_map = rotated.mask, rotated.score_map
             assert background_mask is not None and text_score_map is not None
             assert background_mask.shape == text_score_map.shape
