@@ -6,6 +6,8 @@ instruction to a phase of the tile body through its .loc line, and prints instru
 Static counts: phase A's raster loops run a data-dependent number of times; phases C/D (4 iterations of 2 window rows
 per wavefront, unrolled or not as the compiler chose) and E (8 output rows, unrolled) have fixed trip counts, stated in
 the output.  Dynamic totals come from the PMC runs (profiles/*pmc*).
+The single-variant build has no register pressure to speak of, so the last line is from the PRODUCTION build (the Makefile's flags):
+SGPRs, VGPRs, SGPR spills and scratch bytes of every pixel kernel of the chain, both instances, from the code-object metadata.
 Usage: tools/isa_census.py [--asm out.s] > profiles/r2_isa_census.md"""
 import collections
 import os
@@ -44,6 +46,25 @@ def phase_table():
     first = next(i for i, l in enumerate(lines) if 'uint32_t add_noise_u8x4(' in l)
     last = next(i for i in range(first, len(lines)) if lines[i].startswith('}'))
     return table, (start + 1, end + 1), (first + 1, last + 1)
+
+
+def production_registers():
+    """(kernel, instance, sgprs, vgprs, sgpr spills, vgpr spills, scratch bytes) of the chain's pixel kernels as they ship."""
+    flags = [f for f in FLAGS if f not in ('-g1', '-DVKX_FUSED_CENSUS=2')]
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, 'fused.s')
+        subprocess.run(['/opt/rocm/bin/hipcc'] + flags + ['-o', out, SRC], check=True, capture_output=True)
+        text = open(out).read()
+    rows = []
+    for entry in text[text.index('amdhsa.kernels:'):].split('  - .agpr_count:')[1:]:
+        name = re.search(r'\.name:\s+(\S+)', entry).group(1)
+        m = re.search(r'(k_chain_fused(?:_rim|_over|_whole)?)ILb([01])E', name)
+        if not m:
+            continue
+        field = lambda key: int(re.search(r'\.' + key + r':\s+(\d+)', entry).group(1))
+        rows.append((m.group(1), 'streak' if m.group(2) == '1' else 'plain', field('sgpr_count'), field('vgpr_count'),
+                     field('sgpr_spill_count'), field('vgpr_spill_count'), field('private_segment_fixed_size')))
+    return sorted(rows)
 
 
 def classify(op):
@@ -138,6 +159,9 @@ def main():
     if meta:
         print(f'\nVGPRs of this single-variant build: {meta.group(1)} (the production kernel holds every variant and is compiled to 64 VGPRs, '
               '8 wavefronts per SIMD)')
+    print('\nProduction build (every variant, the Makefile\'s flags), from the code-object metadata: ' +
+          '; '.join(f'{k}<{inst}> {sg} SGPRs, {vg} VGPRs, {ss} SGPR spills, {vs} VGPR spills, {sc} B scratch'
+                    for k, inst, sg, vg, ss, vs, sc in production_registers()))
 
 
 if __name__ == '__main__':

@@ -16,6 +16,7 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHAIN_MEMBERS = ('k_chain_fused', 'k_chain_fused_whole', 'k_chain_fused_rim', 'k_chain_fused_over')
 
 
 def main():
@@ -30,6 +31,8 @@ def main():
         shutil.copy(stats256, os.path.join(out_dir, f'{tag}_kernel_stats_batch256.csv'))
     sums = defaultdict(lambda: defaultdict(float))    # kernel -> counter -> sum over dispatches
     counts = defaultdict(lambda: defaultdict(int))
+    parts = defaultdict(lambda: defaultdict(float))   # the members of k_chain_fused on their own
+    part_calls = defaultdict(lambda: defaultdict(int))
     for path in sorted(glob.glob(os.path.join(ROOT, 'gpurun_out', f'pmc_{tag}', 'p*', '*counter_collection.csv'))):
         with open(path) as fin:
             for row in csv.DictReader(fin):
@@ -38,8 +41,18 @@ def main():
                     continue
                 short = re.search(r'k_(np|chain)_[a-z_]+', name).group(0)
                 short = {'k_np_draw_compact': 'k_np_draw'}.get(short, short)          # (the name the library times it under)
+                # the chain's pixel stage is one kernel (k_chain_fused_whole: small ranges, or a library from before the split) or
+                # up to three per call, timed under one label: summed per call under k_chain_fused (what bench.py reads).  A call
+                # launches each member once at most, so the member with the most dispatches counts the calls.
+                part = short if short in CHAIN_MEMBERS else None
+                if part:
+                    short = 'k_chain_fused'
+                    parts[part][row['Counter_Name']] += float(row['Counter_Value'])
+                    part_calls[part][row['Counter_Name']] += 1
+                    counts[short][row['Counter_Name']] = max(part_calls[m][row['Counter_Name']] for m in CHAIN_MEMBERS)
+                else:
+                    counts[short][row['Counter_Name']] += 1
                 sums[short][row['Counter_Name']] += float(row['Counter_Value'])
-                counts[short][row['Counter_Name']] += 1
     lines = [f'# rocprofv3 PMC counters, {tag}, bench.py --batch {images} --steps 2 --warmup 1 (per launch, mean over '
              'the dispatches of the run)', '',
              'Separate `--pmc` passes with `--kernel-trace` only (tools/pmc.sh).  One launch covers the whole batch.', '']
@@ -50,6 +63,11 @@ def main():
         for c in sorted(per_launch):
             lines.append(f'| {c} | {per_launch[c]:.6g} | {per_launch[c] / images:.6g} |')
         lines.append('')
+        if kernel == 'k_chain_fused' and 'SQ_INSTS_VALU' in per_launch:
+            n = counts[kernel]['SQ_INSTS_VALU']
+            lines += ['Sum of the pixel kernels of a call (k_chain_fused, _rim, _over; or _whole).  VALU instructions per image: ' +
+                      ', '.join(f'{k} {parts[k]["SQ_INSTS_VALU"] / n / images:.6g} ({parts[k]["SQ_WAVES"] / n / images:.6g} wavefronts)'
+                                for k in sorted(parts)), '']
         if 'FETCH_SIZE' in per_launch and 'WRITE_SIZE' in per_launch:
             fetch = per_launch['FETCH_SIZE'] * 1024 * 2.0
             write = per_launch['WRITE_SIZE'] * 1024

@@ -3,7 +3,9 @@
 //   k_chain_setup      one lane per grid cell of every image: closed-form inverse homography, cv.fillPoly edge table, and
 //                      the binning of the cell into the destination tiles its bounding box (+ blur halo) touches.
 //   k_chain_setup_svd  the few cells whose homography needs the Jacobi-SVD least squares (workspace in LDS).
-//   k_chain_fused      one 512-lane workgroup (8 wavefronts) per destination tile.  The tile's WINDOW is 64 x 64
+//   k_chain_fused      (+ k_chain_fused_rim for the tiles on the rim of the result, k_chain_fused_over for the few interior tiles
+//                      with more candidates than LDS holds)
+//                      one 512-lane workgroup (8 wavefronts) per destination tile.  The tile's WINDOW is 64 x 64
 //                      pixels -- one wavefront spans a window row, lane = column -- and holds the tile proper
 //                      (((64 - 2R) & ~3)^2 pixels, R = blur radius) plus its halo:
 //      A  the tile's candidate cells are pulled into LDS and rasterised into an LDS ownership plane with
@@ -76,6 +78,7 @@ struct ItemDev {
     int sh, sw, dh, dw;
     int rows, cols;
     int tiles_x, tiles_y;
+    int rect_x0, rect_y0, rect_w, rect_h;   // interior rectangle of the tile grid (interior_rect; all 0 when there is none)
     int cell_base;     // index of this image's first cell in the batch-wide cell table
     int R;             // blur radius (0 = no blur); the tile proper is (64 - 2R) pixels wide and high
     int hue_on, hue_delta;
@@ -109,6 +112,24 @@ struct ElemPack {
     ItemDev::Elem el[4];
     int n;
 };
+
+// The INTERIOR RECTANGLE of an image's tile grid: the tiles [x0, x1] x [y0, y1] whose whole 64 x 64 window lies inside the
+// result (wx0 >= 0 && wy0 >= 0 && wx0 + W <= dw && wy0 + WH <= dh with wx0 = tx * Tw - R, wy0 = ty * Th - R).  k_chain_fused
+// takes these tiles, k_chain_fused_rim all the others (the RIM).  Small results have no rectangle: x1 < x0 or y1 < y0.
+struct TileRect {
+    int x0, y0, x1, y1;
+    __host__ __device__ bool empty() const { return x1 < x0 || y1 < y0; }
+};
+__host__ __device__ inline TileRect interior_rect(int dw, int dh, int R)
+{
+    const int Tw = tile_side(R), Th = tile_height(R);
+    TileRect r;
+    r.x0 = (R + Tw - 1) / Tw;                               // tx * Tw - R >= 0
+    r.y0 = (R + Th - 1) / Th;
+    r.x1 = dw - W + R >= 0 ? (dw - W + R) / Tw : -1;        // tx * Tw - R + W <= dw
+    r.y1 = dh - WH + R >= 0 ? (dh - WH + R) / Th : -1;
+    return r;
+}
 
 struct TileBin {       // candidate cell rectangle of one tile: [rmin, rmax] x [cmin, cmax]
     int rmin, cmin;    // atomicMin, initialised to 0x7f7f7f7f
@@ -1111,8 +1132,135 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
     }
 }
 
+// The pixel stage of the chain is three kernels.  k_chain_fused takes the tiles of the interior rectangle (TileRect): the
+// EMPTY and the INTERIOR variants only.  k_chain_fused_rim takes the rim with the generic variant.  The rectangle tiles with
+// more than NLDSCELL candidates, which k_chain_fused hands over in a list per range call, are k_chain_fused_over's.  In one kernel
+// the register pressure of the generic variant made the allocator spill the wrapper's scalar state for EVERY tile (99 SGPR
+// spills, v_writelane / v_readlane on the interior path); without it the kernel below has none.
 template <bool STREAK>
 __global__ void __launch_bounds__(NTHREADS, VKX_FUSED_WAVES_PER_EU) k_chain_fused(const ItemDev *__restrict__ items,
+                                                          const vkc::CellC *__restrict__ cells,
+                                                          const TileBin *__restrict__ bins, int bin_slots,
+                                                          int *__restrict__ over_count, int2 *__restrict__ over_list, int over_slots,
+                                                          const HsvLut *__restrict__ lut, int phase_limit)
+{
+    // grid = (rectangle slots, images).  XCD-aware tile order: consecutive workgroup ids land on different XCDs
+    // (id % 8); give every XCD a contiguous run of an image's rectangle tiles so neighbouring tiles (shared source rows,
+    // shared cells) meet in one L2.
+    // The run an XCD takes rotates with the image index: the cheap tiles (outside the distorted page, mostly the
+    // first and last rows) would otherwise always land on the same two XCDs and leave them idle at the end.
+    const ItemDev &it = items[blockIdx.y];
+    const int rw = it.rect_w;
+    const int nrect = rw * it.rect_h;
+    const int per = (nrect + 7) >> 3;            // this image's run length
+    const int run = (int)((blockIdx.x + blockIdx.y) & 7), pos = (int)(blockIdx.x >> 3);
+    const int rl = run * per + pos;
+    if (pos >= per || rl >= nrect) return;
+    if (phase_limit == 10) return;
+    const int ry = __builtin_amdgcn_readfirstlane(div_small(rl, rw, __builtin_amdgcn_rcpf((float)rw)));
+    const int tx = it.rect_x0 + rl - ry * rw, ty = it.rect_y0 + ry;
+    const int tl = ty * it.tiles_x + tx;
+    const TileBin bin = bins[(size_t)blockIdx.y * bin_slots + tl];   // bins are laid out [image][slot of the full tile grid]
+    const int nc = bin.rmax1 > 0 ? max(0, bin.rmax1 - bin.rmin) * max(0, bin.cmax1 - bin.cmin) : 0;
+#ifdef VKX_FUSED_CENSUS
+    // tools/isa_census.py: only the hot variant (interior window, 5-tap blur) so that its ISA can be read in isolation
+    (void)nc;
+    chain_tile<1, STREAK, VKX_FUSED_CENSUS>(it, tx, ty, cells, bin, lut, phase_limit);
+    return;
+#endif
+    if (nc == 0) chain_tile<2, STREAK>(it, tx, ty, cells, bin, lut, phase_limit);
+    else if (nc <= NLDSCELL && phase_limit != 3) {
+        // the common case gets the blur radius as a compile-time constant
+        switch (it.R) {
+        case 0: chain_tile<1, STREAK, 0>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        case 1: chain_tile<1, STREAK, 1>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        case 2: chain_tile<1, STREAK, 2>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        default: chain_tile<1, STREAK, 3>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        }
+    } else if (threadIdx.x == 0) {
+        // overfull (or VKX_FUSED_PHASES=3): the generic variant of k_chain_fused_over takes the tile
+        const int k = atomicAdd(over_count, 1);
+        if (k < over_slots) over_list[k] = make_int2((int)blockIdx.y, tl);     // (k < rectangle tiles of the range <= over_slots)
+    }
+}
+
+// grid = (rim slots, images): the rim tiles of an image in the order top rows, bottom rows, then the left and right columns
+// of the rows beside the rectangle; the same XCD runs as above on the rim index.
+template <bool STREAK>
+__global__ void __launch_bounds__(NTHREADS, VKX_FUSED_WAVES_PER_EU) k_chain_fused_rim(const ItemDev *__restrict__ items,
+                                                          const vkc::CellC *__restrict__ cells,
+                                                          const TileBin *__restrict__ bins, int bin_slots,
+                                                          const HsvLut *__restrict__ lut, int phase_limit)
+{
+    if (phase_limit == 10) return;
+    const ItemDev &it = items[blockIdx.y];
+    const int tiles_x = it.tiles_x, rw = it.rect_w, rh = it.rect_h;
+    const int nrim = tiles_x * it.tiles_y - rw * rh;
+    const int per = (nrim + 7) >> 3;
+    const int run = (int)((blockIdx.x + blockIdx.y) & 7), pos = (int)(blockIdx.x >> 3);
+    const int q = run * per + pos;
+    if (pos >= per || q >= nrim) return;
+    int tl;
+    const int top = it.rect_y0 * tiles_x, bottom = (it.tiles_y - it.rect_y0 - rh) * tiles_x;
+    if (rw * rh == 0 || q < top) tl = q;
+    else if (q < top + bottom) tl = q - top + (it.rect_y0 + rh) * tiles_x;
+    else {
+        const int m = q - top - bottom, side = tiles_x - rw;      // (side > 0: the rows beside the rectangle have rim tiles)
+        const int r = __builtin_amdgcn_readfirstlane(div_small(m, side, __builtin_amdgcn_rcpf((float)side)));
+        const int c = m - r * side;
+        tl = (it.rect_y0 + r) * tiles_x + (c < it.rect_x0 ? c : c + rw);
+    }
+    const TileBin bin = bins[(size_t)blockIdx.y * bin_slots + tl];
+    const int ty = __builtin_amdgcn_readfirstlane(div_small(tl, tiles_x, __builtin_amdgcn_rcpf((float)tiles_x)));
+    const int tx = tl - ty * tiles_x;
+    const int nc = bin.rmax1 > 0 ? max(0, bin.rmax1 - bin.rmin) * max(0, bin.cmax1 - bin.cmin) : 0;
+    if (nc == 0) chain_tile<2, STREAK>(it, tx, ty, cells, bin, lut, phase_limit);
+    else {
+        switch (it.R) {
+        case 0: chain_tile<0, STREAK, 0>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        case 1: chain_tile<0, STREAK, 1>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        case 2: chain_tile<0, STREAK, 2>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        default: chain_tile<0, STREAK, 3>(it, tx, ty, cells, bin, lut, phase_limit); break;
+        }
+    }
+}
+
+// The overfull list of a range of images: (image, tile) pairs, one list and one counter per call of vkx_chain_plan_tiles.
+// Workgroup b takes the entries b, b + gridDim.x, ... through the generic variant with the blur radius read from the item
+// (these tiles are few: 5 of 10 242 on the benchmark's pages; the grid is half the range's rectangle tiles, 512 at most).
+// A kernel of its own at half the occupancy: ANY loop around a tile body makes the compiler carry the sixteen homography
+// doubles of phase C around it as loop state (undefined values merged at the loop header after the control flow is
+// structurised), and at the 64 VGPRs of the two kernels above that state goes to scratch -- 37 to 43 VGPR spills in
+// k_chain_fused_rim with the walk inside.
+constexpr int kOverGrid = 512;
+template <bool STREAK>
+__global__ void __launch_bounds__(NTHREADS, 4) k_chain_fused_over(const ItemDev *__restrict__ items,
+                                                          const vkc::CellC *__restrict__ cells,
+                                                          const TileBin *__restrict__ bins, int bin_slots,
+                                                          const int *__restrict__ over_count, const int2 *__restrict__ over_list,
+                                                          int over_slots, const HsvLut *__restrict__ lut, int phase_limit)
+{
+    const int n_over = min(*over_count, over_slots);
+    if ((int)blockIdx.x >= n_over || phase_limit == 10) return;
+    // (every early return inside chain_tile is uniform over the workgroup and ends the inlined body only: all lanes reach
+    //  the barrier that separates two tiles' use of LDS)
+    for (int k = (int)blockIdx.x; k < n_over; k += (int)gridDim.x) {
+        const int2 e = over_list[k];
+        const int img = __builtin_amdgcn_readfirstlane(e.x), tl = __builtin_amdgcn_readfirstlane(e.y);
+        const ItemDev &it = items[img];
+        const TileBin bin = bins[(size_t)img * bin_slots + tl];
+        const int tiles_x = __builtin_amdgcn_readfirstlane(it.tiles_x);
+        const int ty = __builtin_amdgcn_readfirstlane(div_small(tl, tiles_x, __builtin_amdgcn_rcpf((float)tiles_x)));
+        chain_tile<0, STREAK>(it, tl - ty * tiles_x, ty, cells, bin, lut, phase_limit);
+        __syncthreads();
+    }
+}
+
+// Small ranges (vkx_chain_plan_tiles: fewer than kSplitMinTiles tiles) keep ONE launch over the whole tile grid with all nine
+// variants: the two more launches and kernel tails of the split cost a 64-page batch more than the spills do (measured:
+// +4.7 % per batch), and a call of a few images -- a pipeline lane sends one per call -- pays per dispatch.
+template <bool STREAK>
+__global__ void __launch_bounds__(NTHREADS, VKX_FUSED_WAVES_PER_EU) k_chain_fused_whole(const ItemDev *__restrict__ items,
                                                           const vkc::CellC *__restrict__ cells,
                                                           const TileBin *__restrict__ bins,
                                                           const HsvLut *__restrict__ lut, int phase_limit)
@@ -1138,12 +1286,6 @@ __global__ void __launch_bounds__(NTHREADS, VKX_FUSED_WAVES_PER_EU) k_chain_fuse
     const int wx0 = tx * Tw - it.R, wy0 = ty * Th - it.R;
     const int nc = bin.rmax1 > 0 ? max(0, bin.rmax1 - bin.rmin) * max(0, bin.cmax1 - bin.cmin) : 0;
     const bool interior = wx0 >= 0 && wy0 >= 0 && wx0 + W <= it.dw && wy0 + WH <= it.dh && nc <= NLDSCELL && phase_limit != 3;
-#ifdef VKX_FUSED_CENSUS
-    // tools/isa_census.py: only the hot variant (interior window, 5-tap blur) so that its ISA can be read in isolation
-    (void)interior;
-    chain_tile<1, STREAK, VKX_FUSED_CENSUS>(it, tx, ty, cells, bin, lut, phase_limit);
-    return;
-#endif
     if (nc == 0) chain_tile<2, STREAK>(it, tx, ty, cells, bin, lut, phase_limit);
     else if (interior) {
         // the common case gets the blur radius as a compile-time constant
@@ -1219,14 +1361,15 @@ __global__ void __launch_bounds__(256) k_chain_noise_rows(const ItemDev *__restr
 // One dispatch instead of a descriptor copy and three memsets (every dispatch on a pipeline lane's stream costs the
 // pipeline tens of microseconds while other lanes' plane transfers are in flight): the descriptors are read from the
 // page-locked ring through its device mapping, the tile bins start at (min 0x7f7f7f7f, max + 1 = 0), the deferred list
-// is empty.
+// is empty, and so are the overfull lists of the pixel kernels.
 __global__ void __launch_bounds__(256) k_chain_prologue(uint32_t *__restrict__ desc_dst, const uint32_t *__restrict__ desc_src,
                                                         unsigned n_words, TileBin *__restrict__ bins, unsigned nbins,
-                                                        int *__restrict__ deferred)
+                                                        int *__restrict__ deferred, int *__restrict__ over_count, unsigned n_over)
 {
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
     if (i < n_words) desc_dst[i] = desc_src[i];
     if (i < nbins) bins[i] = TileBin{0x7f7f7f7f, 0x7f7f7f7f, 0, 0};
+    if (i < n_over) over_count[i] = 0;           // (n_over = images <= nbins: the grid covers it)
     if (i == 0) *deferred = 0;
 }
 
@@ -1242,12 +1385,15 @@ struct vkx_chain_plan {
     std::vector<long long> row_prefix;        // first (row, tile column) record of every image with tiled noise
     long long ncells = 0;
     int max_tiles = 0, slots = 0;
+    int rect_slots = 0;                       // rectangle tiles of the largest rectangle, rounded up to 8 (0: no image has one)
     bool elements = false, streak = false;
     const ItemDev *d_items = nullptr;
     const int *d_cell_prefix = nullptr;
     TileBin *bins = nullptr;
     vkc::CellC *cells = nullptr;
     int *deferred = nullptr;
+    int *over_count = nullptr;                // [images]: a call of vkx_chain_plan_tiles counts in the entry of its first image
+    int2 *over_list = nullptr;                // [images][rect_slots] (image of the range, tile): rectangle tiles left to k_chain_fused_over
     const HsvLut *lut = nullptr;
 };
 
@@ -1269,7 +1415,9 @@ int vkx_chain_plan_setup(vkx_ctx *ctx, vkx_chain_plan *p)
     p->slots = ((p->max_tiles + 7) / 8) * 8;              // tile slots per image in the launch grid
     const size_t nbins = (size_t)p->slots * n_items;
     if (n_items > 65535) return VKX_ERR_UNSUPPORTED;      // gridDim.y
-    if ((rc = vkx_scratch_reserve(ctx, s_bins, sizeof(TileBin) * nbins))) return rc;
+    // (after the bins: the overfull counters and lists of the chain's pixel kernels)
+    const size_t over_ints = p->elements ? 0 : (size_t)n_items * (2 + 2 * (size_t)p->rect_slots);
+    if ((rc = vkx_scratch_reserve(ctx, s_bins, sizeof(TileBin) * nbins + sizeof(int) * over_ints))) return rc;
     const size_t items_bytes = sizeof(ItemDev) * (size_t)n_items, prefix_bytes = sizeof(int) * p->prefix.size();
     vkx_tables tab(ctx);
     const size_t items_off = tab.add(items_bytes), prefix_off = tab.add(prefix_bytes), misc_bytes = tab.bytes;
@@ -1284,6 +1432,8 @@ int vkx_chain_plan_setup(vkx_ctx *ctx, vkx_chain_plan *p)
     p->d_items = (const ItemDev *)(misc + items_off);
     p->d_cell_prefix = (const int *)(misc + prefix_off);
     p->bins = (TileBin *)s_bins->ptr;
+    p->over_count = (int *)(p->bins + nbins);
+    p->over_list = (int2 *)(p->over_count + n_items + (n_items & 1));      // (8-byte aligned)
     p->cells = (vkc::CellC *)s_cells->ptr;
     p->deferred = (int *)((unsigned char *)s_cells->ptr + cells_bytes);
     {
@@ -1292,7 +1442,8 @@ int vkx_chain_plan_setup(vkx_ctx *ctx, vkx_chain_plan *p)
         const size_t n_words = (misc_bytes + 3) / 4;
         VKX_TIMED(ctx, "k_chain_prologue");
         k_chain_prologue<<<vkx_blocks(std::max(n_words, nbins), 256), 256, 0, ctx->stream>>>((uint32_t *)misc, (const uint32_t *)ring_dev,
-                                                                                            (unsigned)n_words, p->bins, (unsigned)nbins, p->deferred);
+                                                                                            (unsigned)n_words, p->bins, (unsigned)nbins, p->deferred,
+                                                                                            p->over_count, p->elements ? 0u : (unsigned)n_items);
         VKX_LAUNCH_CHECK();
     }
     { VKX_TIMED(ctx, "k_chain_setup"); k_chain_setup<<<vkx_blocks((size_t)p->ncells, 256), 256, 0, ctx->stream>>>(p->d_items, p->d_cell_prefix, n_items, (int)p->ncells, p->slots, p->cells, p->bins, p->deferred); }
@@ -1320,12 +1471,13 @@ int vkx_chain_plan_tiles(vkx_ctx *ctx, vkx_chain_plan *p, int first, int count)
 {
     if (count <= 0) return VKX_OK;
     // profiling aids: VKX_FUSED_PHASES=1|2 stops the kernel after phase A | C+D, 10..13 inside phase A (tools/phases_a.sh),
-    // 20 writes the horizontal sums of the centre row instead of the finished pixel
+    // 20 writes the horizontal sums of the centre row instead of the finished pixel, 3 sends every non-empty rectangle tile
+    // through the overfull list to the generic variant
     static const int phase_limit = [] { const char *e = getenv("VKX_FUSED_PHASES"); return e ? atoi(e) : 0; }();
     const ItemDev *items = p->d_items + first;
     const TileBin *bins = p->bins + (size_t)first * p->slots;      // bins are laid out [image][slot]
-    const dim3 grid(p->slots, count);
     if (p->elements) {
+        const dim3 grid(p->slots, count);
         VKX_TIMED(ctx, "k_tile_remap");
         ElemPack pack;
         memset(&pack, 0, sizeof(pack));
@@ -1333,9 +1485,52 @@ int vkx_chain_plan_tiles(vkx_ctx *ctx, vkx_chain_plan *p, int first, int count)
         for (int e = 0; e < 4; e++) pack.el[e] = p->dev[first].el[e];
         k_tile_remap<<<grid, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, pack);
     } else {
-        VKX_TIMED_MAJOR(ctx, "k_chain_fused");
-        if (p->streak) k_chain_fused<true><<<grid, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->lut, phase_limit);
-        else k_chain_fused<false><<<grid, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->lut, phase_limit);
+        // the grids of the range: the largest rectangle and the largest rim of its images, rounded up to 8
+        int most_rect = 0, most_rim = 0;
+        long long all_rect = 0, all_tiles = 0;
+        for (int i = first; i < first + count; i++) {
+            const ItemDev &d = p->dev[i];
+            most_rect = std::max(most_rect, d.rect_w * d.rect_h);
+            all_rect += d.rect_w * d.rect_h;
+            all_tiles += (long long)d.tiles_x * d.tiles_y;
+            most_rim = std::max(most_rim, d.tiles_x * d.tiles_y - d.rect_w * d.rect_h);
+        }
+        // the range's own counter and its own part of the list (the ranges of a chunked batch stay independent)
+        int *over_count = p->over_count + first;
+        int2 *over_list = p->over_list + (size_t)first * p->rect_slots;
+        const int over_slots = (int)std::min<long long>((long long)count * p->rect_slots, INT_MAX);
+        VKX_TIMED_MAJOR(ctx, "k_chain_fused");     // one label for all of them
+        // The split saves about 2.4 % of the pixel stage and costs two more launches and kernel tails, 35 - 70 us: it pays from
+        // about 3 ms of kernel, i.e. 85 pages of 2048^2 = 100 000 tiles.  VKX_CHAIN_SPLIT=0 / 1 forces one way (profiling at small batches).
+        constexpr long long kSplitMinTiles = 65536;
+        // (read at every call: the tests of the split kernels set it around their small batches)
+        const char *split_e = getenv("VKX_CHAIN_SPLIT");
+        const int split_env = split_e && split_e[0] ? (split_e[0] == '0' ? 0 : 1) : -1;
+        if (split_env >= 0 ? split_env == 0 : all_tiles < kSplitMinTiles) {
+            const dim3 grid(p->slots, count);
+            if (p->streak) k_chain_fused_whole<true><<<grid, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->lut, phase_limit);
+            else k_chain_fused_whole<false><<<grid, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->lut, phase_limit);
+            VKX_LAUNCH_CHECK();
+            return VKX_OK;
+        }
+        if (most_rect > 0) {
+            const dim3 grid_rect((most_rect + 7) / 8 * 8, count);
+            if (p->streak) k_chain_fused<true><<<grid_rect, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->slots, over_count, over_list, over_slots, p->lut, phase_limit);
+            else k_chain_fused<false><<<grid_rect, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->slots, over_count, over_list, over_slots, p->lut, phase_limit);
+            VKX_LAUNCH_CHECK();
+        }
+        if (most_rim > 0) {        // (an image without a blur whose sides are multiples of 64 has no rim)
+            const dim3 grid_rim((most_rim + 7) / 8 * 8, count);
+            if (p->streak) k_chain_fused_rim<true><<<grid_rim, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->slots, p->lut, phase_limit);
+            else k_chain_fused_rim<false><<<grid_rim, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->slots, p->lut, phase_limit);
+            VKX_LAUNCH_CHECK();
+        }
+        if (most_rect > 0) {       // the tiles the first kernel left in the list
+            // two trips for every workgroup should the whole range be overfull
+            const dim3 grid_over((unsigned)std::min<long long>((all_rect + 1) / 2, kOverGrid));
+            if (p->streak) k_chain_fused_over<true><<<grid_over, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->slots, over_count, over_list, over_slots, p->lut, phase_limit);
+            else k_chain_fused_over<false><<<grid_over, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->slots, over_count, over_list, over_slots, p->lut, phase_limit);
+        }
     }
     VKX_LAUNCH_CHECK();
     return VKX_OK;
@@ -1355,7 +1550,7 @@ int vkx_chain_plan_build(vkx_ctx *ctx, const vkx_chain_item *items, int n_items,
     std::vector<long long> &row_prefix = plan->row_prefix;
     row_prefix.assign((size_t)n_items + 1, 0);
     long long tiles = 0, ncells = 0;
-    int max_tiles = 0;
+    int max_tiles = 0, max_rect = 0;
     for (int i = 0; i < n_items; i++) {
         const vkx_chain_item &it = items[i];
         if (it.blur_ksize > 2 * RMAX + 1 || (it.blur_ksize > 1 && (it.blur_ksize & 1) == 0)) return VKX_ERR_UNSUPPORTED;
@@ -1382,6 +1577,9 @@ int vkx_chain_plan_build(vkx_ctx *ctx, const vkx_chain_item *items, int n_items,
         d.R = it.blur_ksize > 1 ? it.blur_ksize / 2 : 0;
         const int Tw = tile_side(d.R), Th = tile_height(d.R);
         d.tiles_x = (it.dw + Tw - 1) / Tw; d.tiles_y = (it.dh + Th - 1) / Th;
+        const TileRect rect = interior_rect(it.dw, it.dh, d.R);
+        if (!rect.empty()) { d.rect_x0 = rect.x0; d.rect_y0 = rect.y0; d.rect_w = rect.x1 - rect.x0 + 1; d.rect_h = rect.y1 - rect.y0 + 1; }
+        max_rect = std::max(max_rect, d.rect_w * d.rect_h);
         d.cell_base = (int)ncells;
         d.hue_on = it.hue_enabled; d.hue_delta = it.hue_delta;
         d.streak_on = it.streak_enabled && it.streak_alpha != 0.0 && (it.streak_enable_vert || it.streak_enable_hori);
@@ -1424,6 +1622,7 @@ int vkx_chain_plan_build(vkx_ctx *ctx, const vkx_chain_item *items, int n_items,
     }
     plan->ncells = ncells;
     plan->max_tiles = max_tiles;
+    plan->rect_slots = (max_rect + 7) / 8 * 8;
     *out = plan.release();
     return VKX_OK;
 }
