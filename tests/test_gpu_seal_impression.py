@@ -264,6 +264,76 @@ def test_exact_shrinks_and_integer_area_take_their_own_modes():
     del keep
 
 
+SOURCE_GEOMETRIES = {                      # the source (h, w) of a glyph that is resized to (gh, pw)
+    'equal': lambda gh, pw: (gh, pw),
+    'twice': lambda gh, pw: (2 * gh, 2 * pw),
+    'factors_3_2': lambda gh, pw: (3 * gh, 2 * pw),
+    'shrink_1.6': lambda gh, pw: (int(round(1.6 * gh)), int(round(1.6 * pw))),
+    'enlarge_1.4': lambda gh, pw: (int(round(gh / 1.4)), int(round(pw / 1.4))),
+    'one_wide': lambda gh, pw: (gh, 1),
+    'one_high': lambda gh, pw: (1, pw),
+}
+AREA_REFUSES = ('enlarge_1.4', 'one_wide', 'one_high')      # INTER_AREA enlargements: the call refuses them (test_abi_refusals)
+
+
+@pytest.mark.parametrize('interp', (2, 3, 4, 5, 6))
+@pytest.mark.parametrize('kind_name', ('F32', 'U8C1', 'U8C3'))
+def test_every_mode_equals_the_exported_resize(kind_name, interp):
+    """Every mode of the glyph resize is the exported single-plane kernel it stands for: a call whose sources are resized by
+    seal_fill equals the call that is handed the planes N.resize made of them (then the clip to [0, 1], or the > 0) to copy.
+    Both go through the same rotation, fill and alpha / max rescale, so the maps must have the same bits.  Per char one source
+    geometry of SOURCE_GEOMETRIES, in as many passes as it takes to use each; INTER_AREA leaves out its enlargements."""
+    from vkit_amd import _native as N
+    ctx = N.default_ctx()
+    kind = {'F32': N.SEAL_SRC_F32, 'U8C1': N.SEAL_SRC_U8C1, 'U8C3': N.SEAL_SRC_U8C3}[kind_name]
+    chars, seals, planes_host, keep, _, floats = tables(('five_cubic',))
+    n = len(chars)
+    assert n >= 2 and all(int(c['glyph_h']) >= 2 and int(c['plane_w']) >= 2 for c in chars)      # (the enlargements enlarge)
+    kept = [g for g in SOURCE_GEOMETRIES if not (interp == 3 and g in AREA_REFUSES)]
+    rng = np.random.default_rng(100 * interp + kind)
+    ran = set()
+    for first in range(0, len(kept), n):
+        large, small, held = chars.copy(), chars.copy(), []
+        for k in range(n):
+            geometry = kept[(first + k) % len(kept)]
+            gh, pw = int(chars[k]['glyph_h']), int(chars[k]['plane_w'])
+            h, w = SOURCE_GEOMETRIES[geometry](gh, pw)
+            assert h >= 1 and w >= 1
+            if kind == N.SEAL_SRC_F32:
+                src = (R.blocky(rng, (h, w), 1, 0, 5, np.float32) / np.float32(4)).astype(np.float32)
+                src[-1, -1] = 1.0
+            elif kind == N.SEAL_SRC_U8C1:
+                src = R.blocky(rng, (h, w), 1, 0, 2, np.uint8) * np.uint8(90)
+                src[-1, -1] = 90
+            else:                                           # ink where any channel is set: one channel in four is
+                src = (rng.integers(0, 4, (h, w, 3)) == 0).astype(np.uint8) * np.uint8(90)
+                src[-1, -1] = 90
+            if h >= 2:                                      # a part without ink: the resized plane is not constant
+                src[:h // 2] = 0
+            else:
+                src[:, :w // 2] = 0
+            if kind == N.SEAL_SRC_F32:
+                resized = np.clip(np.asarray(N.resize(src, (gh, pw), interp)), 0.0, 1.0).astype(np.float32)
+            else:
+                mask = src > 0 if src.ndim == 2 else (src > 0).any(axis=2)
+                resized = (np.asarray(N.resize(mask.astype(np.uint8) * np.uint8(255), (gh, pw), interp)) > 0).astype(np.uint8)
+            assert resized.shape == (gh, pw) and resized.min() != resized.max(), (geometry, k)
+            for table, plane, plane_kind in ((large, src, kind), (small, resized, N.SEAL_SRC_F32 if kind == N.SEAL_SRC_F32 else N.SEAL_SRC_U8C1)):
+                dev = ctx.to_device(np.ascontiguousarray(plane))
+                held.append(dev)
+                table[k]['src'], table[k]['src_step'], table[k]['src_kind'] = dev.ptr, plane[0].size * plane.itemsize, plane_kind
+                table[k]['src_h'], table[k]['src_w'], table[k]['interpolation'] = plane.shape[0], plane.shape[1], interp
+            ran.add(geometry)
+        got, want = ctx.dev_empty((floats,), np.float32), ctx.dev_empty((floats,), np.float32)
+        N.seal_fill(large, seals, got, planes_host)
+        N.seal_fill(small, seals, want, planes_host)
+        assert R.same_bits(np.array(got.host()), np.array(want.host())), (kind_name, interp, first)
+        assert np.nanmax(np.array(want.host())) > 0
+        del held
+    assert len(ran) == (4 if interp == 3 else 7), ran
+    del keep
+
+
 def test_abi_refusals():
     """every refusal of include/vkx.h: VKX_ERR_INVALID and nothing written"""
     from vkit_amd import _native as N

@@ -5,9 +5,10 @@
 // the host (vkit_amd/pipeline/text_detection/page_cropping.py) and the pixels take two launches:
 //   k_crop_count   every candidate window's two counts (+ the page's nonzero pixels) as per-workgroup partial sums;
 //   k_crop_planes  every plane of every accepted crop: the window copied, the rest filled, and for a core-only plane the
-//                  integer-factor INTER_AREA shrink computed from the same reads (vkd::area_fast_*, shared with resize.hip).
+//                  integer-factor INTER_AREA shrink computed from the same reads (vkd::area_fast_* of vkx_resize_pixel.h, shared with resize.hip).
 // Both are gathers bound by HBM reads of the page windows; the tables (windows, planes) travel as one small copy each.
 #include "vkx_internal.h"
+#include "vkx_resize_pixel.h"
 
 #include <algorithm>
 #include <cstring>

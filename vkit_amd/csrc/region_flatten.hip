@@ -12,14 +12,14 @@
 //                     mask is 0 (Mask.extract_image, fused).  A pair writes a WINDOW of its warped plane: the trim.
 //   k_region_extent   one workgroup a mask: first / last non-zero row and column, LDS min / max.
 //   k_region_resize   cv.resize INTER_CUBIC of N pairs, the tables of every pair in the staged block; the pixel is
-//                     vkd::cubic_pixel_u8's, the arithmetic of vkx_resize_cubic_u8_dev.  The mask is read as (m > 0) * 255
+//                     vkd::taps_pixel_u8's, the arithmetic of vkx_resize_cubic_u8_dev.  The mask is read as (m > 0) * 255
 //                     and written as (v > 0).
 //   k_region_stack    one lane a page pixel: the workgroup first lists the regions whose boxes meet its 64 x 16 tile in
 //                     LDS, a pixel then takes the LAST region of the list that covers it with a set mask (the order of the
 //                     reference's fills), or the background stripe; both planes are written whole, once.
 // These kernels are small and latency-bound; every value is written with plain vector stores.
 #include "vkx_internal.h"
-#include "vkx_resize_cubic.h"
+#include "vkx_resize_pixel.h"
 #include "vkx_warp.h"
 
 #include <algorithm>
@@ -47,7 +47,7 @@ struct ResizeRec {
     long long img_step, msk_step;
     int sh, sw, dh, dw;
     long long img_off, msk_off;
-    long long tab_off;                          // int xofs[dw], yofs[dh]; short xa[4 dw], yb[4 dh] from there
+    long long tab_off;                          // the pair's 4-tap block (vkd::pack_taps), bytes from the start of the staged block
 };
 
 struct ExtentRec { long long off; int h, w; };
@@ -117,28 +117,27 @@ __global__ void __launch_bounds__(256) k_region_resize(const ResizeRec *__restri
                                                        uint8_t *__restrict__ dst)
 {
     const ResizeRec r = recs[blockIdx.x];
-    const int *xofs = (const int *)(tabs + r.tab_off), *yofs = xofs + r.dw;
-    const short *xa = (const short *)(yofs + r.dh), *yb = xa + 4 * (ptrdiff_t)r.dw;
+    const vkd::TapView<short> tab(tabs + r.tab_off, 4, r.dh, r.dw);
     const int tiles_x = (r.dw + 63) >> 6, tiles = tiles_x * ((r.dh + 3) >> 2);
     const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
     for (int t = blockIdx.y; t < tiles; t += gridDim.y) {
         const int x = (t % tiles_x) * 64 + lx, y = (t / tiles_x) * 4 + ly;
         if (x >= r.dw || y >= r.dh) continue;
-        const int x0 = xofs[x], y0 = yofs[y];
+        const int x0 = tab.xofs[x], y0 = tab.yofs[y];
         const uint8_t *msk = r.msk;
         const long long ms = r.msk_step;
         if (r.msk_off >= 0) {
             uint8_t m;
-            vkd::cubic_pixel_u8<1>([&](int sy, int b) { return msk[(ptrdiff_t)sy * ms + b] ? 255 : 0; }, r.sh, r.sw, x0, y0,
-                                   xa + 4 * x, yb + 4 * y, &m);
+            vkd::taps_pixel_u8<1, 4>([&](int sy, int b) { return msk[(ptrdiff_t)sy * ms + b] ? 255 : 0; }, r.sh, r.sw, x0, y0,
+                                     tab.xcoef + 4 * x, tab.ycoef + 4 * y, &m);
             dst[r.msk_off + (ptrdiff_t)y * r.dw + x] = m ? 1 : 0;
         }
         if (r.img_off >= 0) {
             const uint8_t *img = r.img;
             const long long is = r.img_step;
             uint8_t px[3];
-            vkd::cubic_pixel_u8<3>([&](int sy, int b) { return (int)img[(ptrdiff_t)sy * is + b]; }, r.sh, r.sw, x0, y0, xa + 4 * x,
-                                   yb + 4 * y, px);
+            vkd::taps_pixel_u8<3, 4>([&](int sy, int b) { return (int)img[(ptrdiff_t)sy * is + b]; }, r.sh, r.sw, x0, y0, tab.xcoef + 4 * x,
+                                     tab.ycoef + 4 * y, px);
             uint8_t *o = dst + r.img_off + ((ptrdiff_t)y * r.dw + x) * 3;
             o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
         }
@@ -324,26 +323,18 @@ VKX_EXPORT int vkx_region_resize_dev(vkx_ctx *ctx, const vkx_region_resize_pair 
             return rc;
         groups = pair_groups(p.dst_h, p.dst_w, groups);
         tab_off[i] = bytes;
-        bytes += ((sizeof(int) + 4 * sizeof(short)) * ((size_t)p.dst_w + p.dst_h) + 15) & ~(size_t)15;
+        bytes += (vkd::pack_taps(4, false, p.src_h, p.src_w, p.dst_h, p.dst_w, nullptr) + 15) & ~(size_t)15;
     }
     VKX_REQUIRE(!ranges_overlap(ranges), "destinations overlap one another");
     vkx_tables tab(ctx);
     int rc;
     if ((rc = tab.take(bytes))) return rc;
     ResizeRec *recs = tab.at<ResizeRec>(0);
-    vkd::AxisTable tx, ty;
     for (int i = 0; i < n_pairs; i++) {
         const vkx_region_resize_pair &p = pairs_host[i];
         recs[i] = ResizeRec{p.src_image, p.src_mask, p.src_image_step, p.src_mask_step, p.src_h, p.src_w, p.dst_h, p.dst_w,
                             p.dst_image_off, p.dst_mask_off, (long long)tab_off[i]};
-        vkd::build_axis(p.src_w, p.dst_w, &tx);
-        vkd::build_axis(p.src_h, p.dst_h, &ty);
-        int *xofs = tab.at<int>(tab_off[i]), *yofs = xofs + p.dst_w;
-        short *xa = (short *)(yofs + p.dst_h), *yb = xa + 4 * (size_t)p.dst_w;
-        memcpy(xofs, tx.ofs.data(), sizeof(int) * p.dst_w);
-        memcpy(yofs, ty.ofs.data(), sizeof(int) * p.dst_h);
-        memcpy(xa, tx.icoef.data(), sizeof(short) * 4 * p.dst_w);
-        memcpy(yb, ty.icoef.data(), sizeof(short) * 4 * p.dst_h);
+        vkd::pack_taps(4, false, p.src_h, p.src_w, p.dst_h, p.dst_w, tab.at<unsigned char>(tab_off[i]));
     }
     if ((rc = tab.copy_to(&ctx->rf_tables, (size_t)64 << 10))) return rc;
     {

@@ -1,100 +1,59 @@
-// cv.resize(src, dsize, interpolation=INTER_CUBIC) on gfx950 (reference: Image.to_resized_image element/image.py:836-852,
+// cv.resize(src, dsize, interpolation) on gfx950 (reference: Image.to_resized_image element/image.py:836-852,
 // Mask.to_resized_mask element/mask.py:454-479, ScoreMap.to_resized_score_map element/score_map.py:616-640; first
-// user on the path: the bottom layer of fill_page_inactive_region, pipeline/text_detection/page_distortion.py:146-161).
+// user on the path: the bottom layer of fill_page_inactive_region, pipeline/text_detection/page_distortion.py:146-161;
+// every interpolation PageResizingStep samples, pipeline/text_detection/page_resizing.py:110-181 via utility/opt.py:125-148).
 //
-// Separable Keys cubic (A = -0.75), taps s-1 .. s+2 with border replication.  The per-column / per-row tap offsets and
-// coefficients depend on one index only, so the host evaluates them once (float32 arithmetic in OpenCV's order, 11-bit
-// fixed point for uint8) and stages two small tables; the kernel is a pure gather: one lane per destination pixel,
-// 4 x 4 taps per channel, int32 accumulation with the (sum + 2^21) >> 22 rounding for uint8, float32 left-to-right
-// sums for float32.  Bound by HBM/L2 reads of the source (each source row is reused by ~4/scale destination rows).
+// The routing rule, the host-built axis tables and the blocks they travel in are vkx_resize_axes.h's, the arithmetic of a
+// destination pixel vkx_resize_pixel.h's; here are the kernels -- the direct form, one lane a destination pixel on the 64 x 4
+// tile of its workgroup, and the separable form of CUBIC / LANCZOS4 (k_resize_sep) --, the context's cache of table blocks and
+// the dispatch.  The direct kernels are pure gathers, bound by HBM/L2 reads of the source (each source row is reused by
+// ~4/scale destination rows).
 #include "vkx_internal.h"
-#include "vkx_resize_cubic.h"
-#include "vkx_resize_axes.h"
+#include "vkx_resize_pixel.h"
 
 #include <algorithm>
-#include <cfloat>
-#include <climits>
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <utility>
+#include <memory>
+#include <type_traits>
 
 namespace {
 
-using vkd::cv_round_host;
-using vkd::AxisTable;
-using vkd::cubic_coeffs;
-using vkd::build_axis;
 using vkd::clip_index;
-using vkd::AxisTable8;
-using vkd::build_axis8;
-using vkd::build_linear_exact_axis;
-using vkd::AreaTab;
-using vkd::build_area_tab;
 
-template <int CN>
-__global__ void __launch_bounds__(256) k_resize_cubic_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
-                                                         uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                         const int *__restrict__ xofs, const short *__restrict__ xa,
-                                                         const int *__restrict__ yofs, const short *__restrict__ yb)
+// the destination pixel of a lane of the direct kernels (a 64 x 4 tile a workgroup); false: the lane is outside the plane
+__device__ __forceinline__ bool lane_pixel(int dh, int dw, int &dy, int &dx)
 {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    vkd::cubic_pixel_u8<CN>([&](int y, int b) { return (int)src[(ptrdiff_t)y * sstride + b]; }, sh, sw, xofs[dx], yofs[dy],
-                            xa + dx * 4, yb + dy * 4, dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN);
+    dx = blockIdx.x * 64 + (threadIdx.x & 63);
+    dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    return dx < dw && dy < dh;
 }
 
-__global__ void __launch_bounds__(256) k_resize_cubic_f32(const float *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
-                                                          float *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                          const int *__restrict__ xofs, const float *__restrict__ xc,
-                                                          const int *__restrict__ yofs, const float *__restrict__ yc)
+// INTER_LINEAR (KS = 2), INTER_CUBIC (4), INTER_LANCZOS4 (8) on uint8, tables as vkd::TapView lays them out
+template <int CN, int KS>
+__global__ void __launch_bounds__(256) k_resize_taps_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
+                                                        uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
+                                                        const int *__restrict__ xofs, const short *__restrict__ xa,
+                                                        const int *__restrict__ yofs, const short *__restrict__ yb)
 {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const int x0 = xofs[dx], y0 = yofs[dy];
-    int sx[4];
-    float ax[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) { sx[j] = clip_index(x0 - 1 + j, sw); ax[j] = xc[dx * 4 + j]; }
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float *row = src + (ptrdiff_t)clip_index(y0 - 1 + k, sh) * sstride;
-        const float t0 = row[sx[0]] * ax[0], t1 = row[sx[1]] * ax[1], t2 = row[sx[2]] * ax[2], t3 = row[sx[3]] * ax[3];
-        float hsum = t0 + t1;
-        hsum = hsum + t2;
-        hsum = hsum + t3;
-        const float term = hsum * yc[dy * 4 + k];
-        v = k == 0 ? term : v + term;
-    }
-    dst[(ptrdiff_t)dy * dstride + dx] = v;
-}
-
-// INTER_LINEAR (uint8): 2 x 2 taps, horizontal pass in int32 with 11-bit coefficients, OpenCV's vertical rounding
-// uchar((((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2); tables as for the cubic kernel (2 entries).
-template <int CN>
-__global__ void __launch_bounds__(256) k_resize_linear_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
-                                                          uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                          const int *__restrict__ xofs, const short *__restrict__ xa,
-                                                          const int *__restrict__ yofs, const short *__restrict__ yb)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const int sx0 = xofs[dx] * CN, sx1 = clip_index(xofs[dx] + 1, sw) * CN;
-    const int a0 = xa[dx * 2], a1 = xa[dx * 2 + 1];
-    const int b0 = yb[dy * 2], b1 = yb[dy * 2 + 1];
-    const uint8_t *r0 = src + (ptrdiff_t)clip_index(yofs[dy], sh) * sstride;
-    const uint8_t *r1 = src + (ptrdiff_t)clip_index(yofs[dy] + 1, sh) * sstride;
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    const auto load = [&](int y, int b) { return (int)(src + (ptrdiff_t)y * sstride)[b]; };      // (row pointer + int index)
     uint8_t *out = dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN;
-#pragma unroll
-    for (int c = 0; c < CN; c++) {
-        const int h0 = r0[sx0 + c] * a0 + r0[sx1 + c] * a1;
-        const int h1 = r1[sx0 + c] * a0 + r1[sx1 + c] * a1;
-        out[c] = (uint8_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
-    }
+    if constexpr (KS == 2) vkd::linear_pixel_u8<CN>(load, sh, sw, xofs[dx], yofs[dy], xa + dx * KS, yb + dy * KS, out);
+    else vkd::taps_pixel_u8<CN, KS>(load, sh, sw, xofs[dx], yofs[dy], xa + dx * KS, yb + dy * KS, out);
+}
+
+template <int KS>
+__global__ void __launch_bounds__(256) k_resize_taps_f32(const float *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
+                                                         float *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
+                                                         const int *__restrict__ xofs, const float *__restrict__ xc,
+                                                         const int *__restrict__ yofs, const float *__restrict__ yc)
+{
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    dst[(ptrdiff_t)dy * dstride + dx] = vkd::taps_pixel_f32<KS>([&](int y, int x) { return src[(ptrdiff_t)y * sstride + x]; }, sh, sw,
+                                                                xofs[dx], yofs[dy], xc + dx * KS, yc + dy * KS);
 }
 
 // the exact 2 x 2 shrink cv.resize routes to INTER_AREA
@@ -102,48 +61,96 @@ template <int CN>
 __global__ void __launch_bounds__(256) k_resize_half_u8(const uint8_t *__restrict__ src, ptrdiff_t sstride,
                                                         uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride)
 {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
     const uint8_t *p = src + (ptrdiff_t)(2 * dy) * sstride + (ptrdiff_t)(2 * dx) * CN;
-#pragma unroll
-    for (int c = 0; c < CN; c++)
-        dst[(ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN + c] = (uint8_t)((p[c] + p[CN + c] + p[sstride + c] + p[sstride + CN + c] + 2) >> 2);
+    vkd::half_pixel_u8<CN>([&](int y, int x, int c) { return (int)p[y * sstride + x * CN + c]; }, dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN);
 }
 
-// INTER_NEAREST: source index min(floor(d * scale), size - 1), scale in double
+// INTER_NEAREST and INTER_NEAREST_EXACT (ifx .. ify0: the 16.16 step and start of x, then of y); CN = bytes per element
+// (4 = one float32)
 template <int CN>
 __global__ void __launch_bounds__(256) k_resize_nearest_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
                                                            uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
                                                            double ifx, double ify)
 {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const int sx = min((int)floor(dx * ifx), sw - 1), sy = min((int)floor(dy * ify), sh - 1);
-    const uint8_t *p = src + (ptrdiff_t)sy * sstride + (ptrdiff_t)sx * CN;
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    const uint8_t *p = src + (ptrdiff_t)vkd::nearest_index(dy, ify, sh) * sstride + (ptrdiff_t)vkd::nearest_index(dx, ifx, sw) * CN;
 #pragma unroll
     for (int c = 0; c < CN; c++) dst[(ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN + c] = p[c];
 }
 
-void build_linear_axis(int ssize, int dsize, bool horizontal, std::vector<int> *ofs, std::vector<short> *coef)
+template <int CN>
+__global__ void __launch_bounds__(256) k_resize_nearest_exact(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
+                                                              uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
+                                                              int ifx, int ifx0, int ify, int ify0)
 {
-    ofs->resize(dsize); coef->resize((size_t)dsize * 2);
-    const double inv_scale = (double)dsize / ssize, scale = 1. / inv_scale;
-    for (int d = 0; d < dsize; d++) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s0 = (int)std::floor(f);
-        f -= s0;
-        if (horizontal) {
-            if (s0 < 0) { f = 0; s0 = 0; }
-            if (s0 >= ssize - 1) { f = 0; s0 = ssize - 1; }
-        }
-        (*ofs)[d] = s0;
-        const float c[2] = {1.f - f, f};
-        for (int k = 0; k < 2; k++) {
-            const int r = cv_round_host(c[k] * 2048.f);
-            (*coef)[(size_t)d * 2 + k] = (short)(r < -32768 ? -32768 : (r > 32767 ? 32767 : r));
-        }
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    const uint8_t *p = src + (ptrdiff_t)vkd::nearest_exact_index(dy, ify, ify0, sh) * sstride +
+                       (ptrdiff_t)vkd::nearest_exact_index(dx, ifx, ifx0, sw) * CN;
+#pragma unroll
+    for (int c = 0; c < CN; c++) dst[(ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN + c] = p[c];
+}
+
+// INTER_LINEAR_EXACT on uint8 (a LINEAR_EXACT block and its ranges), and INTER_LINEAR on float32
+template <int CN>
+__global__ void __launch_bounds__(256) k_resize_linear_exact_u8(const uint8_t *__restrict__ src, ptrdiff_t sstride,
+                                                                uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
+                                                                const int *__restrict__ xofs, const int *__restrict__ xw,
+                                                                const int *__restrict__ yofs, const int *__restrict__ yw,
+                                                                int xmin, int xmax, int ymin, int ymax)
+{
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    const int p[4] = {xmin, xmax, ymin, ymax};
+    vkd::linear_exact_pixel_u8<CN>([&](int y, int below, int x, int c) { return (unsigned)(src + (ptrdiff_t)y * sstride + (below ? sstride : 0))[x * CN + c]; },
+                                   vkd::LinearExactView{xofs, xw, yofs, yw}, p, dh, dw, dy, dx, dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN);
+}
+
+__global__ void __launch_bounds__(256) k_resize_linear_f32(const float *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
+                                                           float *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
+                                                           double scale_x, double scale_y)
+{
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    dst[(ptrdiff_t)dy * dstride + dx] = vkd::linear_pixel_f32([&](int y, int x) { return src[(ptrdiff_t)y * sstride + x]; }, sh, sw, dy, dx,
+                                                              scale_x, scale_y);
+}
+
+// INTER_AREA: integer scale factors (box sums), and fractional ones (the weighted runs of an AREA block)
+template <int CN, bool F32>
+__global__ void __launch_bounds__(256) k_resize_area_fast(const void *__restrict__ src_, ptrdiff_t sstride, void *__restrict__ dst_,
+                                                          int dh, int dw, ptrdiff_t dstride, int isx, int isy)
+{
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    if (F32) {
+        const float *S = (const float *)src_ + (ptrdiff_t)(dy * isy) * sstride + (ptrdiff_t)(dx * isx);
+        ((float *)dst_)[(ptrdiff_t)dy * dstride + dx] =
+            vkd::area_fast_f32([&](int y, int x) { return S[(ptrdiff_t)y * sstride + x]; }, isx, isy);
+    } else {
+        const uint8_t *S = (const uint8_t *)src_ + (ptrdiff_t)(dy * isy) * sstride + (ptrdiff_t)(dx * isx) * CN;
+        uint8_t *out = (uint8_t *)dst_ + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN;
+#pragma unroll
+        for (int c = 0; c < CN; c++)
+            out[c] = vkd::area_fast_u8([&](int y, int x) { return (int)S[(ptrdiff_t)y * sstride + x * CN + c]; }, isx, isy);
+    }
+}
+
+template <int CN, bool F32>
+__global__ void __launch_bounds__(256) k_resize_area(const void *__restrict__ src_, ptrdiff_t sstride, void *__restrict__ dst_, int dh,
+                                                     int dw, ptrdiff_t dstride, const vkd::AreaView t)
+{
+    int dy, dx;
+    if (!lane_pixel(dh, dw, dy, dx)) return;
+    if constexpr (F32) {
+        vkd::area_pixel<1, true>([&](int y, int x, int) { return ((const float *)src_)[(ptrdiff_t)y * sstride + x]; }, t, dy, dx,
+                                 (float *)dst_ + (ptrdiff_t)dy * dstride + dx);
+    } else {
+        vkd::area_pixel<CN, false>([&](int y, int x, int c) { return (float)((const uint8_t *)src_)[(ptrdiff_t)y * sstride + x * CN + c]; }, t,
+                                   dy, dx, (uint8_t *)dst_ + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN);
     }
 }
 
@@ -175,406 +182,38 @@ __global__ void __launch_bounds__(256) k_zoom_finish(const uint8_t *__restrict__
     dst[(ptrdiff_t)y * dstride + xe] = (uint8_t)v;
 }
 
-
-// ---- the other interpolations PageResizingStep samples (pipeline/text_detection/page_resizing.py:110-181 via
-// utility/opt.py:125-148); arithmetic as restated in oracle/vkx_oracle.c.
-
-}  // namespace
-namespace vkd {   // (declared in vkx_resize_axes.h: seal_fill.hip builds the same tables)
-// interpolateLanczos4 (imgproc): 8 taps s-3 .. s+4
-void lanczos4_coeffs(float x, float c[8])
-{
-    static const double s45 = 0.70710678118654752440084436210485;
-    static const double cs[8][2] = {{1, 0}, {-s45, -s45}, {0, 1}, {s45, -s45}, {-1, 0}, {s45, s45}, {0, -1}, {-s45, s45}};
-    const double pi = 3.1415926535897932384626433832795;
-    if (x < FLT_EPSILON) {
-        for (int i = 0; i < 8; i++) c[i] = 0;
-        c[3] = 1;
-        return;
-    }
-    float sum = 0;
-    const double y0 = -(x + 3) * pi * 0.25, s0 = std::sin(y0), c0 = std::cos(y0);
-    for (int i = 0; i < 8; i++) {
-        const double y = -(x + 3 - i) * pi * 0.25;
-        c[i] = (float)((cs[i][0] * s0 + cs[i][1] * c0) / (y * y));
-        sum += c[i];
-    }
-    sum = 1.f / sum;
-    for (int i = 0; i < 8; i++) c[i] *= sum;
-}
-
-void build_axis8(int ssize, int dsize, AxisTable8 *t)
-{
-    t->ofs.resize(dsize); t->coef.resize((size_t)dsize * 8); t->icoef.resize((size_t)dsize * 8);
-    const double inv_scale = (double)dsize / ssize, scale = 1. / inv_scale;
-    for (int d = 0; d < dsize; d++) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        const int s0 = (int)std::floor(f);
-        f -= s0;
-        t->ofs[d] = s0;
-        lanczos4_coeffs(f, &t->coef[(size_t)d * 8]);
-        for (int k = 0; k < 8; k++) {
-            const int r = cv_round_host(t->coef[(size_t)d * 8 + k] * 2048.f);
-            t->icoef[(size_t)d * 8 + k] = (short)(r < -32768 ? -32768 : (r > 32767 ? 32767 : r));
-        }
-    }
-}
-}  // namespace vkd
-namespace {
-
-template <int CN>
-__global__ void __launch_bounds__(256) k_resize_lanczos4_u8(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
-                                                            uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                            const int *__restrict__ xofs, const short *__restrict__ xa,
-                                                            const int *__restrict__ yofs, const short *__restrict__ yb)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const int x0 = xofs[dx], y0 = yofs[dy];
-    int sx[8], ax[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) { sx[j] = clip_index(x0 - 3 + j, sw) * CN; ax[j] = xa[dx * 8 + j]; }
-    unsigned acc[CN];
-#pragma unroll
-    for (int c = 0; c < CN; c++) acc[c] = 0;
-    for (int k = 0; k < 8; k++) {
-        const uint8_t *row = src + (ptrdiff_t)clip_index(y0 - 3 + k, sh) * sstride;
-        const int b = yb[dy * 8 + k];
-#pragma unroll
-        for (int c = 0; c < CN; c++) {
-            unsigned hsum = 0;
-#pragma unroll
-            for (int j = 0; j < 8; j++) hsum += (unsigned)((int)row[sx[j] + c] * ax[j]);
-            acc[c] += (unsigned)__mul24((int)hsum, b);      // |hsum| < 2^20: same low 32 bits as the 32-bit product
-        }
-    }
-    uint8_t *out = dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN;
-#pragma unroll
-    for (int c = 0; c < CN; c++) {
-        const int r = ((int)(acc[c] + (1u << 21))) >> 22;
-        out[c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-    }
-}
-
-__global__ void __launch_bounds__(256) k_resize_lanczos4_f32(const float *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
-                                                             float *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                             const int *__restrict__ xofs, const float *__restrict__ xc,
-                                                             const int *__restrict__ yofs, const float *__restrict__ yc)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const int x0 = xofs[dx], y0 = yofs[dy];
-    int sx[8];
-    float ax[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) { sx[j] = clip_index(x0 - 3 + j, sw); ax[j] = xc[dx * 8 + j]; }
-    float v = 0.f;
-    for (int k = 0; k < 8; k++) {
-        const float *row = src + (ptrdiff_t)clip_index(y0 - 3 + k, sh) * sstride;
-        float hsum = row[sx[0]] * ax[0];
-#pragma unroll
-        for (int j = 1; j < 8; j++) { const float t = row[sx[j]] * ax[j]; hsum = hsum + t; }
-        const float term = hsum * yc[dy * 8 + k];
-        v = k == 0 ? term : v + term;
-    }
-    dst[(ptrdiff_t)dy * dstride + dx] = v;
-}
-
-// INTER_NEAREST_EXACT (resizeNN_bitexact): 16.16 index arithmetic; CN = bytes per element (4 = one float32)
-template <int CN>
-__global__ void __launch_bounds__(256) k_resize_nearest_exact(const uint8_t *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
-                                                              uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                              int ifx, int ifx0, int ify, int ify0)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const int sx = min((int)(((long long)ifx * dx + ifx0) >> 16), sw - 1);
-    const int sy = min((int)(((long long)ify * dy + ify0) >> 16), sh - 1);
-    const uint8_t *p = src + (ptrdiff_t)sy * sstride + (ptrdiff_t)sx * CN;
-#pragma unroll
-    for (int c = 0; c < CN; c++) dst[(ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN + c] = p[c];
-}
-
-}  // namespace
-namespace vkd {   // (declared in vkx_resize_axes.h: seal_fill.hip builds the same tables)
-// INTER_LINEAR_EXACT on uint8 (resize_bitExact): per axis (offset, 8.8 weight of the second sample) and the range
-// [mn, mx) of destination indices that interpolate; outside it the first / last source sample is copied
-void build_linear_exact_axis(int ssize, int dsize, std::vector<int> *ofs, std::vector<int> *w1, int *dmin, int *dmax)
-{
-    ofs->resize(dsize); w1->resize(dsize);
-    const double inv_scale = (double)dsize / ssize, scale = 1.0 / inv_scale;
-    int mn = 0, mx = dsize;
-    for (int d = 0; d < dsize; d++) {
-        const double fval = scale * ((double)d + 0.5) - 0.5;
-        int ival = (int)std::floor(fval);
-        (*w1)[d] = 0;
-        if (ival >= 0 && ssize > 1) {
-            if (ival < ssize - 1) (*w1)[d] = (int)std::nearbyint((fval - (double)ival) * 256.0);
-            else { ival = ssize - 1; mx = std::min(mx, d); }
-        } else { mn = std::max(mn, d + 1); ival = 0; }
-        (*ofs)[d] = ival;
-    }
-    if (mx < mn) mx = mn;
-    *dmin = mn; *dmax = mx;
-}
-}  // namespace vkd
-namespace {
-
-template <int CN>
-__global__ void __launch_bounds__(256) k_resize_linear_exact_u8(const uint8_t *__restrict__ src, ptrdiff_t sstride,
-                                                                uint8_t *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                                const int *__restrict__ xofs, const int *__restrict__ xw,
-                                                                const int *__restrict__ yofs, const int *__restrict__ yw,
-                                                                int xmin, int xmax, int ymin, int ymax)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const bool two = dy >= ymin && dy < ymax;
-    const int r0 = dy < ymin ? 0 : (dy >= ymax ? yofs[dh - 1] : yofs[dy]);
-    const uint8_t *S0 = src + (ptrdiff_t)r0 * sstride, *S1 = S0 + (two ? sstride : 0);
-    // horizontal taps: both on the first / last sample outside [xmin, xmax)
-    const int xa = dx < xmin ? 0 : (dx >= xmax ? xofs[dw - 1] : xofs[dx]);
-    const bool xin = dx >= xmin && dx < xmax;
-    const unsigned w1 = xin ? (unsigned)xw[dx] : 0u, w0 = 256u - w1;
-    const int xb = xin ? xa + 1 : xa;
-    const unsigned b1 = two ? (unsigned)yw[dy] : 0u, b0 = 256u - b1;
-    uint8_t *out = dst + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN;
-#pragma unroll
-    for (int c = 0; c < CN; c++) {
-        const unsigned h0 = w0 * S0[xa * CN + c] + w1 * S0[xb * CN + c];
-        unsigned r;
-        if (two) {
-            const unsigned h1 = w0 * S1[xa * CN + c] + w1 * S1[xb * CN + c];
-            r = (h0 * b0 + h1 * b1 + (1u << 15)) >> 16;
-        } else {
-            r = (h0 + 128u) >> 8;
-        }
-        out[c] = (uint8_t)(r > 255u ? 255u : r);
-    }
-}
-
-// INTER_LINEAR on float32 (what INTER_LINEAR_EXACT falls back to for a ScoreMap)
-__global__ void __launch_bounds__(256) k_resize_linear_f32(const float *__restrict__ src, int sh, int sw, ptrdiff_t sstride,
-                                                           float *__restrict__ dst, int dh, int dw, ptrdiff_t dstride,
-                                                           double scale_x, double scale_y)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    float fy = (float)((dy + 0.5) * scale_y - 0.5);
-    int y0 = (int)floorf(fy);
-    fy -= y0;
-    if (y0 < 0) { y0 = 0; fy = 0; }
-    if (y0 >= sh - 1) { y0 = sh - 1; fy = 0; }
-    float fx = (float)((dx + 0.5) * scale_x - 0.5);
-    int x0 = (int)floorf(fx);
-    fx -= x0;
-    if (x0 < 0) { x0 = 0; fx = 0; }
-    if (x0 >= sw - 1) { x0 = sw - 1; fx = 0; }
-    const int x1 = clip_index(x0 + 1, sw);
-    const float *S0 = src + (ptrdiff_t)y0 * sstride, *S1 = src + (ptrdiff_t)clip_index(y0 + 1, sh) * sstride;
-    const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
-    const float p0 = S0[x0] * a0, p1 = S0[x1] * a1, q0 = S1[x0] * a0, q1 = S1[x1] * a1;
-    const float h0 = p0 + p1, h1 = q0 + q1;
-    const float t0 = h0 * b0, t1 = h1 * b1;
-    dst[(ptrdiff_t)dy * dstride + dx] = t0 + t1;
-}
-
-// INTER_AREA, integer scale factors (ResizeAreaFast): box sums, then * (1.f / area) (vkd::area_fast_*)
-template <int CN, bool F32>
-__global__ void __launch_bounds__(256) k_resize_area_fast(const void *__restrict__ src_, ptrdiff_t sstride, void *__restrict__ dst_,
-                                                          int dh, int dw, ptrdiff_t dstride, int isx, int isy)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    if (F32) {
-        const float *S = (const float *)src_ + (ptrdiff_t)(dy * isy) * sstride + (ptrdiff_t)(dx * isx);
-        ((float *)dst_)[(ptrdiff_t)dy * dstride + dx] =
-            vkd::area_fast_f32([&](int y, int x) { return S[(ptrdiff_t)y * sstride + x]; }, isx, isy);
-    } else {
-        const uint8_t *S = (const uint8_t *)src_ + (ptrdiff_t)(dy * isy) * sstride + (ptrdiff_t)(dx * isx) * CN;
-        uint8_t *out = (uint8_t *)dst_ + (ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN;
-#pragma unroll
-        for (int c = 0; c < CN; c++)
-            out[c] = vkd::area_fast_u8([&](int y, int x) { return (int)S[(ptrdiff_t)y * sstride + x * CN + c]; }, isx, isy);
-    }
-}
-
-}  // namespace
-namespace vkd {   // (declared in vkx_resize_axes.h: seal_fill.hip builds the same tables)
-// INTER_AREA, fractional scale (ResizeArea): computeResizeAreaTab's (source index, weight) runs per destination index
-void build_area_tab(int ssize, int dsize, double scale, AreaTab *t)
-{
-    t->start.assign(dsize + 1, 0); t->si.clear(); t->alpha.clear();
-    for (int dx = 0; dx < dsize; dx++) {
-        t->start[dx] = (int)t->si.size();
-        const double fsx1 = dx * scale, fsx2 = fsx1 + scale;
-        const double cell = std::min(scale, ssize - fsx1);
-        int sx1 = (int)std::ceil(fsx1), sx2 = (int)std::floor(fsx2);
-        sx2 = std::min(sx2, ssize - 1);
-        sx1 = std::min(sx1, sx2);
-        if (sx1 - fsx1 > 1e-3) { t->si.push_back(sx1 - 1); t->alpha.push_back((float)((sx1 - fsx1) / cell)); }
-        for (int sx = sx1; sx < sx2; sx++) { t->si.push_back(sx); t->alpha.push_back((float)(1.0 / cell)); }
-        if (fsx2 - sx2 > 1e-3) { t->si.push_back(sx2); t->alpha.push_back((float)(std::min(std::min(fsx2 - sx2, 1.), cell) / cell)); }
-    }
-    t->start[dsize] = (int)t->si.size();
-}
-}  // namespace vkd
-namespace {
-
-template <int CN, bool F32>
-__global__ void __launch_bounds__(256) k_resize_area(const void *__restrict__ src_, ptrdiff_t sstride, void *__restrict__ dst_, int dh,
-                                                     int dw, ptrdiff_t dstride, const int *__restrict__ xstart,
-                                                     const int *__restrict__ xsi, const float *__restrict__ xal,
-                                                     const int *__restrict__ ystart, const int *__restrict__ ysi,
-                                                     const float *__restrict__ yal)
-{
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= dw || dy >= dh) return;
-    const int x0 = xstart[dx], x1 = xstart[dx + 1], y0 = ystart[dy], y1 = ystart[dy + 1];
-    float sum[CN];
-#pragma unroll
-    for (int c = 0; c < CN; c++) sum[c] = 0.f;
-    for (int j = y0; j < y1; j++) {
-        const float beta = yal[j];
-        float buf[CN];
-#pragma unroll
-        for (int c = 0; c < CN; c++) buf[c] = 0.f;
-        for (int k = x0; k < x1; k++) {
-            const float alpha = xal[k];
-#pragma unroll
-            for (int c = 0; c < CN; c++) {
-                const float v = F32 ? ((const float *)src_)[(ptrdiff_t)ysi[j] * sstride + xsi[k]]
-                                    : (float)((const uint8_t *)src_)[(ptrdiff_t)ysi[j] * sstride + xsi[k] * CN + c];
-                const float t = v * alpha;
-                buf[c] = buf[c] + t;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < CN; c++) {
-            const float t = beta * buf[c];
-            sum[c] = j == y0 ? t : sum[c] + t;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < CN; c++) {
-        if (F32) ((float *)dst_)[(ptrdiff_t)dy * dstride + dx] = sum[c];
-        else {
-            const int r = vkd::cv_round(sum[c]);
-            ((uint8_t *)dst_)[(ptrdiff_t)dy * dstride + (ptrdiff_t)dx * CN + c] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-        }
-    }
-}
-
-// Host-built tables of one resize geometry in device memory, from the ctx cache when the geometry was seen recently.
-// `build` fills the host arrays (kept alive until the upload has completed) and the metadata on a miss only.
-template <class Build>
-int cached_tables(vkx_ctx *ctx, const int key[6], Build build, std::vector<const void *> *ptrs, const std::vector<int> **meta)
+// The table block of one resize geometry in device memory, from the ctx cache when the geometry was seen recently.  `pack` is
+// a packer of vkx_resize_axes.h bound to the geometry -- pack(nullptr, meta) returns the block's bytes, pack(address, meta)
+// writes it and the small host-side metadata that goes with it -- and runs on a miss only.  A block is one contiguous run of
+// tables (its slot holds 256 bytes at least): a table starts where the one before it ends, so the coefficient tables of a tap
+// block are aligned to 4 bytes only, which is all k_resize_sep and the direct kernels ask of them (int, short and float loads).
+template <class Pack>
+int cached_tables(vkx_ctx *ctx, const int (&key)[6], Pack pack, const unsigned char **block, const std::vector<int> **meta)
 {
     vkx_ctx::ResizeTabs *slot = nullptr;
     for (auto &t : ctx->resize_tabs)
         if (std::equal(key, key + 6, t.key)) slot = &t;
-    int n = 0;
     if (!slot) {
         slot = &ctx->resize_tabs[0];
         for (auto &t : ctx->resize_tabs)
             if (t.stamp < slot->stamp) slot = &t;
-        std::vector<std::pair<const void *, size_t>> arrays;
+        slot->key[0] = -1;                        // invalid until the upload below has succeeded
         std::vector<int> m;
-        build(&arrays, &m);
-        if (arrays.size() > 7) return VKX_ERR_INVALID;
-        vkx_tables tab(ctx);
-        for (size_t i = 0; i < arrays.size(); i++) slot->off[i] = tab.add(arrays[i].second);
-        slot->off[7] = arrays.size();
-        slot->key[0] = -1;
-        // the tables travel as ONE copy out of the page-locked ring (which keeps them alive): no copy per table, no stream
+        // the block travels as ONE copy out of the page-locked ring (which keeps it alive): no copy per table, no stream
         // synchronisation per cache miss -- every page resizes to a geometry of its own
-        int rc = tab.bytes ? tab.take() : vkx_scratch_reserve(ctx, &slot->buf, 256);
+        vkx_tables tab(ctx);
+        int rc = tab.take(pack(nullptr, &m));
         if (rc) return rc;
-        for (size_t i = 0; i < arrays.size(); i++)
-            if (arrays[i].second) memcpy(tab.at<char>(slot->off[i]), arrays[i].first, arrays[i].second);
-        if (tab.bytes && (rc = tab.copy_to(&slot->buf, 256))) return rc;
-        slot->yofs.swap(m);
+        pack(tab.at<unsigned char>(0), &m);
+        if ((rc = tab.copy_to(&slot->buf, 256))) return rc;
+        slot->meta.swap(m);
         std::copy(key, key + 6, slot->key);
     }
-    n = (int)slot->off[7];
     slot->stamp = ++ctx->resize_clock;
-    ptrs->clear();
-    for (int i = 0; i < n; i++) ptrs->push_back((unsigned char *)slot->buf.ptr + slot->off[i]);
-    *meta = &slot->yofs;
+    *block = (const unsigned char *)slot->buf.ptr;
+    *meta = &slot->meta;
     return VKX_OK;
 }
-
-#define VKX_CN_SWITCH(cn, KERNEL, ...)                                      \
-    switch (cn) {                                                           \
-    case 1: KERNEL<1><<<grid, 256, 0, ctx->stream>>>(__VA_ARGS__); break;   \
-    case 3: KERNEL<3><<<grid, 256, 0, ctx->stream>>>(__VA_ARGS__); break;   \
-    default: KERNEL<4><<<grid, 256, 0, ctx->stream>>>(__VA_ARGS__); break;  \
-    }
-
-// interpolations shared by the uint8 and float32 entry points; elem = bytes per element for the nearest kernels
-int resize_nearest_exact(vkx_ctx *ctx, const void *src, int sh, int sw, int elem, ptrdiff_t sstride_b, void *dst, int dh, int dw,
-                         ptrdiff_t dstride_b)
-{
-    const int ifx = (int)((((long long)sw << 16) + dw / 2) / dw), ifx0 = ifx / 2 - sw % 2;
-    const int ify = (int)((((long long)sh << 16) + dh / 2) / dh), ify0 = ify / 2 - sh % 2;
-    dim3 grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
-    VKX_TIMED(ctx, "k_resize_nearest_exact");
-    VKX_CN_SWITCH(elem, k_resize_nearest_exact, (const uint8_t *)src, sh, sw, sstride_b, (uint8_t *)dst, dh, dw, dstride_b, ifx, ifx0, ify, ify0)
-    VKX_LAUNCH_CHECK();
-    return VKX_OK;
-}
-
-template <bool F32>
-int resize_area(vkx_ctx *ctx, const void *src, int sh, int sw, int cn, ptrdiff_t sstride, void *dst, int dh, int dw, ptrdiff_t dstride)
-{
-    if (dw > sw || dh > sh) {
-        vkx_set_error("INTER_AREA is implemented for shrinking only (the reference samples it only then)");
-        return VKX_ERR_UNSUPPORTED;
-    }
-    const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-    const int isx = (int)std::nearbyint(scale_x), isy = (int)std::nearbyint(scale_y);
-    dim3 grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
-    if (std::fabs(scale_x - isx) < DBL_EPSILON && std::fabs(scale_y - isy) < DBL_EPSILON) {
-        VKX_TIMED(ctx, "k_resize_area_fast");
-        switch (cn) {
-        case 1: k_resize_area_fast<1, F32><<<grid, 256, 0, ctx->stream>>>(src, sstride, dst, dh, dw, dstride, isx, isy); break;
-        case 3: k_resize_area_fast<3, F32><<<grid, 256, 0, ctx->stream>>>(src, sstride, dst, dh, dw, dstride, isx, isy); break;
-        default: k_resize_area_fast<4, F32><<<grid, 256, 0, ctx->stream>>>(src, sstride, dst, dh, dw, dstride, isx, isy); break;
-        }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    AreaTab tx, ty;     // filled on a cache miss only
-    std::vector<const void *> p;
-    const std::vector<int> *meta;
-    const int key[6] = {103, 0, sh, sw, dh, dw};
-    int rc = cached_tables(ctx, key, [&](std::vector<std::pair<const void *, size_t>> *arrays, std::vector<int> *) {
-        build_area_tab(sw, dw, scale_x, &tx);
-        build_area_tab(sh, dh, scale_y, &ty);
-        *arrays = {{tx.start.data(), sizeof(int) * tx.start.size()}, {tx.si.data(), sizeof(int) * tx.si.size()},
-                   {tx.alpha.data(), sizeof(float) * tx.alpha.size()}, {ty.start.data(), sizeof(int) * ty.start.size()},
-                   {ty.si.data(), sizeof(int) * ty.si.size()}, {ty.alpha.data(), sizeof(float) * ty.alpha.size()}};
-    }, &p, &meta);
-    if (rc) return rc;
-    VKX_TIMED(ctx, "k_resize_area");
-#define VKX_AREA_ARGS src, sstride, dst, dh, dw, dstride, (const int *)p[0], (const int *)p[1], (const float *)p[2], (const int *)p[3], (const int *)p[4], (const float *)p[5]
-    switch (cn) {
-    case 1: k_resize_area<1, F32><<<grid, 256, 0, ctx->stream>>>(VKX_AREA_ARGS); break;
-    case 3: k_resize_area<3, F32><<<grid, 256, 0, ctx->stream>>>(VKX_AREA_ARGS); break;
-    default: k_resize_area<4, F32><<<grid, 256, 0, ctx->stream>>>(VKX_AREA_ARGS); break;
-    }
-#undef VKX_AREA_ARGS
-    VKX_LAUNCH_CHECK();
-    return VKX_OK;
-}
-
 
 // ---- separable form of the CUBIC / LANCZOS4 gathers ------------------------------------------------------------------
 // One workgroup = a 64 x 16 destination tile.  The source rows the tile's 16 destination rows reach (clipped to the
@@ -775,7 +414,6 @@ int separable_rows(const std::vector<int> &yofs, int sh, int dh, int ks)
     }
     return most > kSepRows ? 0 : most;
 }
-bool separable_fits(const std::vector<int> &yofs, int sh, int dh, int ks) { return separable_rows(yofs, sh, dh, ks) != 0; }
 constexpr int kSepRowsSmall = 24;
 
 template <int KS>
@@ -798,120 +436,103 @@ void launch_sep_u8(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptr
     }
 }
 
-// The four tables (column offsets + coefficients, row offsets + coefficients) of a CUBIC (taps = 4) or LANCZOS4
-// (taps = 8) resize in device memory, from the ctx cache when the geometry was seen recently.
-int resize_tables(vkx_ctx *ctx, int taps, bool fixed, int sh, int sw, int dh, int dw, const int **xofs, const void **xcoef,
-                  const int **yofs, const void **ycoef, const std::vector<int> **yofs_host)
+// f(std::integral_constant<int, CN>()) for the channel count of a call: the CN instance of a kernel template
+template <class F>
+void with_cn(int cn, F f)
 {
-    const int key[6] = {taps, fixed ? 1 : 0, sh, sw, dh, dw};
-    vkx_ctx::ResizeTabs *slot = nullptr;
-    for (auto &t : ctx->resize_tabs)
-        if (std::equal(key, key + 6, t.key)) slot = &t;
-    if (!slot) {
-        slot = &ctx->resize_tabs[0];
-        for (auto &t : ctx->resize_tabs)
-            if (t.stamp < slot->stamp) slot = &t;
-        std::vector<int> xo, yo;
-        std::vector<float> xc, yc;
-        std::vector<short> xi, yi;
-        if (taps == 4) {
-            AxisTable tx, ty;
-            build_axis(sw, dw, &tx);
-            build_axis(sh, dh, &ty);
-            xo.swap(tx.ofs); yo.swap(ty.ofs); xc.swap(tx.coef); yc.swap(ty.coef); xi.swap(tx.icoef); yi.swap(ty.icoef);
-        } else {
-            AxisTable8 tx, ty;
-            build_axis8(sw, dw, &tx);
-            build_axis8(sh, dh, &ty);
-            xo.swap(tx.ofs); yo.swap(ty.ofs); xc.swap(tx.coef); yc.swap(ty.coef); xi.swap(tx.icoef); yi.swap(ty.icoef);
-        }
-        const size_t csz = fixed ? sizeof(short) : sizeof(float);
-        vkx_tables tab(ctx);
-        slot->off[0] = tab.add(sizeof(int) * dw);
-        slot->off[1] = tab.add(csz * taps * dw);
-        slot->off[2] = tab.add(sizeof(int) * dh);
-        slot->off[3] = tab.add(csz * taps * dh);
-        slot->key[0] = -1;                        // invalid until the upload below has succeeded
-        const void *xsrc = fixed ? (const void *)xi.data() : (const void *)xc.data();
-        const void *ysrc = fixed ? (const void *)yi.data() : (const void *)yc.data();
-        // one copy out of the page-locked ring for the four tables (the ring keeps them alive: no synchronisation)
-        int rc = tab.take();
-        if (rc) return rc;
-        memcpy(tab.at<char>(slot->off[0]), xo.data(), sizeof(int) * dw);
-        memcpy(tab.at<char>(slot->off[2]), yo.data(), sizeof(int) * dh);
-        memcpy(tab.at<char>(slot->off[1]), xsrc, csz * taps * dw);
-        memcpy(tab.at<char>(slot->off[3]), ysrc, csz * taps * dh);
-        if ((rc = tab.copy_to(&slot->buf))) return rc;
-        slot->yofs.swap(yo);
-        std::copy(key, key + 6, slot->key);
+    switch (cn) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    default: f(std::integral_constant<int, 4>()); break;
     }
-    slot->stamp = ++ctx->resize_clock;
-    unsigned char *base = (unsigned char *)slot->buf.ptr;
-    *xofs = (const int *)(base + slot->off[0]); *xcoef = base + slot->off[1];
-    *yofs = (const int *)(base + slot->off[2]); *ycoef = base + slot->off[3];
-    *yofs_host = &slot->yofs;
+}
+
+dim3 direct_grid(int dh, int dw) { return dim3(vkx_blocks(dw, 64), vkx_blocks(dh, 4)); }
+
+// CUBIC (KS = 4) and LANCZOS4 (8): the tap block from the cache, then the separable form where its tiles fit, else the direct one
+template <int KS, class T>
+int resize_taps(vkx_ctx *ctx, const T *src, int sh, int sw, int cn, ptrdiff_t sstride, T *dst, int dh, int dw, ptrdiff_t dstride)
+{
+    constexpr bool f32 = sizeof(T) == 4;
+    using CT = typename std::conditional<f32, float, short>::type;
+    const int key[6] = {KS, f32 ? 0 : 1, sh, sw, dh, dw};
+    const unsigned char *block;
+    const std::vector<int> *yofs_host;
+    int rc = cached_tables(ctx, key, [&](unsigned char *out, std::vector<int> *yofs) { return vkd::pack_taps(KS, f32, sh, sw, dh, dw, out, yofs); },
+                           &block, &yofs_host);
+    if (rc) return rc;
+    const vkd::TapView<CT> t(block, KS, dh, dw);
+    VKX_TIMED(ctx, KS == 4 ? "k_resize_cubic" : "k_resize_lanczos4");
+    const int rows = separable_rows(*yofs_host, sh, dh, KS);
+    if constexpr (f32) {
+        if (rows) k_resize_sep<float, float, float, 1, KS><<<dim3(vkx_blocks(dw, kSepTileW), vkx_blocks(dh, kSepTileH)), 256, 0, ctx->stream>>>(
+                src, sh, sw, sstride, dst, dh, dw, dstride, t.xofs, t.xcoef, t.yofs, t.ycoef);
+        else k_resize_taps_f32<KS><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, sh, sw, sstride, dst, dh, dw, dstride, t.xofs, t.xcoef, t.yofs, t.ycoef);
+    } else {
+        if (rows) launch_sep_u8<KS>(ctx, src, sh, sw, cn, sstride, dst, dh, dw, dstride, t.xofs, t.xcoef, t.yofs, t.ycoef, rows);
+        else with_cn(cn, [&](auto CN) {
+            k_resize_taps_u8<CN, KS><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, sh, sw, sstride, dst, dh, dw, dstride, t.xofs, t.xcoef, t.yofs, t.ycoef);
+        });
+    }
+    VKX_LAUNCH_CHECK();
     return VKX_OK;
+}
+
+// interpolations shared by the uint8 and float32 entry points; elem = bytes per element for the nearest kernels
+int resize_nearest(vkx_ctx *ctx, const vkd::ResizePlan &plan, const void *src, int sh, int sw, int elem, ptrdiff_t sstride_b, void *dst, int dh,
+                   int dw, ptrdiff_t dstride_b)
+{
+    const bool exact = plan.mode == vkd::M_NEAREST_EXACT;
+    VKX_TIMED(ctx, exact ? "k_resize_nearest_exact" : "k_resize_nearest");
+    with_cn(elem, [&](auto CN) {
+        if (exact) k_resize_nearest_exact<CN><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>((const uint8_t *)src, sh, sw, sstride_b, (uint8_t *)dst, dh, dw,
+                                                                                         dstride_b, plan.p[0], plan.p[1], plan.p[2], plan.p[3]);
+        else k_resize_nearest_u8<CN><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>((const uint8_t *)src, sh, sw, sstride_b, (uint8_t *)dst, dh, dw, dstride_b,
+                                                                                plan.scale_x, plan.scale_y);
+    });
+    VKX_LAUNCH_CHECK();
+    return VKX_OK;
+}
+
+template <bool F32>
+int resize_area(vkx_ctx *ctx, const vkd::ResizePlan &plan, const void *src, int sh, int sw, int cn, ptrdiff_t sstride, void *dst, int dh, int dw,
+                ptrdiff_t dstride)
+{
+    if (plan.mode == vkd::M_AREA_FAST) {
+        VKX_TIMED(ctx, "k_resize_area_fast");
+        with_cn(cn, [&](auto CN) {
+            k_resize_area_fast<CN, F32><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, sstride, dst, dh, dw, dstride, plan.p[0], plan.p[1]);
+        });
+        VKX_LAUNCH_CHECK();
+        return VKX_OK;
+    }
+    std::unique_ptr<vkd::AreaTabs> tabs;      // built on a cache miss only
+    const int key[6] = {103, 0, sh, sw, dh, dw};
+    const unsigned char *block;
+    const std::vector<int> *n;                // the entry counts of x and y
+    int rc = cached_tables(ctx, key, [&](unsigned char *out, std::vector<int> *counts) {
+        if (!tabs) tabs.reset(new vkd::AreaTabs(sh, sw, dh, dw, plan.scale_x, plan.scale_y));
+        *counts = {(int)tabs->x.si.size(), (int)tabs->y.si.size()};
+        return tabs->pack(out);
+    }, &block, &n);
+    if (rc) return rc;
+    VKX_TIMED(ctx, "k_resize_area");
+    with_cn(cn, [&](auto CN) {
+        k_resize_area<CN, F32><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, sstride, dst, dh, dw, dstride, vkd::AreaView(block, dh, dw, (*n)[0], (*n)[1]));
+    });
+    VKX_LAUNCH_CHECK();
+    return VKX_OK;
+}
+
+// the refusals of the routing rule, in the words of the exported calls
+int refuse(const vkd::ResizePlan &plan, int interpolation)
+{
+    if (plan.mode == vkd::M_REFUSED_AREA_ENLARGES) vkx_set_error("INTER_AREA is implemented for shrinking only (the reference samples it only then)");
+    else vkx_set_error("unknown interpolation code %d", interpolation);
+    return VKX_ERR_UNSUPPORTED;
 }
 
 } // namespace
-
-VKX_EXPORT int vkx_resize_cubic_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_t src_stride,
-                                       uint8_t *dst, int dh, int dw, ptrdiff_t dst_stride)
-{
-    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)sw * cn, sh);
-    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)dw * cn, dh);
-    VKX_REQUIRE_DISJOINT(src, sh, src_stride, (size_t)sw * cn, dst, dh, dst_stride, (size_t)dw * cn);
-    VKX_REQUIRE(ctx && src && dst, "NULL argument");
-    VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
-    VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");
-    const int *xofs, *yofs;
-    const void *xa, *yb;
-    const std::vector<int> *yh;
-    int rc = resize_tables(ctx, 4, true, sh, sw, dh, dw, &xofs, &xa, &yofs, &yb, &yh);
-    if (rc) return rc;
-    dim3 grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
-    VKX_TIMED(ctx, "k_resize_cubic");
-    if (const int rows = separable_rows(*yh, sh, dh, 4)) {
-        launch_sep_u8<4>(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride, xofs, (const short *)xa, yofs, (const short *)yb, rows);
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    switch (cn) {
-    case 1: k_resize_cubic_u8<1><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, xofs, (const short *)xa, yofs, (const short *)yb); break;
-    case 3: k_resize_cubic_u8<3><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, xofs, (const short *)xa, yofs, (const short *)yb); break;
-    default: k_resize_cubic_u8<4><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, xofs, (const short *)xa, yofs, (const short *)yb); break;
-    }
-    VKX_LAUNCH_CHECK();
-    return VKX_OK;
-}
-
-VKX_EXPORT int vkx_resize_cubic_f32_dev(vkx_ctx *ctx, const float *src, int sh, int sw, ptrdiff_t src_stride_el,
-                                        float *dst, int dh, int dw, ptrdiff_t dst_stride_el)
-{
-    VKX_REQUIRE_PITCH(src_stride_el, sw, sh);
-    VKX_REQUIRE_PITCH(dst_stride_el, dw, dh);
-    VKX_REQUIRE_DISJOINT(src, sh, src_stride_el * 4, (size_t)sw * 4, dst, dh, dst_stride_el * 4, (size_t)dw * 4);
-    VKX_REQUIRE(ctx && src && dst, "NULL argument");
-    VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
-    const int *xofs, *yofs;
-    const void *xc, *yc;
-    const std::vector<int> *yh;
-    int rc = resize_tables(ctx, 4, false, sh, sw, dh, dw, &xofs, &xc, &yofs, &yc, &yh);
-    if (rc) return rc;
-    dim3 grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
-    VKX_TIMED(ctx, "k_resize_cubic");
-    if (separable_fits(*yh, sh, dh, 4)) {
-        dim3 sgrid(vkx_blocks(dw, kSepTileW), vkx_blocks(dh, kSepTileH));
-        k_resize_sep<float, float, float, 1, 4><<<sgrid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el,
-                                                                                 xofs, (const float *)xc, yofs, (const float *)yc);
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    k_resize_cubic_f32<<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el, xofs,
-                                                      (const float *)xc, yofs, (const float *)yc);
-    VKX_LAUNCH_CHECK();
-    return VKX_OK;
-}
 
 VKX_EXPORT int vkx_resize_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_t src_stride, uint8_t *dst,
                                  int dh, int dw, ptrdiff_t dst_stride, int interpolation)
@@ -919,97 +540,55 @@ VKX_EXPORT int vkx_resize_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int s
     VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)sw * cn, sh);
     VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)dw * cn, dh);
     VKX_REQUIRE_DISJOINT(src, sh, src_stride, (size_t)sw * cn, dst, dh, dst_stride, (size_t)dw * cn);
-    if (interpolation == VKX_INTER_CUBIC) return vkx_resize_cubic_u8_dev(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride);
     VKX_REQUIRE(ctx && src && dst, "NULL argument");
     VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
     VKX_REQUIRE(cn == 1 || cn == 3 || cn == 4, "1, 3 or 4 channels");
-    dim3 grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
-    if (interpolation == VKX_INTER_NEAREST) {
-        const double ifx = 1. / ((double)dw / sw), ify = 1. / ((double)dh / sh);
-        VKX_TIMED(ctx, "k_resize_nearest");
-        switch (cn) {
-        case 1: k_resize_nearest_u8<1><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, ifx, ify); break;
-        case 3: k_resize_nearest_u8<3><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, ifx, ify); break;
-        default: k_resize_nearest_u8<4><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, ifx, ify); break;
-        }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    if (interpolation == VKX_INTER_NEAREST_EXACT)
-        return resize_nearest_exact(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride);
-    if (interpolation == VKX_INTER_AREA) return resize_area<false>(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride);
-    if (interpolation == VKX_INTER_LANCZOS4) {
-        const int *xofs, *yofs;
-        const void *xa, *yb;
-        const std::vector<int> *yh;
-        int rc = resize_tables(ctx, 8, true, sh, sw, dh, dw, &xofs, &xa, &yofs, &yb, &yh);
-        if (rc) return rc;
-        VKX_TIMED(ctx, "k_resize_lanczos4");
-        if (const int rows = separable_rows(*yh, sh, dh, 8)) {
-            launch_sep_u8<8>(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride, xofs, (const short *)xa, yofs, (const short *)yb, rows);
-            VKX_LAUNCH_CHECK();
-            return VKX_OK;
-        }
-        VKX_CN_SWITCH(cn, k_resize_lanczos4_u8, src, sh, sw, src_stride, dst, dh, dw, dst_stride, xofs, (const short *)xa, yofs, (const short *)yb)
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    if (interpolation == VKX_INTER_LINEAR_EXACT && !(sw == 2 * dw && sh == 2 * dh)) {
-        std::vector<int> xo, xw, yo, yw;     // filled on a cache miss only
-        std::vector<const void *> p;
-        const std::vector<int> *meta;
+    vkd::ResizePlan plan = vkd::plan_resize(false, interpolation, sh, sw, dh, dw);
+    switch (plan.mode) {
+    case vkd::M_TAPS:
+        return plan.ks == 4 ? resize_taps<4>(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride)
+                            : resize_taps<8>(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride);
+    case vkd::M_NEAREST:
+    case vkd::M_NEAREST_EXACT: return resize_nearest(ctx, plan, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride);
+    case vkd::M_AREA_FAST:
+    case vkd::M_AREA: return resize_area<false>(ctx, plan, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride);
+    case vkd::M_LINEAR_EXACT_U8: {
         const int key[6] = {105, 0, sh, sw, dh, dw};
-        int rc = cached_tables(ctx, key, [&](std::vector<std::pair<const void *, size_t>> *arrays, std::vector<int> *m) {
-            int xmin_, xmax_, ymin_, ymax_;
-            build_linear_exact_axis(sw, dw, &xo, &xw, &xmin_, &xmax_);
-            build_linear_exact_axis(sh, dh, &yo, &yw, &ymin_, &ymax_);
-            *arrays = {{xo.data(), sizeof(int) * dw}, {xw.data(), sizeof(int) * dw}, {yo.data(), sizeof(int) * dh},
-                       {yw.data(), sizeof(int) * dh}};
-            *m = {xmin_, xmax_, ymin_, ymax_};
-        }, &p, &meta);
+        const unsigned char *block;
+        const std::vector<int> *range;
+        int rc = cached_tables(ctx, key, [&](unsigned char *out, std::vector<int> *r) {
+            r->resize(4);
+            return vkd::pack_linear_exact(sh, sw, dh, dw, out, r->data());
+        }, &block, &range);
         if (rc) return rc;
-        const int xmin = (*meta)[0], xmax = (*meta)[1], ymin = (*meta)[2], ymax = (*meta)[3];
+        const int *p = range->data();
+        const vkd::LinearExactView t = vkd::LinearExactView::of(block, dh, dw);
         VKX_TIMED(ctx, "k_resize_linear_exact");
-        VKX_CN_SWITCH(cn, k_resize_linear_exact_u8, src, src_stride, dst, dh, dw, dst_stride, (const int *)p[0], (const int *)p[1], (const int *)p[2], (const int *)p[3], xmin, xmax, ymin, ymax)
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
+        with_cn(cn, [&](auto CN) {
+            k_resize_linear_exact_u8<CN><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, src_stride, dst, dh, dw, dst_stride, t.xofs, t.xw, t.yofs, t.yw, p[0], p[1], p[2], p[3]);
+        });
+        break;
     }
-    if (interpolation != VKX_INTER_LINEAR && interpolation != VKX_INTER_LINEAR_EXACT) {
-        vkx_set_error("unknown interpolation code %d", interpolation);
-        return VKX_ERR_UNSUPPORTED;
-    }
-    if (sw == 2 * dw && sh == 2 * dh) {
+    case vkd::M_HALF_U8: {
         VKX_TIMED(ctx, "k_resize_half");
-        switch (cn) {
-        case 1: k_resize_half_u8<1><<<grid, 256, 0, ctx->stream>>>(src, src_stride, dst, dh, dw, dst_stride); break;
-        case 3: k_resize_half_u8<3><<<grid, 256, 0, ctx->stream>>>(src, src_stride, dst, dh, dw, dst_stride); break;
-        default: k_resize_half_u8<4><<<grid, 256, 0, ctx->stream>>>(src, src_stride, dst, dh, dw, dst_stride); break;
-        }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
+        with_cn(cn, [&](auto CN) { k_resize_half_u8<CN><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, src_stride, dst, dh, dw, dst_stride); });
+        break;
     }
-    std::vector<int> xo, yo;
-    std::vector<short> xa, yb;
-    build_linear_axis(sw, dw, true, &xo, &xa);
-    build_linear_axis(sh, dh, false, &yo, &yb);
-    vkx_tables tab(ctx);      // one copy for the four tables, no synchronisation
-    const size_t o0 = tab.add(sizeof(int) * dw), o1 = tab.add(sizeof(short) * 2 * dw), o2 = tab.add(sizeof(int) * dh);
-    const size_t o3 = tab.add(sizeof(short) * 2 * dh);
-    int rc = tab.take();
-    if (rc) return rc;
-    memcpy(tab.at<int>(o0), xo.data(), sizeof(int) * dw);
-    memcpy(tab.at<short>(o1), xa.data(), sizeof(short) * 2 * dw);
-    memcpy(tab.at<int>(o2), yo.data(), sizeof(int) * dh);
-    memcpy(tab.at<short>(o3), yb.data(), sizeof(short) * 2 * dh);
-    if ((rc = tab.copy_to(&ctx->misc))) return rc;
-    unsigned char *base = (unsigned char *)ctx->misc.ptr;
-    const int *dxo = (const int *)(base + o0), *dyo = (const int *)(base + o2);
-    const short *dxa = (const short *)(base + o1), *dyb = (const short *)(base + o3);
-    VKX_TIMED(ctx, "k_resize_linear");
-    switch (cn) {
-    case 1: k_resize_linear_u8<1><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, dxo, dxa, dyo, dyb); break;
-    case 3: k_resize_linear_u8<3><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, dxo, dxa, dyo, dyb); break;
-    default: k_resize_linear_u8<4><<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, dxo, dxa, dyo, dyb); break;
+    case vkd::M_LINEAR_U8: {
+        // not cached: one copy of the block out of the ring, no synchronisation
+        vkx_tables tab(ctx);
+        int rc = tab.take(vkd::pack_taps(2, false, sh, sw, dh, dw, nullptr));
+        if (rc) return rc;
+        vkd::pack_taps(2, false, sh, sw, dh, dw, tab.at<unsigned char>(0));
+        if ((rc = tab.copy_to(&ctx->misc))) return rc;
+        const vkd::TapView<short> t(ctx->misc.ptr, 2, dh, dw);
+        VKX_TIMED(ctx, "k_resize_linear");
+        with_cn(cn, [&](auto CN) {
+            k_resize_taps_u8<CN, 2><<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, sh, sw, src_stride, dst, dh, dw, dst_stride, t.xofs, t.xcoef, t.yofs, t.ycoef);
+        });
+        break;
+    }
+    default: return refuse(plan, interpolation);
     }
     VKX_LAUNCH_CHECK();
     return VKX_OK;
@@ -1021,55 +600,37 @@ VKX_EXPORT int vkx_resize_f32_dev(vkx_ctx *ctx, const float *src, int sh, int sw
     VKX_REQUIRE_PITCH(src_stride_el, sw, sh);
     VKX_REQUIRE_PITCH(dst_stride_el, dw, dh);
     VKX_REQUIRE_DISJOINT(src, sh, src_stride_el * 4, (size_t)sw * 4, dst, dh, dst_stride_el * 4, (size_t)dw * 4);
-    if (interpolation == VKX_INTER_CUBIC) return vkx_resize_cubic_f32_dev(ctx, src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el);
     VKX_REQUIRE(ctx && src && dst, "NULL argument");
     VKX_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad shape");
-    dim3 grid(vkx_blocks(dw, 64), vkx_blocks(dh, 4));
-    switch (interpolation) {
-    case VKX_INTER_NEAREST: {
-        const double ifx = 1. / ((double)dw / sw), ify = 1. / ((double)dh / sh);
-        VKX_TIMED(ctx, "k_resize_nearest");
-        k_resize_nearest_u8<4><<<grid, 256, 0, ctx->stream>>>((const uint8_t *)src, sh, sw, src_stride_el * 4, (uint8_t *)dst, dh, dw,
-                                                              dst_stride_el * 4, ifx, ify);
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    case VKX_INTER_NEAREST_EXACT:
-        return resize_nearest_exact(ctx, src, sh, sw, 4, src_stride_el * 4, dst, dh, dw, dst_stride_el * 4);
-    case VKX_INTER_AREA:
-        return resize_area<true>(ctx, src, sh, sw, 1, src_stride_el, dst, dh, dw, dst_stride_el);
-    case VKX_INTER_LINEAR:
-    case VKX_INTER_LINEAR_EXACT: {     // no bit-exact float32 path in cv.resize: INTER_LINEAR_EXACT falls back to INTER_LINEAR
-        if (sw == 2 * dw && sh == 2 * dh) return resize_area<true>(ctx, src, sh, sw, 1, src_stride_el, dst, dh, dw, dst_stride_el);
+    const vkd::ResizePlan plan = vkd::plan_resize(true, interpolation, sh, sw, dh, dw);
+    switch (plan.mode) {
+    case vkd::M_TAPS:
+        return plan.ks == 4 ? resize_taps<4>(ctx, src, sh, sw, 1, src_stride_el, dst, dh, dw, dst_stride_el)
+                            : resize_taps<8>(ctx, src, sh, sw, 1, src_stride_el, dst, dh, dw, dst_stride_el);
+    case vkd::M_NEAREST:
+    case vkd::M_NEAREST_EXACT: return resize_nearest(ctx, plan, src, sh, sw, 4, src_stride_el * 4, dst, dh, dw, dst_stride_el * 4);
+    case vkd::M_AREA_FAST:
+    case vkd::M_AREA: return resize_area<true>(ctx, plan, src, sh, sw, 1, src_stride_el, dst, dh, dw, dst_stride_el);
+    case vkd::M_LINEAR_F32: {
         VKX_TIMED(ctx, "k_resize_linear");
-        k_resize_linear_f32<<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el,
-                                                           1. / ((double)dw / sw), 1. / ((double)dh / sh));
+        k_resize_linear_f32<<<direct_grid(dh, dw), 256, 0, ctx->stream>>>(src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el, plan.scale_x, plan.scale_y);
         VKX_LAUNCH_CHECK();
         return VKX_OK;
     }
-    case VKX_INTER_LANCZOS4: {
-        const int *xofs, *yofs;
-        const void *xc, *yc;
-        const std::vector<int> *yh;
-        int rc = resize_tables(ctx, 8, false, sh, sw, dh, dw, &xofs, &xc, &yofs, &yc, &yh);
-        if (rc) return rc;
-        VKX_TIMED(ctx, "k_resize_lanczos4");
-        if (separable_fits(*yh, sh, dh, 8)) {
-            dim3 sgrid(vkx_blocks(dw, kSepTileW), vkx_blocks(dh, kSepTileH));
-            k_resize_sep<float, float, float, 1, 8><<<sgrid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el,
-                                                                                     xofs, (const float *)xc, yofs, (const float *)yc);
-            VKX_LAUNCH_CHECK();
-            return VKX_OK;
-        }
-        k_resize_lanczos4_f32<<<grid, 256, 0, ctx->stream>>>(src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el, xofs,
-                                                             (const float *)xc, yofs, (const float *)yc);
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
+    default: return refuse(plan, interpolation);
     }
-    default:
-        vkx_set_error("unknown interpolation code %d", interpolation);
-        return VKX_ERR_UNSUPPORTED;
-    }
+}
+
+VKX_EXPORT int vkx_resize_cubic_u8_dev(vkx_ctx *ctx, const uint8_t *src, int sh, int sw, int cn, ptrdiff_t src_stride,
+                                       uint8_t *dst, int dh, int dw, ptrdiff_t dst_stride)
+{
+    return vkx_resize_u8_dev(ctx, src, sh, sw, cn, src_stride, dst, dh, dw, dst_stride, VKX_INTER_CUBIC);
+}
+
+VKX_EXPORT int vkx_resize_cubic_f32_dev(vkx_ctx *ctx, const float *src, int sh, int sw, ptrdiff_t src_stride_el,
+                                        float *dst, int dh, int dw, ptrdiff_t dst_stride_el)
+{
+    return vkx_resize_f32_dev(ctx, src, sh, sw, src_stride_el, dst, dh, dw, dst_stride_el, VKX_INTER_CUBIC);
 }
 
 VKX_EXPORT int vkx_zoom_in_blur_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,

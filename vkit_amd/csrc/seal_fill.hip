@@ -8,7 +8,7 @@
 // trip a char.  Here one call takes EVERY char of EVERY seal of a page, its records, tap tables and host glyph planes staged
 // as one block (vkx_tables, one copy out of the ring), in three launches and without a synchronisation:
 //   k_seal_planes   one workgroup column a char: the glyph resized into its char plane in context scratch (per pixel the
-//                   arithmetic of the kernels of resize.hip, on its axis tables); score maps clipped to [0, 1], masks as
+//                   functions of vkx_resize_pixel.h the kernels of resize.hip call, on the same table blocks); score maps clipped to [0, 1], masks as
 //                   (resize((m > 0) * 255) > 0).  Also clears the per-seal maxima.
 //   k_seal_gather   one lane a seal pixel: over the chars of its seal whose destination box covers it, the warp sample of
 //                   the char plane (vkx_warp_affine_f32_dev's pixel), kept when the running value is smaller (`mat < value`
@@ -17,13 +17,12 @@
 //   k_seal_scale    map * float32(alpha) / max, two float32 roundings; an all-zero map gives 0 / 0 = NaN as numpy does.
 // The planes are tens of kilobytes: the call is bound by launches and latency.
 #include "vkx_internal.h"
-#include "vkx_resize_axes.h"
+#include "vkx_resize_pixel.h"
 #include "vkx_warp.h"
 
 #include <algorithm>
-#include <cfloat>
-#include <cmath>
 #include <cstring>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -34,18 +33,13 @@ constexpr int kMaxSide = 32767;
 constexpr int kCharGroups = 64;                 // at most this many workgroups stride over the pixels of one char plane
 constexpr unsigned kNanKey = 0xffffffffu;
 
-enum Mode {
-    M_COPY, M_NEAREST_EXACT, M_LINEAR_F32, M_LINEAR_EXACT_U8, M_HALF_U8, M_TAPS, M_AREA_FAST, M_AREA
-};
-
 struct CharRec {
     const unsigned char *src;
     long long src_step;                         // bytes
     int src_kind;                               // VKX_SEAL_SRC_F32 / _U8C1 / _U8C3
     int sh, sw, gh;                             // the glyph is resized to gh x pw
-    int mode, ks, p[4];
-    double scale_x, scale_y;
-    long long tab_off;                          // the char's tap tables, bytes from the start of the staged block
+    vkd::ResizePlan plan;                       // (M_COPY: the source has the glyph's shape)
+    long long tab_off;                          // the char's table block, bytes from the start of the staged block
     long long plane_off;                        // its plane in the plane scratch, floats
     int ph, pw, glyph_up;
     int identity;                               // the rotation is a nop: the plane itself is filled
@@ -80,125 +74,59 @@ struct Src {
     }
 };
 
-using vkd::clip_index;
+// CUBIC / LANCZOS4 of a glyph: the tap pixel on the char's tap block
+template <int KS>
+__device__ __forceinline__ void glyph_taps(const Src &s, bool f32, const unsigned char *tab, int sh, int sw, int dh, int dw, int dy, int dx,
+                                           float *vf, uint8_t *vu)
+{
+    if (f32) {
+        const vkd::TapView<float> t(tab, KS, dh, dw);
+        *vf = vkd::taps_pixel_f32<KS>([&](int y, int x) { return s.f(y, x); }, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + KS * dx, t.ycoef + KS * dy);
+    } else {
+        const vkd::TapView<short> t(tab, KS, dh, dw);
+        vkd::taps_pixel_u8<1, KS>([&](int y, int x) { return s.u(y, x); }, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + KS * dx, t.ycoef + KS * dy, vu);
+    }
+}
 
-// One pixel of the resized glyph as the char plane holds it.  Every branch restates the kernel of resize.hip named beside it.
+// One pixel of the resized glyph as the char plane holds it: the pixel of vkx_resize_pixel.h the char's plan names, read through Src.
 __device__ float glyph_pixel(const CharRec &r, const unsigned char *tabs, int dy, int dx)
 {
     const Src s{r.src, r.src_step, r.src_kind};
     const bool f32 = r.src_kind == VKX_SEAL_SRC_F32;
     const int sh = r.sh, sw = r.sw, dh = r.gh, dw = r.pw;
+    const int *p = r.plan.p;
     const unsigned char *tab = tabs + r.tab_off;
     float vf = 0.f;
-    int vu = 0;
-    switch (r.mode) {
-    case M_COPY:
+    uint8_t vu = 0;
+    switch (r.plan.mode) {
+    case vkd::M_COPY:
         if (f32) return s.f(dy, dx);            // (a matching score map is filled as it is: no clip)
-        vu = s.u(dy, dx);
+        vu = (uint8_t)s.u(dy, dx);
         break;
-    case M_NEAREST_EXACT: {                     // k_resize_nearest_exact
-        const int sx = min((int)(((long long)r.p[0] * dx + r.p[1]) >> 16), sw - 1);
-        const int sy = min((int)(((long long)r.p[2] * dy + r.p[3]) >> 16), sh - 1);
-        if (f32) vf = s.f(sy, sx); else vu = s.u(sy, sx);
-        break;
-    }
-    case M_LINEAR_F32: {                        // k_resize_linear_f32
-        float fy = (float)((dy + 0.5) * r.scale_y - 0.5);
-        int y0 = (int)floorf(fy);
-        fy -= y0;
-        if (y0 < 0) { y0 = 0; fy = 0; }
-        if (y0 >= sh - 1) { y0 = sh - 1; fy = 0; }
-        float fx = (float)((dx + 0.5) * r.scale_x - 0.5);
-        int x0 = (int)floorf(fx);
-        fx -= x0;
-        if (x0 < 0) { x0 = 0; fx = 0; }
-        if (x0 >= sw - 1) { x0 = sw - 1; fx = 0; }
-        const int x1 = clip_index(x0 + 1, sw), y1 = clip_index(y0 + 1, sh);
-        const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
-        const float p0 = s.f(y0, x0) * a0, p1 = s.f(y0, x1) * a1, q0 = s.f(y1, x0) * a0, q1 = s.f(y1, x1) * a1;
-        const float h0 = p0 + p1, h1 = q0 + q1;
-        const float t0 = h0 * b0, t1 = h1 * b1;
-        vf = t0 + t1;
+    case vkd::M_NEAREST_EXACT: {
+        const int sx = vkd::nearest_exact_index(dx, p[0], p[1], sw), sy = vkd::nearest_exact_index(dy, p[2], p[3], sh);
+        if (f32) vf = s.f(sy, sx); else vu = (uint8_t)s.u(sy, sx);
         break;
     }
-    case M_LINEAR_EXACT_U8: {                   // k_resize_linear_exact_u8
-        const int *xofs = (const int *)tab, *xw = xofs + dw, *yofs = xw + dw, *yw = yofs + dh;
-        const int xmin = r.p[0], xmax = r.p[1], ymin = r.p[2], ymax = r.p[3];
-        const bool two = dy >= ymin && dy < ymax;
-        const int r0 = dy < ymin ? 0 : (dy >= ymax ? yofs[dh - 1] : yofs[dy]), r1 = two ? r0 + 1 : r0;
-        const int xa = dx < xmin ? 0 : (dx >= xmax ? xofs[dw - 1] : xofs[dx]);
-        const bool xin = dx >= xmin && dx < xmax;
-        const unsigned w1 = xin ? (unsigned)xw[dx] : 0u, w0 = 256u - w1;
-        const int xb = xin ? xa + 1 : xa;
-        const unsigned b1 = two ? (unsigned)yw[dy] : 0u, b0 = 256u - b1;
-        const unsigned h0 = w0 * s.u(r0, xa) + w1 * s.u(r0, xb);
-        unsigned v;
-        if (two) {
-            const unsigned h1 = w0 * s.u(r1, xa) + w1 * s.u(r1, xb);
-            v = (h0 * b0 + h1 * b1 + (1u << 15)) >> 16;
-        } else {
-            v = (h0 + 128u) >> 8;
-        }
-        vu = (int)(v > 255u ? 255u : v);
+    case vkd::M_LINEAR_F32:
+        vf = vkd::linear_pixel_f32([&](int y, int x) { return s.f(y, x); }, sh, sw, dy, dx, r.plan.scale_x, r.plan.scale_y);
         break;
-    }
-    case M_HALF_U8:                             // k_resize_half_u8
-        vu = (s.u(2 * dy, 2 * dx) + s.u(2 * dy, 2 * dx + 1) + s.u(2 * dy + 1, 2 * dx) + s.u(2 * dy + 1, 2 * dx + 1) + 2) >> 2;
+    case vkd::M_LINEAR_EXACT_U8:
+        vkd::linear_exact_pixel_u8<1>([&](int y, int below, int x, int) { return s.u(y + below, x); }, vkd::LinearExactView::of(tab, dh, dw), p, dh, dw, dy, dx, &vu);
         break;
-    case M_TAPS: {                              // k_resize_cubic_* (4 taps from s - 1), k_resize_lanczos4_* (8 from s - 3)
-        const int ks = r.ks, back = ks / 2 - 1;
-        const int *xofs = (const int *)tab, *yofs = xofs + dw;
-        const int x0 = xofs[dx] - back, y0 = yofs[dy] - back;
-        if (f32) {
-            const float *xc = (const float *)(yofs + dh) + (ptrdiff_t)ks * dx, *yc = (const float *)(yofs + dh) + (ptrdiff_t)ks * dw + (ptrdiff_t)ks * dy;
-            for (int k = 0; k < ks; k++) {
-                const int row = clip_index(y0 + k, sh);
-                float hsum = s.f(row, clip_index(x0, sw)) * xc[0];
-                for (int j = 1; j < ks; j++) { const float t = s.f(row, clip_index(x0 + j, sw)) * xc[j]; hsum = hsum + t; }
-                const float term = hsum * yc[k];
-                vf = k == 0 ? term : vf + term;
-            }
-        } else {
-            const short *xa = (const short *)(yofs + dh) + (ptrdiff_t)ks * dx, *yb = (const short *)(yofs + dh) + (ptrdiff_t)ks * dw + (ptrdiff_t)ks * dy;
-            unsigned acc = 0;
-            for (int k = 0; k < ks; k++) {
-                const int row = clip_index(y0 + k, sh);
-                unsigned hsum = 0;              // int32 with wrap, like the int accumulators of the reference implementation
-                for (int j = 0; j < ks; j++) hsum += (unsigned)(s.u(row, clip_index(x0 + j, sw)) * (int)xa[j]);
-                acc += hsum * (unsigned)(int)yb[k];       // the low 32 bits of the signed product
-            }
-            const int v = ((int)(acc + (1u << 21))) >> 22;
-            vu = v < 0 ? 0 : (v > 255 ? 255 : v);
-        }
+    case vkd::M_HALF_U8: vkd::half_pixel_u8<1>([&](int y, int x, int) { return s.u(2 * dy + y, 2 * dx + x); }, &vu); break;
+    case vkd::M_TAPS:
+        if (r.plan.ks == 4) glyph_taps<4>(s, f32, tab, sh, sw, dh, dw, dy, dx, &vf, &vu);
+        else glyph_taps<8>(s, f32, tab, sh, sw, dh, dw, dy, dx, &vf, &vu);
         break;
-    }
-    case M_AREA_FAST: {                         // k_resize_area_fast
-        const int isx = r.p[0], isy = r.p[1];
-        if (f32) vf = vkd::area_fast_f32([&](int y, int x) { return s.f(dy * isy + y, dx * isx + x); }, isx, isy);
-        else vu = vkd::area_fast_u8([&](int y, int x) { return s.u(dy * isy + y, dx * isx + x); }, isx, isy);
+    case vkd::M_AREA_FAST:
+        if (f32) vf = vkd::area_fast_f32([&](int y, int x) { return s.f(dy * p[1] + y, dx * p[0] + x); }, p[0], p[1]);
+        else vu = vkd::area_fast_u8([&](int y, int x) { return s.u(dy * p[1] + y, dx * p[0] + x); }, p[0], p[1]);
         break;
-    }
-    default: {                                  // M_AREA: k_resize_area
-        const int *xstart = (const int *)tab, *ystart = xstart + dw + 1;
-        const int nx = xstart[dw], ny = ystart[dh];
-        const int *xsi = ystart + dh + 1, *ysi = xsi + nx;
-        const float *xal = (const float *)(ysi + ny), *yal = xal + nx;
-        const int x0 = xstart[dx], x1 = xstart[dx + 1], y0 = ystart[dy], y1 = ystart[dy + 1];
-        float sum = 0.f;
-        for (int j = y0; j < y1; j++) {
-            float buf = 0.f;
-            for (int k = x0; k < x1; k++) {
-                const float v = f32 ? s.f(ysi[j], xsi[k]) : (float)s.u(ysi[j], xsi[k]);
-                const float t = v * xal[k];
-                buf = buf + t;
-            }
-            const float t = yal[j] * buf;
-            sum = j == y0 ? t : sum + t;
-        }
-        if (f32) vf = sum;
-        else { const int v = vkd::cv_round(sum); vu = v < 0 ? 0 : (v > 255 ? 255 : v); }
+    default:                                    // M_AREA
+        if (f32) vkd::area_pixel<1, true>([&](int y, int x, int) { return s.f(y, x); }, vkd::AreaView(tab, dh, dw), dy, dx, &vf);
+        else vkd::area_pixel<1, false>([&](int y, int x, int) { return (float)s.u(y, x); }, vkd::AreaView(tab, dh, dw), dy, dx, &vu);
         break;
-    }
     }
     if (!f32) return vu > 0 ? 1.f : 0.f;        // Mask.to_resized_mask's `> 0`, then mat.astype(np.float32)
     return vf < 0.f ? 0.f : (vf > 1.f ? 1.f : vf);   // np.clip(mat, 0, 1) of to_resized_score_map; a NaN stays
@@ -300,82 +228,19 @@ __global__ void __launch_bounds__(256) k_seal_scale(const SealRec *__restrict__ 
 bool is_u8(int kind) { return kind == VKX_SEAL_SRC_U8C1 || kind == VKX_SEAL_SRC_U8C3; }
 size_t elem_row_bytes(int kind, int w) { return kind == VKX_SEAL_SRC_F32 ? (size_t)w * 4 : (kind == VKX_SEAL_SRC_U8C3 ? (size_t)w * 3 : (size_t)w); }
 
-// How cv.resize runs (sh, sw) -> (dh, dw) with `interpolation` (one of the five a text line samples) on a float32 or uint8 plane:
-// the dispatch of vkx_resize_f32_dev and vkx_resize_u8_dev.  Fills mode, ks, p, scale_*; returns the bytes of the char's tables, or -1 for a refused request.
-long long plan_resize(bool f32, int interpolation, int sh, int sw, int dh, int dw, CharRec *r)
-{
-    r->ks = 0;
-    r->p[0] = r->p[1] = r->p[2] = r->p[3] = 0;
-    r->scale_x = 1. / ((double)dw / sw); r->scale_y = 1. / ((double)dh / sh);
-    const bool half = sw == 2 * dw && sh == 2 * dh;
-    const size_t csz = f32 ? sizeof(float) : sizeof(short);
-    switch (interpolation) {
-    case VKX_INTER_NEAREST_EXACT:
-        r->mode = M_NEAREST_EXACT;
-        r->p[0] = (int)((((long long)sw << 16) + dw / 2) / dw); r->p[1] = r->p[0] / 2 - sw % 2;
-        r->p[2] = (int)((((long long)sh << 16) + dh / 2) / dh); r->p[3] = r->p[2] / 2 - sh % 2;
-        return 0;
-    case VKX_INTER_CUBIC: r->mode = M_TAPS; r->ks = 4; return (long long)((sizeof(int) + 4 * csz) * ((size_t)dw + dh));
-    case VKX_INTER_LANCZOS4: r->mode = M_TAPS; r->ks = 8; return (long long)((sizeof(int) + 8 * csz) * ((size_t)dw + dh));
-    case VKX_INTER_LINEAR_EXACT:
-        if (!half) {
-            if (f32) { r->mode = M_LINEAR_F32; return 0; }
-            r->mode = M_LINEAR_EXACT_U8;
-            return (long long)(2 * sizeof(int) * ((size_t)dw + dh));
-        }
-        if (!f32) { r->mode = M_HALF_U8; return 0; }
-        /* fallthrough: cv.resize routes the exact 2 x 2 shrink of a float32 plane to INTER_AREA */
-    case VKX_INTER_AREA: {
-        if (dw > sw || dh > sh) return -1;
-        const int isx = (int)std::nearbyint(r->scale_x), isy = (int)std::nearbyint(r->scale_y);
-        if (std::fabs(r->scale_x - isx) < DBL_EPSILON && std::fabs(r->scale_y - isy) < DBL_EPSILON) {
-            r->mode = M_AREA_FAST; r->p[0] = isx; r->p[1] = isy;
-            return 0;
-        }
-        r->mode = M_AREA;
-        return -2;                              // sized by the tables themselves
-    }
-    default: return -1;
-    }
-}
-
 bool known_interpolation(int c)
 {
     return c == VKX_INTER_CUBIC || c == VKX_INTER_AREA || c == VKX_INTER_LANCZOS4 || c == VKX_INTER_LINEAR_EXACT || c == VKX_INTER_NEAREST_EXACT;
 }
 
-// the tables of one char, written where the kernel reads them
-void write_tables(const CharRec &r, bool f32, unsigned char *out, const vkd::AreaTab *ax, const vkd::AreaTab *ay)
+// the bytes of a char's table block (none: 0); given an address, the block is written there (and a LINEAR_EXACT plan gets its ranges)
+size_t pack_tables(CharRec &r, bool f32, const vkd::AreaTabs *area, unsigned char *out)
 {
-    const int sh = r.sh, sw = r.sw, dh = r.gh, dw = r.pw;
-    if (r.mode == M_TAPS) {
-        int *xofs = (int *)out, *yofs = xofs + dw;
-        unsigned char *coef = (unsigned char *)(yofs + dh);
-        const size_t csz = f32 ? sizeof(float) : sizeof(short);
-        const void *xsrc, *ysrc;
-        vkd::AxisTable t4x, t4y;
-        vkd::AxisTable8 t8x, t8y;
-        if (r.ks == 4) {
-            vkd::build_axis(sw, dw, &t4x); vkd::build_axis(sh, dh, &t4y);
-            memcpy(xofs, t4x.ofs.data(), sizeof(int) * dw); memcpy(yofs, t4y.ofs.data(), sizeof(int) * dh);
-            xsrc = f32 ? (const void *)t4x.coef.data() : (const void *)t4x.icoef.data();
-            ysrc = f32 ? (const void *)t4y.coef.data() : (const void *)t4y.icoef.data();
-        } else {
-            vkd::build_axis8(sw, dw, &t8x); vkd::build_axis8(sh, dh, &t8y);
-            memcpy(xofs, t8x.ofs.data(), sizeof(int) * dw); memcpy(yofs, t8y.ofs.data(), sizeof(int) * dh);
-            xsrc = f32 ? (const void *)t8x.coef.data() : (const void *)t8x.icoef.data();
-            ysrc = f32 ? (const void *)t8y.coef.data() : (const void *)t8y.icoef.data();
-        }
-        memcpy(coef, xsrc, csz * r.ks * dw);
-        memcpy(coef + csz * r.ks * dw, ysrc, csz * r.ks * dh);
-    } else if (r.mode == M_AREA) {
-        int *xstart = (int *)out, *ystart = xstart + dw + 1;
-        const size_t nx = ax->si.size(), ny = ay->si.size();
-        int *xsi = ystart + dh + 1, *ysi = xsi + nx;
-        float *xal = (float *)(ysi + ny), *yal = xal + nx;
-        memcpy(xstart, ax->start.data(), sizeof(int) * (dw + 1)); memcpy(ystart, ay->start.data(), sizeof(int) * (dh + 1));
-        memcpy(xsi, ax->si.data(), sizeof(int) * nx); memcpy(ysi, ay->si.data(), sizeof(int) * ny);
-        memcpy(xal, ax->alpha.data(), sizeof(float) * nx); memcpy(yal, ay->alpha.data(), sizeof(float) * ny);
+    switch (r.plan.mode) {
+    case vkd::M_TAPS: return vkd::pack_taps(r.plan.ks, f32, r.sh, r.sw, r.gh, r.pw, out);
+    case vkd::M_LINEAR_EXACT_U8: return vkd::pack_linear_exact(r.sh, r.sw, r.gh, r.pw, out, r.plan.p);
+    case vkd::M_AREA: return area->pack(out);
+    default: return 0;
     }
 }
 
@@ -441,7 +306,7 @@ VKX_EXPORT int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, 
 
     // chars: checked, planned, and laid out behind the records in one staged block
     std::vector<CharRec> chars(n_chars);
-    std::vector<vkd::AreaTab> area_x(n_chars), area_y(n_chars);
+    std::vector<std::unique_ptr<vkd::AreaTabs>> area(n_chars);   // of the chars whose plan is M_AREA
     vkx_tables tab(ctx);
     const size_t chars_off = tab.add(sizeof(CharRec) * (size_t)std::max(n_chars, 1));
     const size_t seals_off = tab.add(sizeof(SealRec) * (size_t)n_seals);
@@ -466,22 +331,13 @@ VKX_EXPORT int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, 
         r.sh = p.src_h; r.sw = p.src_w; r.gh = p.glyph_h;
         r.ph = p.plane_h; r.pw = p.plane_w; r.glyph_up = p.glyph_up;
         r.tab_off = 0;
-        long long bytes = 0;
-        if (p.src_h == p.glyph_h && p.src_w == p.plane_w) {
-            r.mode = M_COPY; r.ks = 0; r.p[0] = r.p[1] = r.p[2] = r.p[3] = 0; r.scale_x = r.scale_y = 1.0;
-        } else {
-            bytes = plan_resize(f32, p.interpolation, p.src_h, p.src_w, p.glyph_h, p.plane_w, &r);
-            VKX_REQUIRE(bytes != -1, "INTER_AREA is for shrinking only");
-            if (r.mode == M_AREA) {
-                vkd::build_area_tab(p.src_w, p.plane_w, r.scale_x, &area_x[i]);
-                vkd::build_area_tab(p.src_h, p.glyph_h, r.scale_y, &area_y[i]);
-                bytes = (long long)(sizeof(int) * ((size_t)p.plane_w + p.glyph_h + 2) +
-                                    (sizeof(int) + sizeof(float)) * (area_x[i].si.size() + area_y[i].si.size()));
-            } else if (r.mode == M_LINEAR_EXACT_U8) {
-                bytes = (long long)(2 * sizeof(int) * ((size_t)p.plane_w + p.glyph_h));
-            }
+        r.plan = vkd::ResizePlan();
+        if (p.src_h != p.glyph_h || p.src_w != p.plane_w) {
+            r.plan = vkd::plan_resize(f32, p.interpolation, p.src_h, p.src_w, p.glyph_h, p.plane_w);
+            VKX_REQUIRE(!r.plan.refused(), "INTER_AREA is for shrinking only");
+            if (r.plan.mode == vkd::M_AREA) area[i].reset(new vkd::AreaTabs(p.src_h, p.src_w, p.glyph_h, p.plane_w, r.plan.scale_x, r.plan.scale_y));
+            if (const size_t bytes = pack_tables(r, f32, area[i].get(), nullptr)) r.tab_off = (long long)tab.add(bytes);
         }
-        if (bytes > 0) r.tab_off = (long long)tab.add((size_t)bytes);
         r.identity = p.identity ? 1 : 0;
         double forward[6];
         for (int k = 0; k < 6; k++) forward[k] = (double)p.m[k];
@@ -500,17 +356,7 @@ VKX_EXPORT int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, 
     if ((rc = tab.take())) return rc;
     for (int i = 0; i < n_chars; i++) {
         CharRec &r = chars[i];
-        const bool f32 = (r.src_kind & ~VKX_SEAL_SRC_HOST) == VKX_SEAL_SRC_F32;
-        if (r.mode == M_LINEAR_EXACT_U8) {
-            std::vector<int> xo, xw, yo, yw;
-            vkd::build_linear_exact_axis(r.sw, r.pw, &xo, &xw, &r.p[0], &r.p[1]);
-            vkd::build_linear_exact_axis(r.sh, r.gh, &yo, &yw, &r.p[2], &r.p[3]);
-            int *out = tab.at<int>((size_t)r.tab_off);
-            memcpy(out, xo.data(), sizeof(int) * r.pw); memcpy(out + r.pw, xw.data(), sizeof(int) * r.pw);
-            memcpy(out + 2 * r.pw, yo.data(), sizeof(int) * r.gh); memcpy(out + 2 * r.pw + r.gh, yw.data(), sizeof(int) * r.gh);
-        } else if (r.tab_off) {
-            write_tables(r, f32, tab.at<unsigned char>((size_t)r.tab_off), &area_x[i], &area_y[i]);
-        }
+        if (r.tab_off) pack_tables(r, (r.src_kind & ~VKX_SEAL_SRC_HOST) == VKX_SEAL_SRC_F32, area[i].get(), tab.at<unsigned char>((size_t)r.tab_off));
     }
     if (planes_host_bytes) memcpy(tab.at<unsigned char>(host_off), planes_host, planes_host_bytes);
     // the staged block lands in seal_tables: host sources are addressed there

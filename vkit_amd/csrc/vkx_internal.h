@@ -144,13 +144,12 @@ struct vkx_ctx {
     // block or regrow the ring under it fails (VKX_ERR_NOMEM) and sets desc_hold to 2; the caller falls back to its copy path.
     int desc_hold = 0;
 
-    // The tap tables of the last few CUBIC / LANCZOS4 resize geometries (PageResizingStep resizes seven elements with one
+    // The table blocks of the last few resize geometries (resize.hip; PageResizingStep resizes seven elements with one
     // geometry: the tables are built and uploaded for the first one only).
     struct ResizeTabs {
-        int key[6] = {-1, -1, -1, -1, -1, -1};    // taps, fixed point?, sh, sw, dh, dw
-        vkx_scratch buf;
-        size_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // the tables inside buf (xofs, xcoef, yofs, ycoef for the tap kernels)
-        std::vector<int> yofs;                    // host side: row offsets (tile planning) or other small metadata
+        int key[6] = {-1, -1, -1, -1, -1, -1};    // taps (or 103 AREA, 105 LINEAR_EXACT), fixed point?, sh, sw, dh, dw
+        vkx_scratch buf;                          // the block as its packer of vkx_resize_axes.h wrote it
+        std::vector<int> meta;                    // host side: what the launch needs besides the block (row offsets, entry counts, ranges)
         unsigned long stamp = 0;
     };
     ResizeTabs resize_tabs[6];
@@ -372,43 +371,6 @@ __device__ __forceinline__ float sample_f32(PTR src, int sh, int sw, ptrdiff_t s
     const float v3 = (x1 && y1) ? r1[1] : 0.f;
     const float p0 = v0 * w0, p1 = v1 * w1, p2 = v2 * w2, p3 = v3 * w3;
     return ((p0 + p1) + p2) + p3;
-}
-
-// INTER_AREA at integer factors (cv::ResizeAreaFast): one destination sample from its isx x isy source box, the box read
-// through at(y, x) (box coordinates).  uint8: (sum + 2) >> 2 at 2 x 2, else cvRound(sum * (1.f / area)); float32:
-// (a + b) + (c + d) then * 0.25f at 2 x 2, else the row-major box summed four samples at a time.  Every box sample is
-// read exactly once.  Shared by k_resize_area_fast (resize.hip) and the label shrink of the crop kernel (crop.hip).
-template <class At>
-__device__ __forceinline__ uint8_t area_fast_u8(At at, int isx, int isy)
-{
-    int sum = 0;
-    for (int y = 0; y < isy; y++)
-        for (int x = 0; x < isx; x++) sum += at(y, x);
-    const int r = (isx == 2 && isy == 2) ? (sum + 2) >> 2 : cv_round((float)sum * (1.f / (isx * isy)));
-    return (uint8_t)clamp_u8(r);
-}
-template <class At>
-__device__ __forceinline__ float area_fast_f32(At at, int isx, int isy)
-{
-    if (isx == 2 && isy == 2) {          // the vector body of the 2 x 2 case pairs the rows
-        const float top = at(0, 0) + at(0, 1);
-        const float bottom = at(1, 0) + at(1, 1);
-        const float s4 = top + bottom;
-        return s4 * 0.25f;
-    }
-    const int area = isx * isy;
-    float sum = 0;
-    int k = 0;
-    for (; k <= area - 4; k += 4) {      // the reference sums the row-major box four samples at a time
-        const float a0 = at(k / isx, k % isx), a1 = at((k + 1) / isx, (k + 1) % isx);
-        const float a2 = at((k + 2) / isx, (k + 2) % isx), a3 = at((k + 3) / isx, (k + 3) % isx);
-        float g = a0 + a1;
-        g = g + a2;
-        g = g + a3;
-        sum = sum + g;
-    }
-    for (; k < area; k++) sum = sum + at(k / isx, k % isx);
-    return sum * (1.f / area);
 }
 
 // cv.warpPerspective's source coordinate of destination pixel (x, y) in 1/32 px (imgwarp.cpp WarpPerspectiveInvoker): the
