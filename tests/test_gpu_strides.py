@@ -369,6 +369,22 @@ def build_cases():
     add('resize_cubic_f32', 'vkx_resize_cubic_f32', {'src': (srcf, srcf.shape, f32, 'in'), 'dst': (None, (70, 101), f32, 'out')},
         lambda fn, P: fn(H, P['src'].p, 45, 67, P['src'].stride, P['dst'].p, 70, 101, P['dst'].stride),
         {'dst': later(O.resize_cubic, srcf, (70, 101))})
+    # the row switches of the two tap forms (tests/resize_routes.py CENTRES): at 40 destination rows an interior tile needs
+    # exactly 24, 25 (the two uint8 instances of the separable kernel), 40 and 41 (the last separable shape, the first direct one)
+    # source rows; a generator of their own, so that the rows below keep their data
+    brng = np.random.default_rng(20261019)
+    for interp, heights in ((2, (52, 54, 96, 98)), (4, (42, 44, 85, 86))):
+        for sh in heights:
+            src = _img(brng, sh, 70, 3)
+            add(f'resize_u8 i{interp} cn3 {sh}x70->40x67 (row switch)', 'vkx_resize_u8',
+                {'src': (src, src.shape, u8, 'in'), 'dst': (None, (40, 67, 3), u8, 'out')},
+                lambda fn, P, sh=sh, i=interp: fn(H, P['src'].p, sh, 70, 3, P['src'].stride, P['dst'].p, 40, 67, P['dst'].stride, i),
+                {'dst': later(O.resize, src, (40, 67), interp)})
+            srcf = brng.random((sh, 70), dtype=np.float32) * 4 - 1
+            add(f'resize_f32 i{interp} {sh}x70->40x67 (row switch)', 'vkx_resize_f32',
+                {'src': (srcf, srcf.shape, f32, 'in'), 'dst': (None, (40, 67), f32, 'out')},
+                lambda fn, P, sh=sh, i=interp: fn(H, P['src'].p, sh, 70, P['src'].stride, P['dst'].p, 40, 67, P['dst'].stride, i),
+                {'dst': later(O.resize, srcf, (40, 67), interp)})
     # page scale: the 24-row and 40-row separable forms and the direct kernels (cubic, lanczos4), the exact half, the integer
     # area kernel and the general area tables, the linear-exact tables, nearest and nearest-exact; dw % 4 = 1, 2, 3
     page = _img(rng, 1024, 1024, 3)
