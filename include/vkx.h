@@ -1121,6 +1121,60 @@ typedef struct vkx_seal_rec {
 int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, int n_chars, const vkx_seal_rec *seals_host, int n_seals,
                       const void *planes_host, size_t planes_host_bytes, float *dst, size_t dst_floats);
 
+/* ---- render_text_line_meta, the pixel half (engine/font/freetype.py:314-380, :600-837) ----------------------------------------
+ * vkx_text_lines_dev renders EVERY text line of a page from its glyph bitmaps: two launches whatever the number of lines and
+ * chars, no synchronisation.  The records are HOST tables; every geometric decision in them (char boxes, resized shape, pad,
+ * trim index, which chars the clean-up names) is the caller's and depends on no pixel, every pixel is the call's:
+ *   the paste (:314-380): a plane of paste_h x paste_w, image 255, mask 0, score map 0.0; per char in table order, where its glyph
+ *   (uint8 [glyph_h][glyph_w][channels]) is > 0 (any channel of a 3-channel LCD glyph) the image takes the line's colour
+ *   (1 channel: cvtColor(RGBA2RGB) drops the alpha) or, LCD, ((1 - glyph / 255.0) * 255) truncated, in float64 as numpy has it
+ *   (not 255 - glyph), or the glyph's own paste plane where the caller formed one (a gamma other than 1), and the mask 1; over the whole char box the score map keeps the maximum of the glyphs' score maps;
+ *   the resize (:618-642; resized != paste shape): cv.resize(interpolation) of the image, of (mask * 255) then > 0
+ *   (Mask.to_resized_mask) and of the score map then clipped to [0, 1] (ScoreMap.to_resized_score_map);
+ *   the pad and the trim: the (resized) plane sits at (pad_up, pad_left) of a plane of 255 / 0 / 0.0, whose top left
+ *   out_h x out_w pixels are the output;
+ *   the clean-up of a trimmed char (:693-731, cleanup != 0; boxes {up, left, height, width} in the padded plane): inside
+ *   trimmed_box, where the mask of glyph trimmed_char (resized to the box as a mask when the shapes differ) is set the image is
+ *   255 and the mask 0, and the score map is 0; then inside kept_box the score map keeps the maximum with the score map of
+ *   glyph kept_char (resized to the box and clipped when the shapes differ).
+ * Interpolations: the five codes a text line samples (VKX_INTER_NEAREST_EXACT, _LINEAR_EXACT, _CUBIC, _LANCZOS4, _AREA); AREA
+ * shrinks only.  `blob_host` is ONE host block holding the glyph bitmaps, score maps (float32, offsets multiples of 4) and paste
+ * planes, dense, at the byte offsets of the char records (-1: none); it travels with the tables as one staged upload.  The chars
+ * of a line are consecutive in the table (ascending `line`; trimmed_char / kept_char count from the line's first).  dst: DEVICE,
+ * `dst_bytes` long, aligned to 4 bytes; per line the dense planes image uint8 [out_h][out_w][3] at image_off, mask uint8
+ * [out_h][out_w] at mask_off and, has_score != 0 (exactly the 1-channel lines), score map float32 [out_h][out_w] at score_off
+ * (a multiple of 4), all in bytes; every element of them is written, dst needs no memset.
+ * Refused (VKX_ERR_INVALID, nothing launched): a NULL pointer, n_chars outside 1 .. 65536, n_lines outside 1 .. 4096, a line
+ * without chars, a side outside 1 .. 32767, a negative pad, a colour outside 0 .. 255, a char box outside its line's pasted plane,
+ * a kept box outside the output, a clean-up char outside its line, an unknown interpolation code, a VKX_INTER_AREA enlargement
+ * (of a line or of a clean-up glyph), a blob offset out of range or misaligned, a destination outside dst or misaligned,
+ * destinations that overlap one another. */
+typedef struct vkx_text_char {
+    int64_t image_off;                  /* blob: uint8 [glyph_h][glyph_w][channels of its line] */
+    int64_t score_off;                  /* blob: float32 [glyph_h][glyph_w]; -1 for the glyphs of an LCD line */
+    int64_t paste_off;                  /* blob: uint8 [glyph_h][glyph_w][3], what an LCD glyph pastes; -1: the gamma-1 value */
+    int32_t glyph_h, glyph_w;
+    int32_t line;
+    int32_t up, left;                   /* the char box in the pasted plane: it has the glyph's shape */
+    int32_t reserved;
+} vkx_text_char;
+typedef struct vkx_text_line {
+    int32_t channels;                   /* of its glyphs: 1 (default, monochrome) or 3 (LCD) */
+    int32_t color[3];                   /* the glyph colour of a 1-channel line */
+    int32_t paste_h, paste_w;
+    int32_t resized_h, resized_w;       /* equal to the pasted plane: not resized */
+    int32_t interpolation;              /* VKX_INTER_* */
+    int32_t pad_up, pad_left;
+    int32_t out_h, out_w;
+    int32_t has_score;
+    int32_t cleanup, trimmed_char, kept_char;
+    int32_t trimmed_box[4], kept_box[4];
+    int32_t reserved;
+    int64_t image_off, mask_off, score_off;   /* bytes */
+} vkx_text_line;
+int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host, int n_chars, const vkx_text_line *lines_host, int n_lines,
+                       const void *blob_host, size_t blob_bytes, uint8_t *dst, size_t dst_bytes);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

@@ -398,6 +398,7 @@ _SIGNATURES['vkx_region_extend_masks_dev'] = [c_void_p, c_void_p, c_int, c_void_
                                               ctypes.c_size_t]
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 _SIGNATURES['vkx_seal_fill_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
+_SIGNATURES['vkx_text_lines_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
 _lib = None
@@ -2646,4 +2647,33 @@ def seal_fill(chars, seals, dst, planes_host=None):
     check(lib().vkx_seal_fill_dev(dst.ctx.handle, chars.ctypes.data if len(chars) else None, len(chars), seals.ctypes.data, len(seals),
                                   planes_host.ctypes.data if planes_host.size else None, planes_host.size, c_void_p(dst.ptr),
                                   dst.size))
+    dst.invalidate_host()
+
+
+# --------------------------------------------------------------------------------------------------------------
+# the pixel half of render_text_line_meta for every text line of a page (csrc/text_line.hip): vkx_text_char / vkx_text_line of include/vkx.h
+# --------------------------------------------------------------------------------------------------------------
+TEXT_CHAR_DTYPE = np.dtype([('image_off', np.int64), ('score_off', np.int64), ('paste_off', np.int64), ('glyph_h', np.int32),
+                            ('glyph_w', np.int32), ('line', np.int32), ('up', np.int32), ('left', np.int32), ('reserved', np.int32)],
+                           align=True)
+TEXT_LINE_DTYPE = np.dtype([('channels', np.int32), ('color', np.int32, (3,)), ('paste_h', np.int32), ('paste_w', np.int32),
+                            ('resized_h', np.int32), ('resized_w', np.int32), ('interpolation', np.int32), ('pad_up', np.int32),
+                            ('pad_left', np.int32), ('out_h', np.int32), ('out_w', np.int32), ('has_score', np.int32),
+                            ('cleanup', np.int32), ('trimmed_char', np.int32), ('kept_char', np.int32),
+                            ('trimmed_box', np.int32, (4,)), ('kept_box', np.int32, (4,)), ('reserved', np.int32),
+                            ('image_off', np.int64), ('mask_off', np.int64), ('score_off', np.int64)], align=True)
+assert (TEXT_CHAR_DTYPE.itemsize, TEXT_LINE_DTYPE.itemsize) == (48, 128)
+
+
+def text_lines(chars, lines, blob, dst):
+    """vkx_text_lines_dev: ``chars`` TEXT_CHAR_DTYPE and ``lines`` TEXT_LINE_DTYPE records, ``blob`` the uint8 host block of glyph
+    bitmaps, score maps and paste planes the char records address by byte offset, ``dst`` the uint8 DevArray the lines' planes
+    are written into at the byte offsets of the line records.  TWO launches whatever the number of lines and chars, asynchronous."""
+    chars, lines = _records(chars, TEXT_CHAR_DTYPE), _records(lines, TEXT_LINE_DTYPE)
+    if dst.dtype != np.uint8:
+        raise TypeError('dst must be a uint8 DevArray')
+    blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    check(lib().vkx_text_lines_dev(dst.ctx.handle, chars.ctypes.data if len(chars) else None, len(chars),
+                                   lines.ctypes.data if len(lines) else None, len(lines), blob.ctypes.data if blob.size else None,
+                                   blob.size, c_void_p(dst.ptr), dst.nbytes))
     dst.invalidate_host()

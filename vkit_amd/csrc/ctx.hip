@@ -119,6 +119,8 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->rm_bits);
     scratch_release(&ctx->seal_tables);
     scratch_release(&ctx->seal_planes);
+    scratch_release(&ctx->text_tables);
+    scratch_release(&ctx->text_planes);
     scratch_release(&ctx->glass_win);
     scratch_release(&ctx->jpeg_planes);
     scratch_release(&ctx->pz_tabs);

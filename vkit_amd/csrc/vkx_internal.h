@@ -128,6 +128,7 @@ struct vkx_ctx {
     vkx_scratch rf_tables;                    // text-region flattening (region_flatten.hip): the staged records and tap tables of the last call
     vkx_scratch rm_tables, rm_bits;           // text-region masks (region_masks.hip): the overflow flag + staged tables; the o / d / r bit planes of the last call
     vkx_scratch seal_tables, seal_planes;     // seal impressions (seal_fill.hip): the staged records, tap tables and host planes of the last call; the char planes + per-seal maxima
+    vkx_scratch text_tables, text_planes;     // text lines (text_line.hip): the staged records, resize tables and glyph blob of the last call; the pasted planes of its resized lines
     vkx_scratch glass_win;                    // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows
     bool pz_tabs_ready = false;

@@ -1,8 +1,11 @@
-"""``CharBox``, ``CharGlyph`` and ``TextLine`` of the reference's font engine (vkit/engine/font/type.py:319-699), reduced to what
-the seal-impression engine and the page assembler read.  They are containers: the arrays come from a font engine that ran
-elsewhere.  ``TextLine`` has the fields of the page assembler's reduced text line (``image``, ``mask``, ``score_map``,
-``glyph_color``, ``box``) and is accepted wherever that one is."""
-from typing import List, Optional, Sequence, Tuple
+"""The containers of the reference's font engine (vkit/engine/font/type.py:55-699): the run config and its style, the glyph
+statistics ``build_char_glyph`` reads, ``CharBox``, ``CharGlyph`` and ``TextLine``.  Glyph rasterisation (freetype) stays outside
+the package; the text-line half of the engine, which turns glyph bitmaps into a ``TextLine``, is ``text_line.py``.  ``TextLine``
+has the fields of the page assembler's reduced text line (``image``, ``mask``, ``score_map``, ``glyph_color``, ``box``) and is
+accepted wherever that one is.  The fields the seal-impression engine and the page assembler do not read are keyword fields with
+defaults: a line or a glyph that came from elsewhere is built from the arrays alone."""
+from enum import Enum, unique
+from typing import Any, List, Mapping, Optional, Sequence, Tuple
 
 import attrs
 import numpy as np
@@ -10,6 +13,92 @@ import numpy as np
 from vkit_amd.element import Box, Image, Mask, Polygon, ScoreMap, Shapable
 
 _CV_INTER_CUBIC = 2
+
+
+@attrs.define(frozen=True)
+class FontGlyphInfo:
+    tags: Sequence[str]
+    ascent_plus_pad_up_min_to_font_size_ratio: float
+    height_min_to_font_size_ratio: float
+    width_min_to_font_size_ratio: float
+
+
+@attrs.define
+class FontGlyphInfoCollection:
+    font_glyph_infos: Sequence[FontGlyphInfo]
+    _tag_to_font_glyph_info: Optional[Mapping[str, FontGlyphInfo]] = attrs.field(default=None, init=False, repr=False, eq=False)
+
+    @property
+    def tag_to_font_glyph_info(self):
+        if not self._tag_to_font_glyph_info:
+            tag_to_font_glyph_info = {}
+            for font_glyph_info in self.font_glyph_infos:
+                assert font_glyph_info.tags
+                for tag in font_glyph_info.tags:
+                    assert tag not in tag_to_font_glyph_info
+                    tag_to_font_glyph_info[tag] = font_glyph_info
+            self._tag_to_font_glyph_info = tag_to_font_glyph_info
+        return self._tag_to_font_glyph_info
+
+
+@attrs.define
+class FontVariant:
+    char_to_tags: Mapping[str, Sequence[str]]
+    font_file: Any
+    font_glyph_info_collection: FontGlyphInfoCollection
+    is_ttc: bool = False
+    ttc_font_index: Optional[int] = None
+
+
+@attrs.define
+class FontEngineRunConfigStyle:
+    # Font size.
+    font_size_ratio: float = 1.0
+    font_size_min: int = 12
+    font_size_max: int = 96
+
+    # Space between chars.
+    prob_set_char_space_min: float = 0.5
+    char_space_min: float = 0.0
+    char_space_max: float = 0.2
+    char_space_mean: float = 0.1
+    char_space_std: float = 0.03
+
+    # Space between words.
+    word_space_min: float = 0.3
+    word_space_max: float = 1.0
+    word_space_mean: float = 0.6
+    word_space_std: float = 0.1
+
+    # Effect.
+    glyph_color: Tuple[int, int, int] = (0, 0, 0)
+    # https://en.wikipedia.org/wiki/Gamma_correction
+    glyph_color_gamma: float = 1.0
+
+    # Implementation related options.
+    freetype_force_autohint: bool = False
+
+
+@unique
+class FontEngineRunConfigGlyphSequence(Enum):
+    HORI_DEFAULT = 'hori_default'
+    VERT_DEFAULT = 'vert_default'
+
+
+@attrs.define
+class FontEngineRunConfig:
+    height: int
+    width: int
+    chars: Sequence[str]
+    font_variant: FontVariant
+
+    # Sequence mode.
+    glyph_sequence: FontEngineRunConfigGlyphSequence = FontEngineRunConfigGlyphSequence.HORI_DEFAULT
+
+    style: FontEngineRunConfigStyle = attrs.field(factory=FontEngineRunConfigStyle)
+
+    # For debugging.
+    return_font_variant: bool = False
 
 
 @attrs.define(frozen=True)
@@ -44,6 +133,11 @@ class CharBox(Shapable):
     def width(self):
         return self.box.width
 
+    def to_conducted_resized_char_box(self, shapable_or_shape, resized_height: Optional[int] = None,
+                                      resized_width: Optional[int] = None):
+        return attrs.evolve(self, box=self.box.to_conducted_resized_box(shapable_or_shape=shapable_or_shape,
+                                                                        resized_height=resized_height, resized_width=resized_width))
+
     def to_shifted_char_box(self, offset_y: int = 0, offset_x: int = 0):
         return attrs.evolve(self, box=self.box.to_shifted_box(offset_y=offset_y, offset_x=offset_x))
 
@@ -55,6 +149,21 @@ class CharGlyph:
     # the size of the font's reference char: what a char polygon is widened to
     ref_char_height: int
     ref_char_width: int
+    # what build_char_glyph loads from the font face (reference :394-404)
+    char: str = attrs.field(default='', kw_only=True)
+    ascent: int = attrs.field(default=0, kw_only=True)
+    pad_up: int = attrs.field(default=0, kw_only=True)
+    pad_down: int = attrs.field(default=0, kw_only=True)
+    pad_left: int = attrs.field(default=0, kw_only=True)
+    pad_right: int = attrs.field(default=0, kw_only=True)
+    ref_ascent_plus_pad_up: int = attrs.field(default=0, kw_only=True)
+
+    def __attrs_post_init__(self):
+        # NOTE: ascent could be negative for char like '_'.
+        assert self.pad_up >= 0
+        assert self.pad_down >= 0
+        assert self.pad_left >= 0
+        assert self.pad_right >= 0
 
     @property
     def height(self):
@@ -96,6 +205,12 @@ class TextLine:
     glyph_color: Tuple[int, int, int] = (0, 0, 0)
     # a shifted text line is bound to a page
     shifted: bool = False
+    # what render_text_line_meta knows besides the arrays (reference :463-472); glyph_color is filled from style.glyph_color
+    style: Optional[FontEngineRunConfigStyle] = attrs.field(default=None, kw_only=True)
+    font_size: int = attrs.field(default=0, kw_only=True)
+    text: str = attrs.field(default='', kw_only=True)
+    # For debugging.
+    font_variant: Optional[FontVariant] = attrs.field(default=None, kw_only=True)
 
     @property
     def box(self):
