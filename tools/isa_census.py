@@ -8,7 +8,8 @@ per wavefront, unrolled or not as the compiler chose) and E (8 output rows, unro
 the output.  Dynamic totals come from the PMC runs (profiles/*pmc*).
 The single-variant build has no register pressure to speak of, so the last line is from the PRODUCTION build (the Makefile's flags):
 SGPRs, VGPRs, SGPR spills and scratch bytes of every pixel kernel of the chain, both instances, from the code-object metadata.
-Usage: tools/isa_census.py [--asm out.s] > profiles/r2_isa_census.md"""
+Usage: tools/isa_census.py [--asm out.s] [--all-ops] > profiles/r2_isa_census.md     (--all-ops: every opcode of a phase, not the
+fourteen most frequent)"""
 import collections
 import os
 import re
@@ -27,7 +28,7 @@ def phase_table():
     marks = [('// ---- A: clear the ownership plane', 'A prologue + raster'), ('// ---- C + D:', 'C map'),
              ('unsigned long long ta[CGROUP]', 'C gather'), ('static_assert(CGROUP == 2, "phase D', 'D h-blur'),
              ('// ---- E:', 'E setup + noise load'), ('uint32_t P = epx;', 'E v-blur'),
-             ('if (hue_on) P = vkd::hue_shift_packed(lsdiv, lhdiv, lsel, hue_delta, r, g, b);', 'E hue'),
+             ('lsdiv, lhdiv, lsel, hue_delta, r, g, b);', 'E hue'),
              ("// channel by channel on the lane's own pixel", 'E noise add (per pixel)'),
              ('// 4 adjacent pixels = 12 bytes', 'E pack + store')]
     table = []
@@ -154,7 +155,7 @@ def main():
           'per (cell, edge), loop over the steps); C / D -- per wavefront 8 window rows, 2 per iteration; E -- 8 output rows, '
           'unrolled.\n')
     for n in seen:
-        top = ', '.join(f'{op} x{c}' for op, c in ops[n].most_common(14))
+        top = ', '.join(f'{op} x{c}' for op, c in ops[n].most_common(None if '--all-ops' in sys.argv else 14))
         print(f'* **{n}**: {top}')
     if meta:
         print(f'\nVGPRs of this single-variant build: {meta.group(1)} (the production kernel holds every variant and is compiled to 64 VGPRs, '

@@ -120,6 +120,23 @@ T = [
     ('v_bfe_i32', 'v_bfe_i32 {d}, {d}, 0, 16', '32'),
     ('v_addc_co_u32', 'v_addc_co_u32 {d}, vcc, {a}, {d}, vcc', '32'),
     ('v_lshlrev_b32_sdwa_byte', 'v_lshlrev_b32_sdwa {d}, {a}, {d} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0', '32'),
+    # the forms of the hue round trip with a literal, an SGPR or a source modifier among their operands (vkx_color.h:
+    # profiles/r12a_chain_hue_forms.md)
+    ('v_or_b32_literal', 'v_or_b32 {d}, 0x4b000000, {d}', '32'),
+    ('v_and_b32_literal', 'v_and_b32 {d}, 0x1ff, {d}', '32'),
+    ('v_mul_f32_literal', 'v_mul_f32 {d}, 0x437f0000, {d}', '32'),
+    ('v_add_f32_literal', 'v_add_f32 {d}, 0x4b400000, {d}', '32'),
+    ('v_mul_f32_sgpr', 'v_mul_f32 {d}, s20, {d}', '32'),
+    ('v_mul_f32_e64_abs', 'v_mul_f32_e64 {d}, {a}, |{d}|', '32'),
+    ('v_fma_f32_sgpr', 'v_fma_f32 {d}, {d}, s20, {a}', '32'),
+    ('v_fma_f32_sgpr_twice', 'v_fma_f32 {d}, {d}, s20, -s20', '32'),
+    ('v_fma_f32_sgpr_inline', 'v_fma_f32 {d}, {d}, s20, 1.0', '32'),
+    ('v_fmamk_f32', 'v_fmamk_f32 {d}, {d}, 0x3b808081, {a}', '32'),
+    ('v_fmaak_f32', 'v_fmaak_f32 {d}, {d}, {a}, 0x4b400000', '32'),
+    ('v_fmac_f32_literal', 'v_fmac_f32 {d}, 0x43800000, {a}', '32'),
+    ('v_sad_u16', 'v_sad_u16 {d}, {d}, {a}, {b}', '32'),
+    ('v_mad_i32_i24_sgpr', 'v_mad_i32_i24 {d}, {d}, {a}, s20', '32'),
+    ('v_cndmask_b32_e64_0_m1', 'v_cndmask_b32_e64 {d}, 0, -1, s[20:21]', '32'),
     ('ds_write_b16', 'ds_write_b16 {a}, {d}', '32lds'),
     ('ds_write_b16_d16_hi', 'ds_write_b16_d16_hi {a}, {d}', '32lds'),
     ('ds_write_b64', 'ds_write_b64 {a32}, {d}', '64lds'),
