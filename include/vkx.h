@@ -1066,6 +1066,47 @@ int vkx_region_extend_masks_dev(vkx_ctx *ctx, const vkx_region_masks_rec *region
                                 const uint8_t *text_mask, ptrdiff_t text_mask_step, int page_h, int page_w, uint8_t *dst,
                                 size_t dst_bytes);
 
+/* ---- the set-operation mask of a list of elements (element/mask.py:126-244) -----------------------------------------------
+ * Mask.from_boxes / from_polygons / from_masks / from_score_maps and, through generate_fill_by_*_mask, the DISTINCT / INTERSECT
+ * forms of the fill_by_* families (element/image.py:371-665, mask.py:283-410, score_map.py:315-520): count(y, x) is the number
+ * of list entries active at the pixel (an entry listed twice counts twice; a polygon counts once where its outline and its spans
+ * both land) and dst = 1 where the mode's predicate holds (UNION count > 0, DISTINCT count == 1, INTERSECT count > 1), else 0.
+ * The result does not depend on the order in which the entries are rasterised.  At most four launches whatever n, none when
+ * n == 0 (dst is zeroed), into a fresh plane: every byte of the h x w window of dst is written, no byte of its padding.
+ * One HOST record an entry: its kind, its window [up, up + h) x [left, left + w) in plane coordinates, and
+ *   VKX_SET_BOX        nothing more: the whole window is active;
+ *   VKX_SET_POLYGON    the range [pts_off, pts_off + pts_cnt) of pts_host (int32 (x, y) pairs, plane coordinates): the
+ *                      cv.fillPoly raster of vkx_fill_poly_mask_u8; the window is the polygon's bounding box;
+ *   VKX_SET_MASK_U8    plane: DEVICE (host for vkx_set_mask) uint8 [h][w] over the window, active where > 0;
+ *   VKX_SET_SCORE_F32  plane: float32 [h][w] over the window, active where > 0.0 (ScoreMap.to_mask()).
+ * plane_step and dst_step are row steps in bytes (at least one row, unused with a single row: the pitch contract of this
+ * header).  windows (optional, window_bytes bytes): entry e's own active raster, dense h_e x w_e at byte window_off_e; with
+ * VKX_SET_WINDOWS_GATED ORed into mode it is ANDed with dst (the window a non-unique fill_by_masks / fill_by_score_maps fills
+ * through).  The bytes between the first and the last polygon window are zeroed; windows of different entries may not share
+ * bytes unless the entries are equal.  Refused (VKX_ERR_INVALID, nothing launched, dst untouched): n < 0 or above 65536, a NULL
+ * dst, a plane side outside 1 .. 32767, an unknown kind or mode, a window outside h x w, a polygon vertex outside its window, a
+ * point range outside pts_host, plane_step or dst_step shorter than the row or negative, a NULL plane for a mask or score map,
+ * window_bytes too small, an element plane, dst and windows that overlap one another.  _dev: asynchronous on the ctx stream
+ * while no polygon has more than 64 vertices (the tables are consumed before the call returns). */
+#define VKX_SET_BOX 0
+#define VKX_SET_POLYGON 1
+#define VKX_SET_MASK_U8 2
+#define VKX_SET_SCORE_F32 3
+#define VKX_SET_UNION 0
+#define VKX_SET_DISTINCT 1
+#define VKX_SET_INTERSECT 2
+#define VKX_SET_WINDOWS_GATED 0x100
+typedef struct vkx_set_elem {
+    int32_t kind, up, left, h, w, pts_off, pts_cnt, reserved;
+    const void *plane;
+    int64_t plane_step;
+    int64_t window_off;
+} vkx_set_elem;
+int vkx_set_mask_dev(vkx_ctx *ctx, const vkx_set_elem *elems_host, int n, const int32_t *pts_host, int n_pts, int mode, int h,
+                     int w, uint8_t *dst, ptrdiff_t dst_step, uint8_t *windows, size_t window_bytes);
+int vkx_set_mask(vkx_ctx *ctx, const vkx_set_elem *elems_host, int n, const int32_t *pts_host, int n_pts, int mode, int h, int w,
+                 uint8_t *dst, ptrdiff_t dst_step, uint8_t *windows, size_t window_bytes);
+
 /* ---- fill_text_line_to_seal_impression (engine/seal_impression/text_line_slot_filler.py:28-205) --------------------------
  * vkx_seal_fill_dev builds the text-line score map of EVERY seal impression of a page: three launches whatever the number of
  * seals and chars, no synchronisation.  The records are HOST tables; the geometry in them (resized width, rotation matrix and

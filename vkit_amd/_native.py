@@ -399,6 +399,9 @@ _SIGNATURES['vkx_region_extend_masks_dev'] = [c_void_p, c_void_p, c_int, c_void_
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 _SIGNATURES['vkx_seal_fill_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_text_lines_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
+_SIGNATURES['vkx_set_mask_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ssize, c_void_p,
+                                   ctypes.c_size_t]
+_SIGNATURES['vkx_set_mask'] = _SIGNATURES['vkx_set_mask_dev']
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
 _lib = None
@@ -2677,3 +2680,103 @@ def text_lines(chars, lines, blob, dst):
                                    lines.ctypes.data if len(lines) else None, len(lines), blob.ctypes.data if blob.size else None,
                                    blob.size, c_void_p(dst.ptr), dst.nbytes))
     dst.invalidate_host()
+
+
+# --------------------------------------------------------------------------------------------------------------
+# the set-operation mask of a list of elements (csrc/element_sets.hip): vkx_set_elem of include/vkx.h
+# --------------------------------------------------------------------------------------------------------------
+SET_BOX, SET_POLYGON, SET_MASK_U8, SET_SCORE_F32 = 0, 1, 2, 3
+SET_UNION, SET_DISTINCT, SET_INTERSECT, SET_WINDOWS_GATED = 0, 1, 2, 0x100
+SET_ELEM_DTYPE = np.dtype([('kind', np.int32), ('up', np.int32), ('left', np.int32), ('h', np.int32), ('w', np.int32),
+                           ('pts_off', np.int32), ('pts_cnt', np.int32), ('reserved', np.int32), ('plane', np.uint64),
+                           ('plane_step', np.int64), ('window_off', np.int64)], align=True)
+assert SET_ELEM_DTYPE.itemsize == 56
+_SET_MODES = {'UNION': SET_UNION, 'DISTINCT': SET_DISTINCT, 'INTERSECT': SET_INTERSECT}
+
+
+def set_mask(elements, shape, mode, want_windows=False, ctx=None, gated=False):
+    """vkx_set_mask_dev: the uint8 (h, w) plane that is 1 where the number of ``elements`` active at the pixel meets ``mode``
+    (SET_UNION > 0, SET_DISTINCT == 1, SET_INTERSECT > 1, or an enum member of those names).  An element is
+      a box-like object (``up`` / ``left`` / ``height`` / ``width``): its window is active;
+      a signed-integer (N, 2) array of (x, y) vertices in plane coordinates: the cv.fillPoly raster, window = its bounding box;
+      a uint8 or float32 plane (numpy or DevArray), active where > 0, over the whole plane or, as ``(plane, box_like)`` or
+      ``(plane, (up, left))``, over that window.
+    At most FOUR launches whatever the number of elements, asynchronous while no polygon has more than 64 vertices.  Host planes
+    are uploaded for the call.  Returns a DevArray in resident mode or when an element plane is one, else a host array; with
+    ``want_windows`` also the list of every element's own active raster over its window (``gated``: ANDed with the result), as
+    views of one packed block."""
+    mode = _SET_MODES[mode.name] if hasattr(mode, 'name') else int(mode)
+    h, w = int(shape[0]), int(shape[1])
+    elements = list(elements)
+    resident_out = resident_mode()
+    for el in elements:
+        plane = el[0] if isinstance(el, tuple) else el
+        if isinstance(plane, DevArray):
+            resident_out = True
+            ctx = ctx or plane.ctx
+    ctx = ctx or default_ctx()
+    # the records column by column: one numpy assignment a field, the polygons' bounding boxes from one reduceat
+    n = len(elements)
+    kinds, geos, planes, steps = [SET_POLYGON] * n, [None] * n, [0] * n, [0] * n
+    points, poly_at, keep = [], [], []
+    for i, el in enumerate(elements):
+        window = None
+        if type(el) is tuple:
+            el, window = el
+        if isinstance(el, np.ndarray) and el.ndim == 2 and el.shape[1] == 2 and el.dtype.kind == 'i':
+            if not len(el):
+                raise ValueError('a polygon without points')
+            points.append(el)
+            poly_at.append(i)
+        elif hasattr(el, 'up') and hasattr(el, 'left'):
+            kinds[i], geos[i] = SET_BOX, (el.up, el.left, el.height, el.width)
+        elif isinstance(el, (np.ndarray, DevArray)) and el.ndim == 2 and np.dtype(el.dtype) in (_U8, _F32):
+            is_f32 = np.dtype(el.dtype) == _F32
+            dev = ctx.to_device(el)
+            if dev.ctx is not ctx:
+                raise ValueError('the element planes live on one context')
+            keep.append(dev)
+            if window is None:
+                up, left = 0, 0
+            elif hasattr(window, 'up'):
+                if (window.height, window.width) != tuple(el.shape):
+                    raise ValueError(f'plane shape {tuple(el.shape)} != its window {(window.height, window.width)}')
+                up, left = window.up, window.left
+            else:
+                up, left = window
+            kinds[i], geos[i] = (SET_SCORE_F32 if is_f32 else SET_MASK_U8), (up, left, el.shape[0], el.shape[1])
+            planes[i], steps[i] = dev.ptr, el.shape[1] * (4 if is_f32 else 1)
+        else:
+            raise TypeError(f'set_mask: not an element: {type(el).__name__}')
+    recs = np.zeros(n, SET_ELEM_DTYPE)
+    flat = np.ascontiguousarray(np.concatenate(points), dtype=np.int32) if points else np.zeros((0, 2), np.int32)
+    n_pts = len(flat)
+    if points:
+        counts = np.fromiter((len(p) for p in points), np.int64, len(points))
+        starts = np.concatenate(([0], np.cumsum(counts)[:-1]))
+        lo, hi = np.minimum.reduceat(flat, starts, axis=0), np.maximum.reduceat(flat, starts, axis=0)
+        boxes = np.stack([lo[:, 1], lo[:, 0], hi[:, 1] - lo[:, 1] + 1, hi[:, 0] - lo[:, 0] + 1], axis=1).tolist()
+        for i, box in zip(poly_at, boxes):
+            geos[i] = box
+        recs['pts_off'][poly_at], recs['pts_cnt'][poly_at] = starts, counts
+    geo = np.array(geos, np.int64).reshape(n, 4)
+    recs['kind'], recs['plane'], recs['plane_step'] = kinds, planes, steps
+    recs['up'], recs['left'], recs['h'], recs['w'] = geo[:, 0], geo[:, 1], geo[:, 2], geo[:, 3]
+    window_bytes = 0
+    if want_windows and n:
+        sizes = (geo[:, 2] * geo[:, 3] + 255) & ~255
+        recs['window_off'] = np.cumsum(sizes) - sizes
+        window_bytes = int(sizes.sum())
+    dst = ctx.dev_empty((h, w), np.uint8)
+    block = ctx.dev_empty((max(window_bytes, 1),), np.uint8) if want_windows else None
+    check(lib().vkx_set_mask_dev(ctx.handle, recs.ctypes.data if len(recs) else None, len(recs), flat.ctypes.data if n_pts else None,
+                                 n_pts, mode | (SET_WINDOWS_GATED if gated else 0), h, w, c_void_p(dst.ptr), w,
+                                 c_void_p(block.ptr) if want_windows else None, window_bytes))
+    del keep
+    if not want_windows:
+        return dst if resident_out else dst.host()
+    layout = zip(recs['window_off'].tolist(), geo[:, 2].tolist(), geo[:, 3].tolist())
+    if resident_out:
+        return dst, [DevView(block, off, (wh, ww)) for off, wh, ww in layout]
+    packed = block.host()
+    return dst.host(), [packed[off:off + wh * ww].reshape(wh, ww) for off, wh, ww in layout]

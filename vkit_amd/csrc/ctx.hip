@@ -117,6 +117,8 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->rf_tables);
     scratch_release(&ctx->rm_tables);
     scratch_release(&ctx->rm_bits);
+    scratch_release(&ctx->set_tables);
+    scratch_release(&ctx->set_planes);
     scratch_release(&ctx->seal_tables);
     scratch_release(&ctx->seal_planes);
     scratch_release(&ctx->text_tables);

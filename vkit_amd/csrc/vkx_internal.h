@@ -127,6 +127,7 @@ struct vkx_ctx {
                                               // bitmaps of the workgroups when they do not fit LDS
     vkx_scratch rf_tables;                    // text-region flattening (region_flatten.hip): the staged records and tap tables of the last call
     vkx_scratch rm_tables, rm_bits;           // text-region masks (region_masks.hip): the overflow flag + staged tables; the o / d / r bit planes of the last call
+    vkx_scratch set_tables, set_planes;       // element set masks (element_sets.hip): the overflow flag + staged tables; the two index planes (int [2][h * w]) of the last call
     vkx_scratch seal_tables, seal_planes;     // seal impressions (seal_fill.hip): the staged records, tap tables and host planes of the last call; the char planes + per-seal maxima
     vkx_scratch text_tables, text_planes;     // text lines (text_line.hip): the staged records, resize tables and glyph blob of the last call; the pasted planes of its resized lines
     vkx_scratch glass_win;                    // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)

@@ -3,6 +3,6 @@ from .point import Point, PointList, PointTuple
 from .box import Box
 from .polygon import Polygon
 from .soup import PointArray, PolygonSoup
-from .mask import Mask
-from .score_map import ScoreMap
+from .mask import Mask, MaskSetItemConfig
+from .score_map import ScoreMap, ScoreMapSetItemConfig
 from .image import Image, ImageMode, ImageSetItemConfig

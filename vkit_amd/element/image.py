@@ -12,7 +12,7 @@ import numpy as np
 
 from ._writable import LazyMat, WritableContext
 from .opt import generate_shape_and_resized_shape
-from .type import Shapable
+from .type import ElementSetOperationMode, Shapable
 
 
 @unique
@@ -178,6 +178,65 @@ class Image(LazyMat, Shapable):
         with self.writable_context:
             object.__setattr__(self, '_mat', mat)
 
+    # ---- fills of a list of elements (reference image.py:371-665): vkit_amd/element/_sets.py
+    @classmethod
+    def check_values_and_alphas_uniqueness(cls, values, alphas):
+        return check_elements_uniqueness(values) and check_elements_uniqueness(alphas)
+
+    @classmethod
+    def unpack_element_value_tuples(cls, element_value_tuples):
+        """(element, value) or (element, value, alpha) tuples -> elements, values, alphas (1.0 where none is given)."""
+        elements, values, alphas = [], [], []
+        for element_value_tuple in element_value_tuples:
+            if len(element_value_tuple) == 2:
+                element, value = element_value_tuple
+                alpha = 1.0
+            else:
+                element, value, alpha = element_value_tuple
+            elements.append(element)
+            values.append(value)
+            alphas.append(alpha)
+        return elements, values, alphas
+
+    def _fill_by_tuples(self, kind, tuples, mode, skip_values_uniqueness_check):
+        elements, values, alphas = self.unpack_element_value_tuples(tuples)
+        _sets.fill_by(self, kind, elements, values, alphas, mode, skip_values_uniqueness_check=skip_values_uniqueness_check)
+
+    def fill_by_box_value_tuples(self, box_value_tuples, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                 skip_values_uniqueness_check: bool = False):
+        self._fill_by_tuples(_sets.BOXES, box_value_tuples, mode, skip_values_uniqueness_check)
+
+    def fill_by_boxes(self, boxes, value, alpha: Union[np.ndarray, float] = 1.0,
+                      mode: ElementSetOperationMode = ElementSetOperationMode.UNION):
+        self.fill_by_box_value_tuples(((box, value, alpha) for box in boxes), mode=mode, skip_values_uniqueness_check=True)
+
+    def fill_by_polygon_value_tuples(self, polygon_value_tuples, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                     skip_values_uniqueness_check: bool = False):
+        self._fill_by_tuples(_sets.POLYGONS, polygon_value_tuples, mode, skip_values_uniqueness_check)
+
+    def fill_by_polygons(self, polygons, value, alpha: Union[np.ndarray, float] = 1.0,
+                         mode: ElementSetOperationMode = ElementSetOperationMode.UNION):
+        self.fill_by_polygon_value_tuples(((polygon, value, alpha) for polygon in polygons), mode=mode,
+                                          skip_values_uniqueness_check=True)
+
+    def fill_by_mask_value_tuples(self, mask_value_tuples, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                  skip_values_uniqueness_check: bool = False):
+        self._fill_by_tuples(_sets.MASKS, mask_value_tuples, mode, skip_values_uniqueness_check)
+
+    def fill_by_masks(self, masks, value, alpha: Union[np.ndarray, float] = 1.0,
+                      mode: ElementSetOperationMode = ElementSetOperationMode.UNION):
+        self.fill_by_mask_value_tuples(((mask, value, alpha) for mask in masks), mode=mode, skip_values_uniqueness_check=True)
+
+    def fill_by_score_map_value_tuples(self, score_map_value_tuples,
+                                       mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                       skip_values_uniqueness_check: bool = False):
+        # the score maps are the selection and the alpha: alphas given with them are ignored, as in the reference
+        self._fill_by_tuples(_sets.SCORE_MAPS, score_map_value_tuples, mode, skip_values_uniqueness_check)
+
+    def fill_by_score_maps(self, score_maps, value, mode: ElementSetOperationMode = ElementSetOperationMode.UNION):
+        self.fill_by_score_map_value_tuples(((score_map, value) for score_map in score_maps), mode=mode,
+                                            skip_values_uniqueness_check=True)
+
     def __setitem__(self, element, config):
         """image[box | polygon | mask | score_map] = value | ImageSetItemConfig (reference image.py:667-712)."""
         if isinstance(config, ImageSetItemConfig):
@@ -321,3 +380,5 @@ class Image(LazyMat, Shapable):
 
 from .box import Box  # noqa: E402
 from .score_map import ScoreMap  # noqa: E402
+from .uniqueness import check_elements_uniqueness  # noqa: E402
+from . import _sets  # noqa: E402

@@ -13,6 +13,13 @@ _LUT_INVERT = (np.arange(256) == 0).astype(np.uint8).reshape(1, 256)           #
 _LUT_X255 = ((np.arange(256) > 0).astype(np.uint8) * 255).reshape(1, 256)      # (mat > 0).astype(uint8) * 255
 
 
+@attrs.define
+class MaskSetItemConfig:
+    value: Union['Mask', np.ndarray, int] = 1
+    keep_max_value: bool = False
+    keep_min_value: bool = False
+
+
 @attrs.define(frozen=True, eq=False)
 class Mask(LazyMat, Shapable):
     _mat: np.ndarray = attrs.field(alias='mat')
@@ -67,6 +74,23 @@ class Mask(LazyMat, Shapable):
             box.extract_np_array(count)[...] += 1
         return cls._from_np_active_count(shape, mode, count, attached_box)
 
+    # One vkx_set_mask call each (csrc/element_sets.hip) instead of one count pass an element (reference mask.py:174-244);
+    # a Box as ``shape_or_box`` takes the elements relative to it and attaches itself to the result.
+    @classmethod
+    def from_polygons(cls, shape_or_box, polygons: Iterable['Polygon'],
+                      mode: ElementSetOperationMode = ElementSetOperationMode.UNION):
+        return _sets.build_set_mask(_sets.POLYGONS, shape_or_box, polygons, mode)[0]
+
+    @classmethod
+    def from_masks(cls, shape_or_box, masks: Iterable['Mask'],
+                   mode: ElementSetOperationMode = ElementSetOperationMode.UNION):
+        return _sets.build_set_mask(_sets.MASKS, shape_or_box, masks, mode)[0]
+
+    @classmethod
+    def from_score_maps(cls, shape_or_box, score_maps: Iterable['ScoreMap'],
+                        mode: ElementSetOperationMode = ElementSetOperationMode.UNION):
+        return _sets.build_set_mask(_sets.SCORE_MAPS, shape_or_box, score_maps, mode)[0]
+
     # ---- properties
     @property
     def height(self):
@@ -100,6 +124,47 @@ class Mask(LazyMat, Shapable):
     def assign_mat(self, mat: np.ndarray):
         with self.writable_context:
             object.__setattr__(self, '_mat', mat)
+
+    # ---- fills of a list of elements (reference mask.py:283-410): vkit_amd/element/_sets.py
+    @classmethod
+    def unpack_element_value_pairs(cls, element_value_pairs):
+        return _sets.unpack_element_value_pairs(element_value_pairs)
+
+    def fill_by_box_value_pairs(self, box_value_pairs, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                keep_max_value: bool = False, keep_min_value: bool = False,
+                                skip_values_uniqueness_check: bool = False):
+        boxes, values = self.unpack_element_value_pairs(box_value_pairs)
+        _sets.fill_by(self, _sets.BOXES, boxes, values, None, mode, keep_max_value, keep_min_value, skip_values_uniqueness_check)
+
+    def fill_by_boxes(self, boxes: Iterable['Box'], value: Union['Mask', np.ndarray, int] = 1,
+                      mode: ElementSetOperationMode = ElementSetOperationMode.UNION, keep_max_value: bool = False,
+                      keep_min_value: bool = False):
+        self.fill_by_box_value_pairs(((box, value) for box in boxes), mode=mode, keep_max_value=keep_max_value,
+                                     keep_min_value=keep_min_value, skip_values_uniqueness_check=True)
+
+    def fill_by_polygon_value_pairs(self, polygon_value_pairs, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                    keep_max_value: bool = False, keep_min_value: bool = False,
+                                    skip_values_uniqueness_check: bool = False):
+        polygons, values = self.unpack_element_value_pairs(polygon_value_pairs)
+        _sets.fill_by(self, _sets.POLYGONS, polygons, values, None, mode, keep_max_value, keep_min_value,
+                      skip_values_uniqueness_check)
+
+    def fill_by_polygons(self, polygons: Iterable['Polygon'], value: Union['Mask', np.ndarray, int] = 1,
+                         mode: ElementSetOperationMode = ElementSetOperationMode.UNION, keep_max_value: bool = False,
+                         keep_min_value: bool = False):
+        self.fill_by_polygon_value_pairs(((polygon, value) for polygon in polygons), mode=mode, keep_max_value=keep_max_value,
+                                         keep_min_value=keep_min_value, skip_values_uniqueness_check=True)
+
+    def __setitem__(self, element, config):
+        """mask[box | polygon] = value | MaskSetItemConfig (reference mask.py:412-437)."""
+        if isinstance(config, MaskSetItemConfig):
+            value, keep_max_value, keep_min_value = config.value, config.keep_max_value, config.keep_min_value
+        else:
+            value, keep_max_value, keep_min_value = config, False, False
+        element.fill_mask(mask=self, value=value, keep_min_value=keep_min_value, keep_max_value=keep_max_value)
+
+    def __getitem__(self, element):
+        return element.extract_mask(self)
 
     def to_inverted_mask(self):
         if self.on_device:
@@ -212,13 +277,19 @@ class Mask(LazyMat, Shapable):
         self.to_inverted_mask().fill_image(out, value=0)
         return out
 
+    def extract_score_map(self, score_map: 'ScoreMap'):
+        out = self.equivalent_box.extract_score_map(score_map).copy()
+        self.to_inverted_mask().fill_score_map(out, value=0.0)
+        return out
+
 
 def generate_fill_by_masks_mask(shape, masks, mode: ElementSetOperationMode):
     if mode == ElementSetOperationMode.UNION:
         return None
-    raise NotImplementedError('non-UNION mask set operations are outside the accelerated path')
+    return Mask.from_masks(shape, masks, mode)
 
 
 from .box import Box  # noqa: E402
 from .score_map import ScoreMap  # noqa: E402
 from .image import Image  # noqa: E402
+from . import _sets  # noqa: E402

@@ -10,7 +10,7 @@ from typing import Iterable, Optional, Sequence, Tuple, Union
 import attrs
 import numpy as np
 
-from .type import Shapable
+from .type import ElementSetOperationMode, Shapable
 
 
 @attrs.define(frozen=True, eq=False)
@@ -134,6 +134,9 @@ class Polygon:
                        keep_min_value: bool = False):
         self.mask.fill_score_map(score_map=score_map, value=value, keep_max_value=keep_max_value,
                                  keep_min_value=keep_min_value)
+
+    def extract_score_map(self, score_map: 'ScoreMap'):
+        return self.mask.extract_score_map(score_map)
 
     def extract_image(self, image: 'Image'):
         return self.mask.extract_image(image)
@@ -286,7 +289,9 @@ class Polygon:
 
 
 def generate_fill_by_polygons_mask(shape, polygons, mode):
-    raise NotImplementedError('polygon set operations are outside the accelerated path')
+    if mode == ElementSetOperationMode.UNION:
+        return None
+    return Mask.from_polygons(shape, polygons, mode)
 
 
 def polygon_centroids(xy: np.ndarray) -> np.ndarray:

@@ -3,7 +3,7 @@
 On the hot path a ScoreMap is (a) an element that grid / affine distortions remap with float32 bilinear
 weights and (b) the per-pixel alpha of a text-line layer in the page composite.
 """
-from typing import Optional, Tuple
+from typing import Iterable, Optional, Tuple, Union
 
 import attrs
 import numpy as np
@@ -12,6 +12,13 @@ from vkit_amd import _native
 from ._writable import LazyMat, WritableContext
 from .opt import _deferred_stack, generate_shape_and_resized_shape
 from .type import ElementSetOperationMode, Shapable
+
+
+@attrs.define
+class ScoreMapSetItemConfig:
+    value: Union['ScoreMap', np.ndarray, float] = 1.0
+    keep_max_value: bool = False
+    keep_min_value: bool = False
 
 
 @attrs.define(frozen=True, eq=False)
@@ -75,6 +82,73 @@ class ScoreMap(LazyMat, Shapable):
         with self.writable_context:
             object.__setattr__(self, '_mat', mat)
 
+    # ---- fills of a list of elements (reference score_map.py:315-520): vkit_amd/element/_sets.py
+    @classmethod
+    def unpack_element_value_pairs(cls, is_prob: bool, element_value_pairs):
+        elements, values = [], []
+        for element, value in element_value_pairs:
+            elements.append(element)
+            if is_prob:
+                if isinstance(value, ScoreMap):
+                    assert (0.0 <= value.mat).all() and (value.mat <= 1.0).all()
+                elif isinstance(value, np.ndarray):
+                    assert (0.0 <= value).all() and (value <= 1.0).all()
+                elif isinstance(value, float):
+                    assert 0.0 <= value <= 1.0
+                else:
+                    raise NotImplementedError()
+            values.append(value)
+        return elements, values
+
+    def _fill_by_pairs(self, kind, pairs, mode, keep_max_value, keep_min_value, skip_values_uniqueness_check):
+        elements, values = self.unpack_element_value_pairs(self.is_prob, pairs)
+        _sets.fill_by(self, kind, elements, values, None, mode, keep_max_value, keep_min_value, skip_values_uniqueness_check)
+
+    def fill_by_box_value_pairs(self, box_value_pairs, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                keep_max_value: bool = False, keep_min_value: bool = False,
+                                skip_values_uniqueness_check: bool = False):
+        self._fill_by_pairs(_sets.BOXES, box_value_pairs, mode, keep_max_value, keep_min_value, skip_values_uniqueness_check)
+
+    def fill_by_boxes(self, boxes: Iterable['Box'], value: Union['ScoreMap', np.ndarray, float] = 1.0,
+                      mode: ElementSetOperationMode = ElementSetOperationMode.UNION, keep_max_value: bool = False,
+                      keep_min_value: bool = False):
+        self.fill_by_box_value_pairs(((box, value) for box in boxes), mode=mode, keep_max_value=keep_max_value,
+                                     keep_min_value=keep_min_value, skip_values_uniqueness_check=True)
+
+    def fill_by_polygon_value_pairs(self, polygon_value_pairs, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                    keep_max_value: bool = False, keep_min_value: bool = False,
+                                    skip_values_uniqueness_check: bool = False):
+        self._fill_by_pairs(_sets.POLYGONS, polygon_value_pairs, mode, keep_max_value, keep_min_value,
+                            skip_values_uniqueness_check)
+
+    def fill_by_polygons(self, polygons: Iterable['Polygon'], value: Union['ScoreMap', np.ndarray, float] = 1.0,
+                         mode: ElementSetOperationMode = ElementSetOperationMode.UNION, keep_max_value: bool = False,
+                         keep_min_value: bool = False):
+        self.fill_by_polygon_value_pairs(((polygon, value) for polygon in polygons), mode=mode, keep_max_value=keep_max_value,
+                                         keep_min_value=keep_min_value, skip_values_uniqueness_check=True)
+
+    def fill_by_mask_value_pairs(self, mask_value_pairs, mode: ElementSetOperationMode = ElementSetOperationMode.UNION,
+                                 keep_max_value: bool = False, keep_min_value: bool = False,
+                                 skip_values_uniqueness_check: bool = False):
+        self._fill_by_pairs(_sets.MASKS, mask_value_pairs, mode, keep_max_value, keep_min_value, skip_values_uniqueness_check)
+
+    def fill_by_masks(self, masks: Iterable['Mask'], value: Union['ScoreMap', np.ndarray, float] = 1.0,
+                      mode: ElementSetOperationMode = ElementSetOperationMode.UNION, keep_max_value: bool = False,
+                      keep_min_value: bool = False):
+        self.fill_by_mask_value_pairs(((mask, value) for mask in masks), mode=mode, keep_max_value=keep_max_value,
+                                      keep_min_value=keep_min_value, skip_values_uniqueness_check=True)
+
+    def __setitem__(self, element, config):
+        """score_map[box | polygon | mask] = value | ScoreMapSetItemConfig (reference score_map.py:521-550)."""
+        if isinstance(config, ScoreMapSetItemConfig):
+            value, keep_max_value, keep_min_value = config.value, config.keep_max_value, config.keep_min_value
+        else:
+            value, keep_max_value, keep_min_value = config, False, False
+        element.fill_score_map(score_map=self, value=value, keep_min_value=keep_min_value, keep_max_value=keep_max_value)
+
+    def __getitem__(self, element):
+        return element.extract_score_map(self)
+
     def to_shifted_score_map(self, offset_y: int = 0, offset_x: int = 0):
         assert self.box
         return attrs.evolve(self, box=self.box.to_shifted_box(offset_y=offset_y, offset_x=offset_x))
@@ -135,9 +209,10 @@ class ScoreMap(LazyMat, Shapable):
 def generate_fill_by_score_maps_mask(shape, score_maps, mode: ElementSetOperationMode):
     if mode == ElementSetOperationMode.UNION:
         return None
-    raise NotImplementedError('non-UNION score-map set operations are outside the accelerated path')
+    return Mask.from_score_maps(shape, score_maps, mode)
 
 
 from .box import Box  # noqa: E402
 from .mask import Mask  # noqa: E402
 from .image import Image  # noqa: E402
+from . import _sets  # noqa: E402
