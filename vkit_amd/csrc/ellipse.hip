@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "vkx_internal.h"
+#include "vkx_host_tables.h"
 
 namespace {
 
@@ -200,22 +201,6 @@ __global__ __launch_bounds__(256) void k_ellipse_segments(const Segment *__restr
     }
 }
 
-// OpenCV's SinTable: sin of whole degrees 0 .. 450 as float literals with seven decimals
-const float *sin_table()
-{
-    static float table[451];
-    static bool ready = false;
-    if (!ready) {
-        for (int d = 0; d <= 450; d++) {
-            char text[32];
-            snprintf(text, sizeof text, "%.7f", std::sin((double)d * 3.14159265358979323846 / 180.0));
-            table[d] = strtof(text, nullptr);
-        }
-        ready = true;
-    }
-    return table;
-}
-
 int64_t round_vertex(double v)
 {
     // EllipseEx rounds in two steps so that cvRound never sees more than 32 bits
@@ -226,7 +211,7 @@ int64_t round_vertex(double v)
 // The open polyline cv.ellipse draws for one axis-aligned, full ellipse, appended to `out` as segments
 void ellipse_segments(int cx, int cy, int ax, int ay, std::vector<Segment> &out)
 {
-    const float *sn = sin_table();
+    const float *sn = vkx_host_tables::sin_table();     // OpenCV's SinTable, shared by every context of the process
     const int64_t ccx = (int64_t)cx * kOne, ccy = (int64_t)cy * kOne;
     const int64_t aw = std::llabs((int64_t)ax * kOne), ah = std::llabs((int64_t)ay * kOne);
     const int size = (int)((std::max(aw, ah) + kHalf) >> kShift);

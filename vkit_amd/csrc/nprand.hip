@@ -31,6 +31,7 @@
 // and the caller redraws that plane with numpy on the host.  Expected rate: < 1e-6 per 2048^2 plane.
 #include "vkx_internal.h"
 #include "np_ziggurat.h"
+#include "vkx_host_tables.h"
 
 #include <string.h>
 #include <algorithm>
@@ -53,51 +54,8 @@ constexpr int kTile = 64 * kRounds;       // raw draws per tile
 constexpr double kNorR = 3.6541528853610087963519472518;
 constexpr double kNorInvR = 0.27366123732975827203338247596;
 
-#define PCG_MULT ((((u128)0x2360ED051FC65DA4ull) << 64) | (u128)0x4385DF649FCCF645ull)
-
-// Stream-independent jump constants: s_{k + j} = A^j s_k + inc * G_j with G_j = 1 + A + ... + A^(j-1) (mod 2^128).
-struct JumpTabs {
-    uint64_t pow2[64][4];    // j = 2^i: A^j lo, hi, G_j lo, hi
-    uint64_t lane[64][4];    // j = l + 1
-    uint64_t a64[2], g64[2];
-    uint64_t a128[2], g128[2];
-};
-static JumpTabs g_jump_host;
-static bool g_jump_host_ready = false;
-
-static void jump_consts(u128 j, u128 *a, u128 *g)
-{
-    u128 acc_mult = 1, acc_plus = 0, cur_mult = PCG_MULT, cur_plus = 1;
-    while (j > 0) {
-        if (j & 1) {
-            acc_mult *= cur_mult;
-            acc_plus = acc_plus * cur_mult + cur_plus;
-        }
-        cur_plus = (cur_mult + 1) * cur_plus;
-        cur_mult *= cur_mult;
-        j >>= 1;
-    }
-    *a = acc_mult;
-    *g = acc_plus;
-}
-
-static void build_jump_tabs()
-{
-    if (g_jump_host_ready) return;
-    auto put = [](uint64_t *w, u128 a, u128 g) {
-        w[0] = (uint64_t)a; w[1] = (uint64_t)(a >> 64); w[2] = (uint64_t)g; w[3] = (uint64_t)(g >> 64);
-    };
-    u128 a, g;
-    for (int i = 0; i < 64; i++) { jump_consts((u128)1 << i, &a, &g); put(g_jump_host.pow2[i], a, g); }
-    for (int l = 0; l < 64; l++) { jump_consts((u128)(l + 1), &a, &g); put(g_jump_host.lane[l], a, g); }
-    jump_consts(64, &a, &g);
-    g_jump_host.a64[0] = (uint64_t)a; g_jump_host.a64[1] = (uint64_t)(a >> 64);
-    g_jump_host.g64[0] = (uint64_t)g; g_jump_host.g64[1] = (uint64_t)(g >> 64);
-    jump_consts(128, &a, &g);
-    g_jump_host.a128[0] = (uint64_t)a; g_jump_host.a128[1] = (uint64_t)(a >> 64);
-    g_jump_host.g128[0] = (uint64_t)g; g_jump_host.g128[1] = (uint64_t)(g >> 64);
-    g_jump_host_ready = true;
-}
+#define PCG_MULT VKX_PCG_MULT
+using vkx_host_tables::JumpTabs;      // the stream-independent jump constants, one read-only table for the process
 
 struct NpTabs {              // uploaded once per context
     JumpTabs jump;
@@ -1464,12 +1422,11 @@ __global__ void __launch_bounds__(256) k_np_tail_log_est(const uint64_t *__restr
 static int np_tables(vkx_ctx *ctx, const NpTabs **out)
 {
     if (!ctx->np_tabs.ptr) {
-        build_jump_tabs();
         vkx_tables tab(ctx);
         int rc = tab.take(sizeof(NpTabs));
         if (rc) return rc;
         NpTabs *t = tab.at<NpTabs>(0);
-        t->jump = g_jump_host;
+        t->jump = vkx_host_tables::jump_tabs();
         memcpy(t->ki, kNpZigK, 2048);
         memcpy(t->wi, kNpZigW, 2048);
         memcpy(t->fi, kNpZigF, 2048);
@@ -1569,8 +1526,9 @@ static int np_chunk_prepare(vkx_ctx *ctx, NpChunk &c)
         if ((rc = tab.take((size_t)c.n_jobs * sizeof(NpJob)))) return rc;
         hj = tab.at<NpJob>(0);
     }
-    const u128 g64 = ((u128)g_jump_host.g64[1] << 64) | g_jump_host.g64[0];
-    const u128 g128 = ((u128)g_jump_host.g128[1] << 64) | g_jump_host.g128[0];
+    const JumpTabs &jump = vkx_host_tables::jump_tabs();
+    const u128 g64 = ((u128)jump.g64[1] << 64) | jump.g64[0];
+    const u128 g128 = ((u128)jump.g128[1] << 64) | jump.g128[0];
     long long tile_base = 0;
     for (int i = 0; i < c.n_jobs; i++) {
         const vkx_np_job &j = c.jobs[i];
