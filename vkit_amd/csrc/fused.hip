@@ -63,6 +63,8 @@ constexpr int CGROUP = VKX_FUSED_CGROUP;      // window rows a wavefront maps + 
 
 // explicit global address space: pointers loaded from a descriptor in memory would otherwise be "flat"
 #define VKX_GLOBAL __attribute__((address_space(1)))
+// constant address space: memory that no one writes while the kernel runs; a load through a uniform pointer is a scalar load
+#define VKX_CONSTANT __attribute__((address_space(4)))
 typedef const uint8_t VKX_GLOBAL *gsrc_t;
 typedef uint8_t VKX_GLOBAL *gdst_t;
 typedef unsigned long long u64_u1 __attribute__((aligned(1)));
@@ -284,13 +286,6 @@ typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t dot2_u16_ks(uint32_t k_uniform, uint32_t b, uint32_t c)
 {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2_t, k_uniform), __builtin_bit_cast(ushort2_t, b), c, false);
-}
-
-// a wave-uniform 64-bit value, moved into SGPRs
-__device__ __forceinline__ uint64_t uniform64(uint64_t v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
 }
 
 // nx / de and ny / de, both correctly rounded: the instruction sequence the compiler emits for an IEEE double division
@@ -948,59 +943,92 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
     // border tile and the streak instance fetch the 3 samples of the lane's own pixel (a dword + a short: exactly 6 bytes).
     // The descriptor fields only this phase needs are read here, through a pointer the optimiser cannot trace back:
     // hoisted to the top of the kernel they would sit in SGPRs through phases A - D and spill.
-    // (a global-address-space pointer: no FLAT instruction anywhere in this kernel -- flat loads tick both memory counters
-    //  and return out of order with respect to LDS operations)
-    const ItemDev VKX_GLOBAL *ite_ = (const ItemDev VKX_GLOBAL *)&it;
+    // (a CONSTANT-address-space pointer: the descriptors are read-only for the life of the kernel and the pointer is uniform, so
+    //  every field below arrives through the scalar unit, as one batch of s_load behind one lgkmcnt wait, straight into SGPRs.
+    //  Through a global pointer the compiler cannot know that the stores of phases A - D left the descriptor alone: it read the
+    //  fields with vector loads -- a vmcnt(0) round trip each, hue_on behind all eight noise rows -- and v_readfirstlane pairs.
+    //  No FLAT instruction anywhere in this kernel either way.)
+    const ItemDev VKX_CONSTANT *ite_ = (const ItemDev VKX_CONSTANT *)&it;
     asm volatile("" : "+s"(ite_));
-    const ItemDev VKX_GLOBAL &ite = *ite_;
-    // (such loads come back in VGPRs; the row address arithmetic wants them scalar)
-    const gdst_t dst = (gdst_t)uniform64((uint64_t)ite.dst);
-    const int16_t VKX_GLOBAL *noise = (const int16_t VKX_GLOBAL *)uniform64((uint64_t)ite.noise);
-    const ptrdiff_t dstride = (ptrdiff_t)uniform64((uint64_t)ite.dstride), nstride = (ptrdiff_t)uniform64((uint64_t)ite.nstride);
+    const ItemDev VKX_CONSTANT &ite = *ite_;
+    // lane r < 8: the parked record of this wavefront's row r (tiled noise).  Asked for BEFORE the descriptor fields and whether
+    // the noise is tiled or not, so that the LDS read and the scalar loads are one batch behind one lgkmcnt wait (an EMPTY tile
+    // parks the record only now and has to know first).
+    typedef const char VKX_GLOBAL *gbytes_t;
+    u32x2 nrow = {0u, 0u};
+    if constexpr (!EMPTY) nrow = *(const u32x2 *)(lnrow + 2 * (wave + NWAVES * (lane & 7)));
+    const gdst_t dst = (gdst_t)ite.dst;
+    const gbytes_t nbase = (gbytes_t)ite.noise;
+    const ptrdiff_t dstride = ite.dstride, nstride = ite.nstride;
+    const int hue_on_ = ite.hue_on, hue_delta = ite.hue_delta;
+    const int noise_tiled = ite.noise_tiled;      // (read whether there is noise or not: behind the test of `noise` it is a second round trip)
+    // (all of them wanted HERE, as operands of an empty statement: left alone, the loads sink to their uses, and the test of `noise`,
+    //  the row record, the strides and the hue fields are three waits one behind the other.  Operands only -- a scalar RESULT of an
+    //  asm statement counts as divergent, and the row address arithmetic would move to the vector unit.)
+    asm volatile("" : "+v"(nrow.x), "+v"(nrow.y)
+                    : "s"(dst), "s"(nbase), "s"(dstride), "s"(nstride), "s"(hue_on_), "s"(hue_delta), "s"(noise_tiled));
+    const bool noise = nbase != nullptr, hue_on = hue_on_ != 0;
+    const bool tiled = noise & (noise_tiled != 0);
     uint32_t nzA[ROWS_PER_WAVE];
     uint32_t nzB[ROWS_PER_WAVE];
-    // (as the other descriptor fields of this phase: read again here rather than kept in SGPRs through phases A - D)
-    const bool tiled = noise && __builtin_amdgcn_readfirstlane(ite.noise_tiled) != 0;
+    // The rows cy = wave + NWAVES i of this wavefront: all but the last few lie inside an interior tile whatever the wavefront.
+    // Said at compile time, because the wavefront index is a run-time value to the compiler: a branch per row otherwise, and a
+    // skipped row's registers, reused by the next one, put a vmcnt(0) in front of it.
+    auto row_live = [&](int i, int cy) { return (INTERIOR && RC >= 0 && NWAVES * (i + 1) <= tile_height(RC >= 0 ? RC : 0)) || cy < th; };
     if constexpr (EMPTY) {                   // (no phase A: parked here)
         if (nrows_here) *(u32x2 *)(lnrow + 2 * nrow_y) = nrec;
-        if (tiled) __syncthreads();
+        if (tiled) {
+            __syncthreads();
+            nrow = *(const u32x2 *)(lnrow + 2 * (wave + NWAVES * (lane & 7)));
+        }
     }
+    const uint32_t never = tiled ? 0u : 0xffffu;       // a plane's rows cross nothing (a scalar, or-ed to the row's boundary)
     const int full4 = (tw >> 2) << 2;          // columns covered by whole 4-pixel (12-byte) groups
     // whole groups: the lane's dword of its 4-pixel group = row samples g4 .. g4 + 3 (row bytes g4 .. g4 + 3 of the tile)
     const bool grouped = !STREAK && (INTERIOR || ocx < full4);
     const uint32_t g4 = (uint32_t)((ocx >> 2) * 12 + (ocx & 3) * 4);
     const uint32_t k3 = grouped ? g4 : (uint32_t)(ocx * 3);      // the first sample this lane fetches
     const bool nlane = ocol && !(grouped && (ocx & 3) == 3);
-    u32x2 nrow = {0u, 0u};           // lane r < 8: the parked record of this wavefront's row r
-    if (tiled) nrow = *(const u32x2 *)(lnrow + 2 * (wave + NWAVES * (lane & 7)));
+    // INTERIOR: every lane fetches, with no exec mask and nothing to zero first.  A lane that adds no noise (a halo column, the
+    // fourth lane of a group) takes the address of output column 0, which a lane beside it fetches anyway: inside the row's
+    // slot or plane row whatever the pitch and wherever the allocation ends.
+    constexpr bool every_lane = INTERIOR;
+    const uint32_t k3n = (every_lane && !nlane) ? 0u : k3;
+    const uint32_t k3b = k3n << 1;
+    // The row's first sample is a SCALAR 64-bit base -- the slot offset of the row record, or (y0 + cy) * nstride + 3 x0 of a
+    // plane, stepped from row to row and chosen by a scalar select --; the lane adds its 32-bit byte offset, as the store to
+    // dst does: two v_readlane per row and the load.
+    long long prow = (long long)(y0 + wave) * (long long)nstride + (long long)x0 * 3;
+    const long long pstep = (long long)NWAVES * (long long)nstride;
+    if (noise) {
 #pragma unroll
-    for (int i = 0; i < ROWS_PER_WAVE; i++) {
-        nzA[i] = 0; nzB[i] = 0;
-        const int cy = wave + NWAVES * i;
-        if (noise && nlane && cy < th) {
-            const int16_t VKX_GLOBAL *np_;
-            if (tiled) {
-                // (the row's base is a scalar: the loads take it as their SGPR base, the lane's sample offset as the offset)
-                const int16_t VKX_GLOBAL *rowp = noise + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)nrow.x, i);
-                const uint32_t sd = (uint32_t)__builtin_amdgcn_readlane((int)nrow.y, i);
-                uint32_t off = k3;
-                if ((sd & 0xffffu) < 3u * W) {       // the row runs into the next generator tile (6 % of the rows)
-                    asm volatile("" ::: "memory");   // (a real branch: as a select the common rows would pay for the rare ones)
-                    // a fetch that begins before the boundary stays in this slot: it ends at most three samples past it, and a
-                    // slot ends with the first three samples of its successor (k_np_tiles_finish)
-                    off += k3 >= (sd & 0xffffu) ? (uint32_t)((int)sd >> 16) : 0u;
-                }
-                np_ = rowp + off;
-            } else {
-                np_ = noise + (ptrdiff_t)(y0 + cy) * nstride + (ptrdiff_t)x0 * 3 + (ptrdiff_t)k3;
+        for (int i = 0; i < ROWS_PER_WAVE; i++) {
+            const int cy = wave + NWAVES * i;
+            const long long prow_i = prow;
+            prow += pstep;
+            if (!row_live(i, cy)) continue;      // uniform over the wavefront
+            const uint32_t rx = (uint32_t)__builtin_amdgcn_readlane((int)nrow.x, i);
+            const uint32_t sd = (uint32_t)__builtin_amdgcn_readlane((int)nrow.y, i) | never;
+            const gbytes_t rowb = nbase + 2 * (tiled ? (long long)rx : prow_i);
+            uint32_t off = k3b;                  // the lane's first sample, in bytes from the row's
+            if ((sd & 0xffffu) < 3u * W) {       // the row runs into the next generator tile (6 % of the rows)
+                asm volatile("" ::: "memory");   // (a real branch: as a select the common rows would pay for the rare ones)
+                // a fetch that begins before the boundary stays in this slot: it ends at most three samples past it, and a
+                // slot ends with the first three samples of its successor (k_np_tiles_finish)
+                off += k3n >= (sd & 0xffffu) ? (uint32_t)((int)sd >> 16) << 1 : 0u;
             }
-            if (grouped) {
-                const unsigned long long v = *(const u64_u1 VKX_GLOBAL *)np_;
-                nzA[i] = (uint32_t)v;
-                nzB[i] = (uint32_t)(v >> 32);
-            } else {
-                nzA[i] = *(const u32_u1 VKX_GLOBAL *)np_;
-                nzB[i] = *(const u16_u1 VKX_GLOBAL *)(np_ + 2);
+            // (ONE load for both kinds of row: with a load of its own in the branch, the wait of every row is a vmcnt(0))
+            const gbytes_t np_ = rowb + (size_t)off;
+            if (!every_lane) { nzA[i] = 0; nzB[i] = 0; }
+            if (every_lane || nlane) {
+                if (grouped) {
+                    const unsigned long long v = *(const u64_u1 VKX_GLOBAL *)np_;
+                    nzA[i] = (uint32_t)v;
+                    nzB[i] = (uint32_t)(v >> 32);
+                } else {
+                    nzA[i] = *(const u32_u1 VKX_GLOBAL *)np_;
+                    nzB[i] = *(const u16_u1 VKX_GLOBAL *)(np_ + 4);
+                }
             }
         }
     }
@@ -1013,8 +1041,6 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
         const uint32_t o0 = (q > 0 && 2 * q - 1 < K) ? kq[q > 0 ? 2 * q - 1 : 0] : 0u, o1 = 2 * q < K ? kq[2 * q < 2 * RMAX + 1 ? 2 * q : 0] : 0u;
         wpair[q] = (wave & 1) ? (o0 | (o1 << 16)) : (e0 | (e1 << 16));
     }
-    const bool hue_on = __builtin_amdgcn_readfirstlane(ite.hue_on) != 0;
-    const int hue_delta = __builtin_amdgcn_readfirstlane(ite.hue_delta);
     const int right4 = min(lane + 1, 63) << 2;       // ds_bpermute address of the right-hand neighbour
     const uint32_t dcol4 = (uint32_t)(x0 * 3) + g4;  // this lane's dword of a 4-pixel group
     const bool streak_on = STREAK && ite.streak_on != 0;
@@ -1032,7 +1058,7 @@ __device__ __forceinline__ void chain_tile(const ItemDev &it, const int tx, cons
 #pragma unroll
     for (int i = 0; i < ROWS_PER_WAVE; i++) {
         const int cy = wave + NWAVES * i;
-        if (cy >= th) continue;                 // uniform over the wavefront
+        if (!row_live(i, cy)) continue;         // uniform over the wavefront
         const int gy = y0 + cy;
         uint32_t P = epx;                       // the pixel as r | g << 8 | b << 16
         if constexpr (!EMPTY) {
