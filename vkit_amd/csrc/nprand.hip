@@ -33,6 +33,7 @@
 #include "np_ziggurat.h"
 #include "vkx_host_tables.h"
 
+#include <stddef.h>
 #include <string.h>
 #include <algorithm>
 
@@ -91,6 +92,9 @@ struct TilePlan {
 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// The wedge test's fi and the fast accept's c = -2^52 wi side by side: 16 bytes per layer, like the ki | wi table, so that one byte
+// offset addresses both tables
+struct FiC { double fi, c; };
 __device__ __forceinline__ u128 mk128(const uint64_t *w) { return ((u128)w[1] << 64) | (u128)w[0]; }
 
 __device__ __forceinline__ uint64_t pcg_out(u128 s)
@@ -105,7 +109,8 @@ __device__ __forceinline__ uint64_t pcg_out(u128 s)
 // wants 64-bit operands in even-aligned register pairs, so every "high half of a product, zero extended" costs a move).  Here by
 // columns: the products of limb columns 0, 1 and 2 as three kinds of 64-bit accumulators that cannot overflow (a 32 x 32 product
 // plus two 32-bit addends fits 64 bits) or may wrap (column 2: bits 128 and up are dropped anyway), the four products of column 3
-// as a multiply-add chain of which the low word counts, and ONE carry chain over 32-bit halves, which need no alignment: 16.
+// as two multiply-add chains of which the low words count, and two carry chains of three over 32-bit halves, which need no alignment,
+// one after the other: 10 multiply-adds + 6 adds = 16.
 struct LcgStride {
     uint32_t a0, a1, a2, a3;      // multiplier limbs
     uint64_t c0, c1, c23;         // addend: limb 0, limb 1 (zero extended), limbs 2-3
@@ -139,18 +144,22 @@ __device__ __forceinline__ u128 lcg_step(u128 s, const LcgStride &k)
     uint64_t F = (uint64_t)k.a0 * s2 + k.c23;                 // bits 64 .. 127
     F += (uint64_t)k.a1 * s1;
     F += (uint64_t)k.a2 * s0;
-    uint64_t G = mul_u64_u32_v(k.a0, s3);                     // bits 96 .. 127: the low word
+    // column 3 (bits 96 .. 127: the low words) as two chains of two: each feeds one add of the top limb, which then adds no bare carry
+    uint64_t G = mul_u64_u32_v(k.a0, s3), H = mul_u64_u32_v(k.a2, s1);
     G = mad_u64_u32_v(k.a1, s2, G);
-    G = mad_u64_u32_v(k.a2, s1, G);
-    G = mad_u64_u32_v(k.a3, s0, G);
-    unsigned ca, cb, cc, cd;
-    const uint32_t t = __builtin_addc((uint32_t)(E >> 32), (uint32_t)O1, 0u, &ca);
-    const uint32_t r1 = __builtin_addc(t, (uint32_t)O2, 0u, &cb);
+    H = mad_u64_u32_v(k.a3, s0, H);
+    // limbs 1 - 3 as two sums of 96 bits: [F.hi : F.lo : E.hi] + [G : O1.hi : O1.lo], then + [H : O2.hi : O2.lo]
+    unsigned ca, cb, cc, cd, ce;
+    uint32_t t = __builtin_addc((uint32_t)(E >> 32), (uint32_t)O1, 0u, &ca);
     const uint32_t u = __builtin_addc((uint32_t)F, (uint32_t)(O1 >> 32), ca, &cc);
+    uint32_t w = __builtin_addc((uint32_t)(F >> 32), (uint32_t)G, cc, &ce);
+    // the first chain ends before the second begins (an empty statement that only orders the two: no instruction, no carry passes through
+    // it): interleaved they need two live carries, and the compiler then makes a 0 / 1 value of one (v_cndmask) and adds it with an
+    // instruction of its own
+    asm("" : "+v"(t), "+v"(w));
+    const uint32_t r1 = __builtin_addc(t, (uint32_t)O2, 0u, &cb);
     const uint32_t r2 = __builtin_addc(u, (uint32_t)(O2 >> 32), cb, &cd);
-    unsigned ce;
-    const uint32_t w = __builtin_addc((uint32_t)(F >> 32), (uint32_t)G, cc, &ce);
-    const uint32_t r3 = __builtin_addc(w, 0u, cd, &ce);
+    const uint32_t r3 = __builtin_addc(w, (uint32_t)H, cd, &ce);
     return ((u128)r3 << 96) | ((u128)r2 << 64) | ((u128)r1 << 32) | (uint32_t)E;
 }
 
@@ -356,7 +365,7 @@ __device__ __forceinline__ uint32_t compact_tile_lds(int16_t *flat, uint64_t m)
 }
 
 template <class Emit, int MODE>
-__device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 *__restrict__ zig /* LDS: ki | wi */, const double *__restrict__ fi /* LDS */,
+__device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 *__restrict__ zig /* LDS: ki | wi */, const FiC *__restrict__ fic /* LDS: fi | -2^52 wi */,
                           WaveWork<typename Emit::Store, MODE == kEmit || MODE == kCompact> &ws, u128 &s, u128 &s2, uint32_t c_in, long long prefix,
                           long long draw_base, typename Emit::Store VKX_GLOBAL *rec_val, uint64_t VKX_GLOBAL *rec_mask, void *emit_dst,
                           uint32_t &count_out, uint32_t &carry_out, uint64_t &start0, uint64_t &emit0, bool &has_tail, uint32_t &flags,
@@ -376,33 +385,44 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
     // two rounds per iteration from two independent generator states (draws 64 r + l and 64 (r + 1) + l, both striding
     // 128): both table look-ups are issued first and the two stride steps run while they are in flight, so that the LDS latency of
     // the chain state -> draw -> table -> compare is covered by the wavefront's own multiplies instead of by other wavefronts
-    // the fields phase 1 needs, on 32-bit words: idx = bits 0-7, the sign = bit 8, rabs = bits 9-60 of the rotated XSL-RR word
+    // the fields phase 1 needs, on 32-bit words.  The XSL-RR word u = rotr64(x, r) holds idx in bits 0-7, the sign in bit 8 and rabs in
+    // bits 9-60; the draw is rotated ONCE, by r + 9 (the 64-bit shifts take their amounts, r + 9 and 55 - r, modulo 64): rabs then sits in
+    // bits 0-51 -- its low word is the low word of the float64 2^52 + rabs as it stands --, idx in bits 23-30 of the high word and the sign
+    // in its bit 31, where the sign v_bitop3 takes it from
     struct Draw {
-        uint32_t lo, dlo, dhi;   // low word of the draw; 2^52 + rabs as float64 bits
+        uint32_t hi, dlo, dhi;   // high word of rotr64(x, r + 9); 2^52 + rabs as float64 bits
         u32x4 e;                 // ki | 2^52 (as dlo, dhi), wi: one 16-byte LDS read
+        double c;                // -2^52 wi: 8 bytes from the same offset of the fi | c table
     };
     // the constants of the field extraction and of the sign, held in VGPRs: v_bitop3_b32 issues at about half the cycles of a VOP3
     // when all three operands are VGPRs (4.46 with an SGPR constant, 2.46 without: profiles/np_instruction_rates.md)
     uint32_t k_m20 = 0x000fffffu, k_exp = 0x43300000u, k_sgn = 0x80000000u;
     asm volatile("" : "+v"(k_m20), "+v"(k_exp), "+v"(k_sgn));
     auto lookup = [&](const u128 &st) {
-        const uint64_t u = pcg_out(st);
         Draw d;
-        d.lo = (uint32_t)u;
-        d.e = ((const u32x4 *)zig)[d.lo & 0xff];
-        d.dlo = __builtin_amdgcn_alignbit((uint32_t)(u >> 32), d.lo, 9);
-        d.dhi = __builtin_amdgcn_bitop3_b32((uint32_t)(u >> 41), k_m20, k_exp, 0xea /* (a & b) | c */);
+        const uint64_t hi = (uint64_t)(st >> 64), x = hi ^ (uint64_t)st;
+        const uint32_t r = (uint32_t)(hi >> 58);
+        const uint64_t v = (x >> ((r + 9) & 63)) | (x << ((55 - r) & 63));
+        d.hi = (uint32_t)(v >> 32);
+        d.dlo = (uint32_t)v;
+        d.dhi = __builtin_amdgcn_bitop3_b32(d.hi, k_m20, k_exp, 0xea /* (a & b) | c */);
+        const uint32_t off = (d.hi >> 19) & 0xff0u;       // 16 idx
+        d.e = *(const u32x4 *)((const char *)zig + off);
+        if (MODE != kCount) d.c = *(const double *)((const char *)fic + off + offsetof(FiC, c));
         return d;
     };
     // what draw `lane` of round r would emit as a fast accept; the event push of the draws that are not one
     auto finish = [&](int r, const u128 &st, const Draw &d) -> typename Emit::Val {
         typename Emit::Val v = 0;
         if (MODE != kCount) {
-            // x = rabs * wi, the sign (bit 8 of the draw, rotated to bit 31) or-ed into wi: rabs < 2^52 converts exactly through
-            // the exponent trick and the product of a signed factor is the signed product
-            const uint32_t wsgn = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_alignbit(d.lo, d.lo, 9), k_sgn, d.e[3], 0xea);
-            const double wi = __longlong_as_double(((long long)wsgn << 32) | d.e[2]);
-            const double x = (__longlong_as_double((long long)(((uint64_t)d.dhi << 32) | d.dlo)) - 4503599627370496.0) * wi;
+            // x = +-(rabs * wi) as ONE fma: D = 2^52 + rabs holds rabs < 2^52 exactly (the exponent trick), c = -2^52 wi is exact (a power
+            // of two times a normal double), so D wi + c is rabs wi exactly and rounds once, as the product (D - 2^52) * wi does; the sign goes
+            // onto the result (in place, into the high word of the fma's own register pair): round-to-nearest is symmetric, so
+            // -(rabs * wi) is the rabs * (-wi) numpy forms
+            const double wi = __longlong_as_double((long long)(((uint64_t)d.e[3] << 32) | d.e[2]));
+            const uint64_t xa = (uint64_t)__double_as_longlong(__builtin_fma(__longlong_as_double((long long)(((uint64_t)d.dhi << 32) | d.dlo)), wi, d.c));
+            const uint32_t xs = __builtin_amdgcn_bitop3_b32(d.hi, k_sgn, (uint32_t)(xa >> 32), 0xea);
+            const double x = __longlong_as_double((long long)(((uint64_t)xs << 32) | (uint32_t)xa));
             v = Emit::make(job, x, false, flags);
             if (MODE == kRecord) rec_val[64 * r + lane] = (typename Emit::Store)v;
             else if (MODE == kEmit) ws.val[r][lane] = (typename Emit::Store)v;
@@ -469,7 +489,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                            __longlong_as_double(((long long)zig[idx].w << 32) | zig[idx].z);
                 if (u & 0x100) x = -x;
                 const double un = u2dbl(pcg_out(PCG_MULT * se + inc));
-                const double f1 = fi[idx], f0 = fi[idx - 1];
+                const double f1 = fic[idx].fi, f0 = fic[idx - 1].fi;
                 const double lhs = (f0 - f1) * un + f1;
                 const double t = -0.5 * x;
                 const double y = t * x;                       // in [-6.7, 0]
@@ -692,13 +712,15 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
     carry_out = carry;
 }
 
-__device__ __forceinline__ void load_tables(uint4 *zig, double *fi, const NpTabs *__restrict__ tabs)
+__device__ __forceinline__ void load_tables(uint4 *zig, FiC *fic, const NpTabs *__restrict__ tabs)
 {
     for (int i = threadIdx.x; i < 256; i += blockDim.x) {
         const uint64_t k = tabs->ki[i], w = tabs->wi[i];
         // ki with the exponent of 2^52 (ki < 2^52): the walk compares it with 2^52 + rabs, the float64 it builds anyway
         zig[i] = make_uint4((uint32_t)k, (uint32_t)(k >> 32) | 0x43300000u, (uint32_t)w, (uint32_t)(w >> 32));
-        fi[i] = __longlong_as_double((long long)tabs->fi[i]);
+        fic[i].fi = __longlong_as_double((long long)tabs->fi[i]);
+        // exact: a power-of-two scaling of a normal double (wi > 2^-80)
+        fic[i].c = -4503599627370496.0 * __longlong_as_double((long long)w);
     }
     __syncthreads();
 }
@@ -776,9 +798,9 @@ __global__ void __launch_bounds__(256) k_np_draw(const NpJob *__restrict__ jobs,
                                                  vkx_np_result *__restrict__ results, const NpTabs *__restrict__ tabs)
 {
     __shared__ uint4 zig[256];
-    __shared__ double fi[256];
+    __shared__ FiC fic[256];
     __shared__ WaveWork<typename Emit::Store, false> work[4];
-    load_tables(zig, fi, tabs);
+    load_tables(zig, fic, tabs);
     const JumpTabs &g_jump = tabs->jump;
     const long long n_waves = (long long)gridDim.x * 4;
     for (long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); tile < total_tiles; tile += n_waves) {
@@ -789,7 +811,7 @@ __global__ void __launch_bounds__(256) k_np_draw(const NpJob *__restrict__ jobs,
         bool has_tail;
         u128 s, s2;
         tile_lane_states(g_jump, job, mk128(&states[2 * tile]), s, s2);
-        walk_tile<Emit, kRecord>(job, g_jump, zig, fi, work[threadIdx.x >> 6], s, s2, 0u, 0, 0,
+        walk_tile<Emit, kRecord>(job, g_jump, zig, fic, work[threadIdx.x >> 6], s, s2, 0u, 0, 0,
                                  (typename Emit::Store VKX_GLOBAL *)(rec_val + tile * kTile), (uint64_t VKX_GLOBAL *)(rec_mask + tile * kRounds),
                                  nullptr, count, carry, start0, emit0, has_tail, flags, nullptr);
         if (__lane_id() == 0) {
@@ -804,7 +826,7 @@ __global__ void __launch_bounds__(256) k_np_draw(const NpJob *__restrict__ jobs,
 // The draw pass of the int16 kinds: the same walk, but a tile's samples leave squeezed together (kCompact) for the tile's slot of
 // kSlot elements -- the placement pass that used to read 2 bytes per RAW DRAW plus the emit masks, rank the samples and
 // scatter them is gone: what follows only copies (k_np_apply), or nothing follows at all (VKX_NP_NORMAL_TILES: the chain
-// kernel reads the slots).  kDrawWaves wavefronts share the ziggurat tables: 8 x 9.0 KB + 6 KB per workgroup, two workgroups
+// kernel reads the slots).  kDrawWaves wavefronts share the ziggurat tables: 8 x 9.0 KB + 8 KB = 81 920 B per workgroup, two workgroups
 // (16 wavefronts at 112 VGPRs) per CU.
 constexpr int kSlot = kTile + 16;        // elements per slot: the tile's samples, three lent by the next tile, 16-byte group rounding
 constexpr int kLent = 3;                 // a reader's 4-sample fetch that begins in a tile ends at most three samples into the next
@@ -822,14 +844,14 @@ __global__ void __launch_bounds__(64 * kDrawWaves) k_np_draw_compact(const NpJob
     // above the 64 KB a ds_read offset field reaches, it took one more instruction per round)
     struct Lds {
         uint4 zig[256];
-        double fi[256];
+        FiC fic[256];
         WaveWork<int16_t, true> work[kDrawWaves];
     };
     __shared__ Lds lds;
     uint4 *zig = lds.zig;
-    double *fi = lds.fi;
+    FiC *fic = lds.fic;
     WaveWork<int16_t, true> *work = lds.work;
-    load_tables(zig, fi, tabs);
+    load_tables(zig, fic, tabs);
     const JumpTabs &g_jump = tabs->jump;
     // a wavefront walks a run of consecutive tiles: the walk leaves the lane's states at the next tile's first two rounds, so the
     // job search and the start states (two full 128-bit products and a stride step per lane) are paid once per run and job, not
@@ -850,7 +872,7 @@ __global__ void __launch_bounds__(64 * kDrawWaves) k_np_draw_compact(const NpJob
         uint32_t count, carry, flags = 0;
         uint64_t start0, emit0;
         bool has_tail;
-        walk_tile<Emit, kCompact>(job, g_jump, zig, fi, work[threadIdx.x >> 6], s, s2, 0u, 0, 0,
+        walk_tile<Emit, kCompact>(job, g_jump, zig, fic, work[threadIdx.x >> 6], s, s2, 0u, 0, 0,
                                   (int16_t VKX_GLOBAL *)(job.rec + (tile - job.tile_base) * kSlot), nullptr, nullptr,
                                   count, carry, start0, emit0, has_tail, flags, nullptr);
         if (__lane_id() == 0) {
@@ -868,7 +890,7 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
                                                      vkx_np_result *__restrict__ results, const NpTabs *__restrict__ tabs)
 {
     __shared__ uint4 zig[256];
-    __shared__ double fi[256];
+    __shared__ FiC fic[256];
     __shared__ WaveWork<int16_t, false> work[1];
     __shared__ unsigned long long part[1024];
     __shared__ uint32_t n_irregular;
@@ -880,7 +902,7 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
     const uint64_t *st = states + 2 * job.tile_base;
     const int words = (T + 63) >> 6;
     if (threadIdx.x == 0) n_irregular = 0;
-    load_tables(zig, fi, tabs);
+    load_tables(zig, fic, tabs);
     const JumpTabs &g_jump = tabs->jump;
     // phase A: every tile takes its predecessor's speculative carry-out
     for (int w = threadIdx.x >> 6; w < words; w += 16) {
@@ -927,7 +949,7 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
                     bool ht;
                     u128 s, s2;
                     tile_lane_states(g_jump, job, mk128(&st[2 * j]), s, s2);
-                    walk_tile<EmitNone, kCount>(job, g_jump, zig, fi, work[0], s, s2, c, 0, 0, nullptr, nullptr, nullptr, count, out,
+                    walk_tile<EmitNone, kCount>(job, g_jump, zig, fic, work[0], s, s2, c, 0, 0, nullptr, nullptr, nullptr, count, out,
                                                 s0, e0, ht, flags, nullptr);
                     simulated = true;
                 }
@@ -1328,9 +1350,9 @@ __global__ void __launch_bounds__(64) k_np_place_walk(const NpJob *__restrict__ 
                                                        const NpTabs *__restrict__ tabs)
 {
     __shared__ uint4 zig[256];
-    __shared__ double fi[256];
+    __shared__ FiC fic[256];
     __shared__ __attribute__((aligned(16))) WaveWork<typename Emit::Store, true> work[1];
-    load_tables(zig, fi, tabs);
+    load_tables(zig, fic, tabs);
     const JumpTabs &g_jump = tabs->jump;
     const int lane = __lane_id();
     const long long n_waves = (long long)gridDim.x;
@@ -1359,7 +1381,7 @@ __global__ void __launch_bounds__(64) k_np_place_walk(const NpJob *__restrict__ 
             if (TILES) dst = (void *)((intptr_t)(job.rec + (tile - job.tile_base) * kSlot) - 2 * (intptr_t)p.prefix);
             u128 s, s2;
             tile_lane_states(g_jump, job, mk128(&states[2 * tile]), s, s2);
-            walk_tile<Emit, kEmit>(job, g_jump, zig, fi, work[0], s, s2, p.c_in & ~kIrregular,
+            walk_tile<Emit, kEmit>(job, g_jump, zig, fic, work[0], s, s2, p.c_in & ~kIrregular,
                                    (long long)p.prefix, (tile - job.tile_base) * kTile, nullptr, nullptr, dst, count, carry, start0, emit0, ht,
                                    flags, &results[j].draws);
             if (flags) atomicOr(&results[j].flags, flags);
