@@ -484,24 +484,31 @@ def test_throughput_noise_plane_matches_its_definition():
 
 
 def test_dense_and_pitched_planes_agree():
-    """The element-wise and RGB pixel kernels have two bodies: 16 bytes (4 pixels) per lane on dense, aligned planes, one
-    byte (pixel) per lane on any pitch.  Both must produce the oracle's bytes: every entry point is run on a dense plane, on
-    a padded one (odd pitch: unaligned rows) and, where the operator allows it, in place."""
+    """The element-wise and RGB pixel kernels have two bodies that share each operator's arithmetic: 16 bytes (4 pixels) per
+    lane on dense, aligned planes, one byte (pixel) per lane on any pitch.  Every entry point must produce the expected bytes
+    -- the oracle's, or plain numpy for the table lookup -- on a dense plane, on a padded one (odd pitch: unaligned rows),
+    on a dense one whose base pointers are one byte off (the alignment half of the choice) and, where the operator allows
+    it, in place; and it must write nothing outside the plane."""
     import ctypes
     from vkit_amd import _native as N
     ctx, lib = N.default_ctx(), N.lib()
     rng = default_rng(77)
 
-    def run(call, src, cn, pitch_pad, extra=None, inplace=False):
-        """call(src_ptr, src_pitch, dst_ptr, dst_pitch, extra_ptr, extra_pitch_el) on device copies; returns the result"""
+    def run(call, src, cn, pitch_pad, extra=None, inplace=False, offset=0):
+        """call(src_ptr, src_pitch, dst_ptr, dst_pitch, extra_ptr, extra_pitch_el) on device copies; returns the result.
+        The planes start `offset` bytes into their buffers and are followed by 16 more bytes."""
         h, w = src.shape[:2]
         row = w * cn
         pitch = row + pitch_pad
-        host = np.zeros((h, pitch), np.uint8)
-        host[:, :row] = src.reshape(h, row)
-        d_src, d_dst = ctx.malloc(host.nbytes + 64), ctx.malloc(host.nbytes + 64)
+        total = offset + h * pitch + 16
+
+        def plane(buf):
+            return buf[offset:offset + h * pitch].reshape(h, pitch)
+        host = np.zeros(total, np.uint8)
+        plane(host)[:, :row] = src.reshape(h, row)
+        d_src, d_dst = ctx.malloc(total + 64), ctx.malloc(total + 64)
         ctx.upload(d_src, host)
-        ctx.upload(d_dst, np.full((h, pitch), 0xA5, np.uint8))
+        ctx.upload(d_dst, np.full(total, 0xA5, np.uint8))
         d_extra, extra_pitch = 0, 0
         if extra is not None:
             per = extra.size // h
@@ -510,16 +517,26 @@ def test_dense_and_pitched_planes_agree():
             e[:, :per] = extra.reshape(h, per)
             d_extra = ctx.malloc(e.nbytes + 64)
             ctx.upload(d_extra, e)
-        N.check(call(d_src, pitch, d_src if inplace else d_dst, pitch, d_extra, extra_pitch))
-        out = np.zeros((h, pitch), np.uint8)
-        ctx.download(d_src if inplace else d_dst, out)
+        d_out = d_src if inplace else d_dst
+        N.check(call(d_src + offset, pitch, d_out + offset, pitch, d_extra, extra_pitch))
+        out = np.zeros(total, np.uint8)
+        ctx.download(d_out, out)
         ctx.sync()
         for p in (d_src, d_dst, d_extra):
             if p:
                 ctx.free(p)
         if not inplace:
-            assert (out[:, row:] == 0xA5).all()          # nothing written into the padding
-        return out[:, :row].reshape(src.shape)
+            outside = np.ones(total, bool)
+            plane(outside)[:, :row] = False
+            assert (out[outside] == 0xA5).all()          # nothing written before, after or into the padding of the plane
+        return plane(out)[:, :row].reshape(src.shape)
+
+    def lut_numpy(mat, cn, lut, chmask):
+        want = mat.reshape(mat.shape[0], mat.shape[1], cn).copy()
+        for c in range(cn):
+            if (chmask >> c) & 1:
+                want[..., c] = lut[c][want[..., c]]
+        return want.reshape(mat.shape)
 
     for (h, w) in ((37, 53), (64, 64), (1, 7), (5, 1), (130, 257)):
         rgb = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
@@ -532,38 +549,36 @@ def test_dense_and_pitched_planes_agree():
         for delta in (37, -200, 0):
             cases.append((f'color_shift {delta}', rgb, 3, None, O.color_shift_rgb(rgb, delta), True,
                           lambda s, sp, d, dp, e, ep, delta=delta: lib.vkx_color_shift_rgb_dev(ctx.handle, s, h, w, sp, delta, d, dp)))
-        cases.append(('rgb2hsv', rgb, 3, None, None, True,
+        cases.append(('rgb2hsv', rgb, 3, None, O.rgb2hsv_full(rgb), True,
                       lambda s, sp, d, dp, e, ep: lib.vkx_cvt_rgb_hsv_u8_dev(ctx.handle, s, h, w, sp, 1, d, dp)))
-        cases.append(('hsv2rgb', rgb, 3, None, None, True,
+        cases.append(('hsv2rgb', rgb, 3, None, O.hsv2rgb_full(rgb), True,
                       lambda s, sp, d, dp, e, ep: lib.vkx_cvt_rgb_hsv_u8_dev(ctx.handle, s, h, w, sp, 0, d, dp)))
         cases.append(('brightness', rgb, 3, None, O.brightness_shift_rgb(rgb, 20), True,
                       lambda s, sp, d, dp, e, ep: lib.vkx_brightness_shift_rgb_dev(ctx.handle, s, h, w, sp, 20, d, dp)))
         cases.append(('color_balance', rgb, 3, None, O.color_balance_rgb(rgb, 0.4), True,
                       lambda s, sp, d, dp, e, ep: lib.vkx_color_balance_rgb_dev(ctx.handle, s, h, w, sp, ctypes.c_double(0.4), d, dp)))
         for mat, cn in ((rgb, 3), (gray, 1), (rgba, 4)):
-            cases.append((f'mean_shift cn{cn}', mat, cn, None, None, True,
+            cases.append((f'mean_shift cn{cn}', mat, cn, None, O.mean_shift(mat, 40, threshold=128, channels=[0, 2]), True,
                           lambda s, sp, d, dp, e, ep, cn=cn: lib.vkx_mean_shift_u8_dev(ctx.handle, s, h, w, cn, sp, 40, 1, 128, 0, 0b101, d, dp)))
-            cases.append((f'mean_shift cycle cn{cn}', mat, cn, None, None, True,
+            cases.append((f'mean_shift cycle cn{cn}', mat, cn, None, O.mean_shift(mat, -77, cycle=True), True,
                           lambda s, sp, d, dp, e, ep, cn=cn: lib.vkx_mean_shift_u8_dev(ctx.handle, s, h, w, cn, sp, -77, 0, 0, 1, 0, d, dp)))
-            cases.append((f'complement cn{cn}', mat, cn, None, None, True,
+            cases.append((f'complement cn{cn}', mat, cn, None,
+                          O.complement(mat, threshold=100, enable_threshold_lte=True, channels=[0, 1]), True,
                           lambda s, sp, d, dp, e, ep, cn=cn: lib.vkx_pointwise_u8_dev(ctx.handle, s, h, w, cn, sp, 0, 100, 1, 0b011, d, dp)))
-            cases.append((f'posterize cn{cn}', mat, cn, None, None, True,
+            cases.append((f'posterize cn{cn}', mat, cn, None, O.posterization(mat, 5), True,
                           lambda s, sp, d, dp, e, ep, cn=cn: lib.vkx_pointwise_u8_dev(ctx.handle, s, h, w, cn, sp, 1, 5, 0, 0, d, dp)))
-            cases.append((f'impulse cn{cn}', mat, cn, sel, None, True,
+            cases.append((f'impulse cn{cn}', mat, cn, sel, O.impulse_noise(mat, sel), True,
                           lambda s, sp, d, dp, e, ep, cn=cn: lib.vkx_impulse_noise_u8_dev(ctx.handle, s, h, w, cn, sp, e, ep, d, dp)))
             lut = rng.integers(0, 256, (cn, 256), dtype=np.uint8)
-            cases.append((f'lut cn{cn}', mat, cn, None, None, True,
+            cases.append((f'lut cn{cn}', mat, cn, None, lut_numpy(mat, cn, lut, 0b110), True,
                           lambda s, sp, d, dp, e, ep, cn=cn, lut=lut: lib.vkx_apply_lut_u8_dev(ctx.handle, s, h, w, cn, sp, lut.ctypes.data, 0b110, d, dp)))
         cases.append(('add_noise', rgb, 3, noise, O.add_noise_i16(rgb, noise), True,
                       lambda s, sp, d, dp, e, ep: lib.vkx_add_noise_i16_dev(ctx.handle, s, h, w, 3, sp, e, ep, d, dp)))
         for name, mat, cn, extra, want, can_inplace, call in cases:
-            dense = run(call, mat, cn, 0, extra)
-            pitched = run(call, mat, cn, 5, extra)
-            np.testing.assert_array_equal(dense, pitched, err_msg=f'{name} {(h, w)}')
-            if want is not None:
-                np.testing.assert_array_equal(dense, want, err_msg=f'{name} {(h, w)} vs oracle')
+            for layout, kw in (('dense', dict(pitch_pad=0)), ('pitched', dict(pitch_pad=5)), ('dense, base + 1', dict(pitch_pad=0, offset=1))):
+                np.testing.assert_array_equal(run(call, mat, cn, extra=extra, **kw), want, err_msg=f'{name} {(h, w)} {layout}')
             if can_inplace:
-                np.testing.assert_array_equal(run(call, mat, cn, 0, extra, inplace=True), dense, err_msg=f'{name} in place')
+                np.testing.assert_array_equal(run(call, mat, cn, 0, extra, inplace=True), want, err_msg=f'{name} {(h, w)} in place')
 
 
 def test_histogram_dense_and_pitched():

@@ -4,6 +4,7 @@
 #include "vkx_color.h"
 
 #include <algorithm>
+#include <initializer_list>
 
 #include <float.h>
 
@@ -293,42 +294,40 @@ struct HsvTables {
     int hdiv[256];
 };
 
-__device__ __forceinline__ void rgb2hsv_px(const int *__restrict__ sdiv, const int *__restrict__ hdiv, int r, int g, int b,
-                                           int &H, int &S, int &V)
-{
-    vkd::rgb2hsv_full(sdiv, hdiv, r, g, b, H, S, V);
-}
+__device__ __forceinline__ uint32_t pack3(int a, int b, int c) { return (uint32_t)a | ((uint32_t)b << 8) | ((uint32_t)c << 16); }
 
-__device__ __forceinline__ void hsv2rgb_px(int H, int S, int V, int &r, int &g, int &b) { vkd::hsv2rgb_full(H, S, V, r, g, b); }
-
-// mode 0: color_shift (RGB -> HSV, H += delta mod 256, HSV -> RGB); 1: RGB -> HSV; 2: HSV -> RGB
+// mode 0: color_shift (RGB -> HSV, H += delta mod 256, HSV -> RGB: the arithmetic of the fused chain kernel,
+// vkd::hue_shift_packed); 1: RGB -> HSV; 2: HSV -> RGB.  The division tables and the hue sector selectors sit in LDS.
 template <int MODE>
-__global__ void __launch_bounds__(256) k_hsv(const uint8_t *__restrict__ src, int h, int w, ptrdiff_t sstride,
-                                             uint8_t *__restrict__ dst, ptrdiff_t dstride, int delta,
-                                             const HsvTables *__restrict__ T)
+struct HsvOp {
+    const int *sdiv, *hdiv;
+    const uint32_t *sel;
+    int delta;
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b, uint32_t c) const
+    {
+        if (MODE == 0) return vkd::hue_shift_packed(sdiv, hdiv, sel, delta, (int)a, (int)b, (int)c);
+        int x, y, z;
+        if (MODE == 1) vkd::rgb2hsv_full(sdiv, hdiv, (int)a, (int)b, (int)c, x, y, z);
+        else vkd::hsv2rgb_full((int)a, (int)b, (int)c, x, y, z);
+        return pack3(x, y, z);
+    }
+};
+
+// The operator of a workgroup of 256 lanes (`tid`: the lane's number in it), its tables staged from device memory.  Every lane of
+// the workgroup calls this: there is a barrier inside.  Read straight from device memory in the pitched body, the selectors
+// cost the colour shift a ninth memory instruction per pixel and 14 % of its time (profiles/photo_shared_ops.md).
+template <int MODE>
+__device__ __forceinline__ HsvOp<MODE> hsv_op_staged(const HsvTables *__restrict__ T, unsigned tid, int delta)
 {
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= w || y >= h) return;
-    const uint8_t *s = src + (ptrdiff_t)y * sstride + (ptrdiff_t)x * 3;
-    uint8_t *d = dst + (ptrdiff_t)y * dstride + (ptrdiff_t)x * 3;
-    int a = s[0], b = s[1], c = s[2];
-    if (MODE == 0 || MODE == 1) {
-        int H, S, V;
-        rgb2hsv_px(T->sdiv, T->hdiv, a, b, c, H, S, V);
-        a = H; b = S; c = V;
+    __shared__ int lsdiv[256], lhdiv[256];
+    __shared__ uint32_t lsel[8];
+    if (MODE != 2) {
+        lsdiv[tid] = T->sdiv[tid];
+        lhdiv[tid] = T->hdiv[tid];
+        if (tid < 8) lsel[tid] = vkd::kHsvSelectors[tid];
+        __syncthreads();
     }
-    if (MODE == 0) {
-        int hh = (a + delta) % 256;
-        if (hh < 0) hh += 256;
-        a = hh;
-    }
-    if (MODE == 0 || MODE == 2) {
-        int r, g, bl;
-        hsv2rgb_px(a, b, c, r, g, bl);
-        a = r; b = g; c = bl;
-    }
-    d[0] = (uint8_t)a; d[1] = (uint8_t)b; d[2] = (uint8_t)c;
+    return HsvOp<MODE>{lsdiv, lhdiv, lsel, delta};
 }
 
 // RGB2HLS_f / HLS2RGB_f through the 8-bit wrappers (color_hsv.simd.hpp, scalar path), hrange 256, no FMA.
@@ -406,91 +405,83 @@ __device__ __forceinline__ void hls2rgb_px(int H, int L, int S, int &R, int &G, 
 // RGB2Gray<uchar>: 15-bit fixed point
 __device__ __forceinline__ int rgb2gray_px(int R, int G, int B) { return (R * 9798 + G * 19235 + B * 3735 + (1 << 14)) >> 15; }
 
+// uint8(clip(w0 * a + w1 * b, 0, 255)): float32 products rounded separately, clip, truncation (photometric/color.py:371-396)
+__device__ __forceinline__ uint8_t weighted_u8(float w0, float a, float w1, float b)
+{
+    const float t0 = w0 * a, t1 = w1 * b;
+    float v = t0 + t1;
+    v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+    return (uint8_t)v;
+}
+
 // mode 0: brightness_shift (RGB -> HLS, L = clip(L + delta), HLS -> RGB); 1: RGB -> HLS; 2: HLS -> RGB;
-//      3: RGB -> GRAY (1 channel out); 4: GRAY -> RGB; 5: color_balance (w0 * gray + w1 * px, clip, truncate)
+//      5: color_balance (w0 * gray + w1 * px, clip, truncate).  3, 4 and 6 .. 9 change the channel count: k_cvt_cn.
 template <int MODE>
-__global__ void __launch_bounds__(256) k_cvt(const uint8_t *__restrict__ src, int h, int w, ptrdiff_t sstride,
-                                             uint8_t *__restrict__ dst, ptrdiff_t dstride, int delta, float w0, float w1)
-{
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= w || y >= h) return;
-    constexpr int SCN = MODE == 4 ? 1 : 3, DCN = MODE == 3 ? 1 : 3;
-    const uint8_t *s = src + (ptrdiff_t)y * sstride + (ptrdiff_t)x * SCN;
-    uint8_t *d = dst + (ptrdiff_t)y * dstride + (ptrdiff_t)x * DCN;
-    if (MODE == 4) {
-        const uint8_t v = s[0];
-        d[0] = v; d[1] = v; d[2] = v;
-        return;
-    }
-    int a = s[0], b = s[1], c = s[2];
-    if (MODE == 3) {
-        d[0] = (uint8_t)rgb2gray_px(a, b, c);
-        return;
-    }
-    if (MODE == 5) {
-        const float gray = (float)rgb2gray_px(a, b, c);
-        const int in[3] = {a, b, c};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float t0 = w0 * gray, t1 = w1 * (float)in[k];
-            float v = t0 + t1;
-            v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
-            d[k] = (uint8_t)v;
+struct CvtOp {
+    int delta;
+    float w0, w1;
+    __device__ __forceinline__ uint32_t operator()(uint32_t ua, uint32_t ub, uint32_t uc) const
+    {
+        int a = (int)ua, b = (int)ub, c = (int)uc;
+        if (MODE == 5) {
+            const float gray = (float)rgb2gray_px(a, b, c);
+            return pack3(weighted_u8(w0, gray, w1, (float)a), weighted_u8(w0, gray, w1, (float)b), weighted_u8(w0, gray, w1, (float)c));
         }
-        return;
+        if (MODE == 0 || MODE == 1) {
+            int H, L, S;
+            rgb2hls_px(a, b, c, H, L, S);
+            a = H; b = L; c = S;
+        }
+        if (MODE == 0 && delta != 0) b = vkd::clamp_u8(b + delta);
+        if (MODE == 0 || MODE == 2) {
+            int R, G, B;
+            hls2rgb_px(a, b, c, R, G, B);
+            a = R; b = G; c = B;
+        }
+        return pack3(a, b, c);
     }
-    if (MODE == 0 || MODE == 1) {
-        int H, L, S;
-        rgb2hls_px(a, b, c, H, L, S);
-        a = H; b = L; c = S;
-    }
-    if (MODE == 0 && delta != 0) b = vkd::clamp_u8(b + delta);
-    if (MODE == 0 || MODE == 2) {
-        int R, G, B;
-        hls2rgb_px(a, b, c, R, G, B);
-        a = R; b = G; c = B;
-    }
-    d[0] = (uint8_t)a; d[1] = (uint8_t)b; d[2] = (uint8_t)c;
+};
+
+// The lane's element of a plane of `cols` x `rows` elements under the pitched launch (64 x 4 lanes per workgroup); false outside it.
+__device__ __forceinline__ bool lane_xy(int cols, int rows, int &x, int &y)
+{
+    x = blockIdx.x * 64 + threadIdx.x;
+    y = blockIdx.y * 4 + threadIdx.y;
+    return x < cols && y < rows;
 }
 
-// RGBA conversions of Image.to_target_mode_image (element/image.py:188-216): 6 RGBA -> RGB (alpha dropped), 7 RGB -> RGBA
-// (alpha 255), 8 GRAY -> RGBA, 9 RGBA -> GRAY (the RGB2Gray weights on the first three channels)
+// The conversions that change the channel count, pixel in, pixel out: 3 RGB -> GRAY (RGB2Gray weights), 4 GRAY -> RGB, and the
+// RGBA ones of Image.to_target_mode_image (element/image.py:188-216): 6 RGBA -> RGB (alpha dropped), 7 RGB -> RGBA (alpha 255),
+// 8 GRAY -> RGBA, 9 RGBA -> GRAY (the weights on the first three channels)
 template <int MODE>
-__global__ void __launch_bounds__(256) k_cvt_alpha(const uint8_t *__restrict__ src, int h, int w, ptrdiff_t sstride,
-                                                   uint8_t *__restrict__ dst, ptrdiff_t dstride)
+__global__ void __launch_bounds__(256) k_cvt_cn(const uint8_t *__restrict__ src, int h, int w, ptrdiff_t sstride,
+                                                uint8_t *__restrict__ dst, ptrdiff_t dstride)
 {
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= w || y >= h) return;
-    constexpr int SCN = MODE == 6 || MODE == 9 ? 4 : (MODE == 7 ? 3 : 1), DCN = MODE == 6 ? 3 : (MODE == 9 ? 1 : 4);
+    constexpr int SCN = MODE == 4 || MODE == 8 ? 1 : (MODE == 3 || MODE == 7 ? 3 : 4);
+    constexpr int DCN = MODE == 3 || MODE == 9 ? 1 : (MODE == 4 || MODE == 6 ? 3 : 4);
+    int x, y;
+    if (!lane_xy(w, h, x, y)) return;
     const uint8_t *s = src + (ptrdiff_t)y * sstride + (ptrdiff_t)x * SCN;
     uint8_t *d = dst + (ptrdiff_t)y * dstride + (ptrdiff_t)x * DCN;
-    if (MODE == 6) { d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; }
-    else if (MODE == 7) { d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = 255; }
-    else if (MODE == 8) { const uint8_t v = s[0]; d[0] = v; d[1] = v; d[2] = v; d[3] = 255; }
-    else d[0] = (uint8_t)rgb2gray_px(s[0], s[1], s[2]);
+    if (DCN == 1) {
+        d[0] = (uint8_t)rgb2gray_px(s[0], s[1], s[2]);
+        return;
+    }
+    const uint8_t r = s[0], g = s[SCN == 1 ? 0 : 1], b = s[SCN == 1 ? 0 : 2];
+    d[0] = r; d[1] = g; d[2] = b;
+    if (DCN == 4) d[3] = 255;
 }
 
-// uint8(clip(w0 * a + w1 * b, 0, 255)) on the channels of `chmask` (0 = all), b copied elsewhere: color_balance on any
-// image mode (photometric/color.py:371-396: float32 products rounded separately, clip, truncation)
+// weighted_u8(w0, a, w1, b) on the channels of `chmask` (0 = all), b copied elsewhere: color_balance on any image mode
 __global__ void __launch_bounds__(256) k_blend_u8(const uint8_t *__restrict__ a, ptrdiff_t astride, const uint8_t *__restrict__ b,
                                                   ptrdiff_t bstride, int h, int wc, int cn, float w0, float w1, unsigned chmask,
                                                   uint8_t *__restrict__ dst, ptrdiff_t dstride)
 {
-    const int xe = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (xe >= wc || y >= h) return;
-    const int c = xe % cn;
+    int xe, y;
+    if (!lane_xy(wc, h, xe, y)) return;
     const uint8_t vb = b[(ptrdiff_t)y * bstride + xe];
-    uint8_t out = vb;
-    if (chmask == 0 || ((chmask >> c) & 1u)) {
-        const float t0 = w0 * (float)a[(ptrdiff_t)y * astride + xe], t1 = w1 * (float)vb;
-        float v = t0 + t1;
-        v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
-        out = (uint8_t)v;
-    }
-    dst[(ptrdiff_t)y * dstride + xe] = out;
+    dst[(ptrdiff_t)y * dstride + xe] = (chmask == 0 || ((chmask >> (xe % cn)) & 1u))
+                                           ? weighted_u8(w0, (float)a[(ptrdiff_t)y * astride + xe], w1, (float)vb) : vb;
 }
 
 // uint8(clip((1 - m) * px + m * fog, 0, 255)) with a float32 weight plane m [h, w] shared by the cn channels and one
@@ -499,82 +490,146 @@ __global__ void __launch_bounds__(256) k_fog_f32(const uint8_t *__restrict__ src
                                                  ptrdiff_t mstride, int h, int w, int cn, float f0, float f1, float f2, float f3,
                                                  uint8_t *__restrict__ dst, ptrdiff_t dstride)
 {
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= w || y >= h) return;
+    int x, y;
+    if (!lane_xy(w, h, x, y)) return;
     const float mk = m[(ptrdiff_t)y * mstride + x], inv = 1.0f - mk;
     const float fog[4] = {f0, f1, f2, f3};
-    for (int c = 0; c < cn; c++) {
-        const float t0 = inv * (float)src[(ptrdiff_t)y * sstride + (ptrdiff_t)x * cn + c], t1 = mk * fog[c];
-        float v = t0 + t1;
-        v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
-        dst[(ptrdiff_t)y * dstride + (ptrdiff_t)x * cn + c] = (uint8_t)v;
+    for (int c = 0; c < cn; c++)
+        dst[(ptrdiff_t)y * dstride + (ptrdiff_t)x * cn + c] = weighted_u8(inv, (float)src[(ptrdiff_t)y * sstride + (ptrdiff_t)x * cn + c], mk, fog[c]);
+}
+
+// ---- element-wise operators ------------------------------------------------------------------------------------------
+// Each operator is stated once and run through two mappers (below): one byte or pixel per lane on any row pitch, 16 bytes or
+// 4 pixels per lane on a dense plane.  Byte operators map (value, channel, index within the lane's group) to the new value.
+struct MeanShiftOp {
+    int delta, has_thr, thr, cycle;
+    unsigned chmask;
+    __device__ __forceinline__ int operator()(int v, int c, int) const
+    {
+        if ((chmask == 0 || ((chmask >> c) & 1u)) && delta != 0) {
+            bool apply = true;
+            if (has_thr) apply = delta > 0 ? (v <= thr) : (thr <= v);
+            if (apply) v += delta;
+            v = cycle ? (v & 255) : vkd::clamp_u8(v);      // python's % 256 of a two's complement int is & 255
+        }
+        return v;
     }
+};
+
+// complement / posterization (photometric/color.py:299-357, 423-432)
+struct PointOp {
+    int op, p0, p1;
+    unsigned chmask;
+    __device__ __forceinline__ int operator()(int v, int c, int) const
+    {
+        const bool on = chmask == 0 || ((chmask >> c) & 1u);
+        if (op == VKX_POINT_COMPLEMENT) {
+            if (on && (p0 < 0 || (p1 ? v <= p0 : p0 <= v))) v = 255 - v;
+        } else if (on) {
+            v &= (0xFF >> p0) << p0;
+        }
+        return v;
+    }
+};
+
+// lut[c][v] on the selected channels (the per-value half of the two equalisations); `lut` wherever the kernel keeps it
+struct LutOp {
+    const uint8_t *lut; /* [cn][256] */
+    unsigned chmask;
+    __device__ __forceinline__ int operator()(int v, int c, int) const { return (chmask == 0 || ((chmask >> c) & 1u)) ? (int)lut[c * 256 + v] : v; }
+};
+
+// int16 arithmetic like the reference's (uint8 -> int16) + int16 sum: wraps at 16 bits, then saturates to uint8
+__device__ __forceinline__ int add_noise_px(int px, int16_t noise) { return vkd::clamp_u8((int16_t)((int16_t)px + noise)); }
+
+// impulse_noise (photometric/noise.py:125-150): per-PIXEL selector 0 keep / 1 salt (255) / 2 pepper (0)
+__device__ __forceinline__ uint32_t impulse_px(uint32_t sel, uint32_t px) { return sel == 1 ? 255u : (sel == 2 ? 0u : px); }
+
+// ---- the pitched mappers: any row pitch, one byte (one RGB pixel) per lane ------------------------------------------------
+template <class F>
+__device__ __forceinline__ void map_bytes_pitched(const uint8_t *__restrict__ src, ptrdiff_t sstride, uint8_t *__restrict__ dst,
+                                                  ptrdiff_t dstride, int h, int w, int cn, F f)
+{
+    int xe, y;                                   // xe: element index within the row
+    if (!lane_xy(w * cn, h, xe, y)) return;
+    dst[(ptrdiff_t)y * dstride + xe] = (uint8_t)f((int)src[(ptrdiff_t)y * sstride + xe], xe % cn, 0);
+}
+
+// f takes (r, g, b) and returns r | g << 8 | b << 16
+template <class F>
+__device__ __forceinline__ void map_rgb_pitched(const uint8_t *__restrict__ src, ptrdiff_t sstride, uint8_t *__restrict__ dst,
+                                                ptrdiff_t dstride, int h, int w, F f)
+{
+    int x, y;
+    if (!lane_xy(w, h, x, y)) return;
+    const uint8_t *s = src + (ptrdiff_t)y * sstride + (ptrdiff_t)x * 3;
+    uint8_t *d = dst + (ptrdiff_t)y * dstride + (ptrdiff_t)x * 3;
+    const uint32_t q = f(s[0], s[1], s[2]);
+    d[0] = (uint8_t)q; d[1] = (uint8_t)(q >> 8); d[2] = (uint8_t)(q >> 16);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_hsv(const uint8_t *__restrict__ src, int h, int w, ptrdiff_t sstride,
+                                             uint8_t *__restrict__ dst, ptrdiff_t dstride, int delta,
+                                             const HsvTables *__restrict__ T)
+{
+    map_rgb_pitched(src, sstride, dst, dstride, h, w, hsv_op_staged<MODE>(T, threadIdx.y * 64 + threadIdx.x, delta));
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_cvt(const uint8_t *__restrict__ src, int h, int w, ptrdiff_t sstride,
+                                             uint8_t *__restrict__ dst, ptrdiff_t dstride, int delta, float w0, float w1)
+{
+    map_rgb_pitched(src, sstride, dst, dstride, h, w, CvtOp<MODE>{delta, w0, w1});
 }
 
 __global__ void __launch_bounds__(256) k_mean_shift(const uint8_t *__restrict__ src, int h, int w, int cn, ptrdiff_t sstride,
                                                     uint8_t *__restrict__ dst, ptrdiff_t dstride, int delta, int has_thr,
                                                     int thr, int cycle, unsigned chmask)
 {
-    const int xe = blockIdx.x * 64 + threadIdx.x; // element index within the row
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (xe >= w * cn || y >= h) return;
+    map_bytes_pitched(src, sstride, dst, dstride, h, w, cn, MeanShiftOp{delta, has_thr, thr, cycle, chmask});
+}
+
+__global__ void __launch_bounds__(256) k_pointwise(const uint8_t *__restrict__ src, int h, int w, int cn, ptrdiff_t sstride,
+                                                   uint8_t *__restrict__ dst, ptrdiff_t dstride, int op, int p0, int p1,
+                                                   unsigned chmask)
+{
+    map_bytes_pitched(src, sstride, dst, dstride, h, w, cn, PointOp{op, p0, p1, chmask});
+}
+
+// channel_permutation: out[c] = in[perm[c]], 2 bits per channel.  It needs whole pixels: no dense body.
+__global__ void __launch_bounds__(256) k_permute(const uint8_t *__restrict__ src, int h, int w, int cn, ptrdiff_t sstride,
+                                                 uint8_t *__restrict__ dst, ptrdiff_t dstride, int perm)
+{
+    int xe, y;
+    if (!lane_xy(w * cn, h, xe, y)) return;
     const int c = xe % cn;
-    int v = src[(ptrdiff_t)y * sstride + xe];
-    if ((chmask == 0 || ((chmask >> c) & 1u)) && delta != 0) {
-        bool apply = true;
-        if (has_thr) apply = delta > 0 ? (v <= thr) : (thr <= v);
-        if (apply) v += delta;
-        if (cycle) { v %= 256; if (v < 0) v += 256; }
-        else v = vkd::clamp_u8(v);
-    }
-    dst[(ptrdiff_t)y * dstride + xe] = (uint8_t)v;
+    dst[(ptrdiff_t)y * dstride + xe] = src[(ptrdiff_t)y * sstride + xe - c + ((perm >> (2 * c)) & 3)];
+}
+
+__global__ void __launch_bounds__(256) k_apply_lut(const uint8_t *__restrict__ src, int h, int w, int cn, ptrdiff_t sstride,
+                                                   uint8_t *__restrict__ dst, ptrdiff_t dstride,
+                                                   const uint8_t *__restrict__ lut /* [cn][256] */, unsigned chmask)
+{
+    map_bytes_pitched(src, sstride, dst, dstride, h, w, cn, LutOp{lut, chmask});
 }
 
 __global__ void __launch_bounds__(256) k_add_noise(const uint8_t *__restrict__ src, int h, int wc, ptrdiff_t sstride,
                                                    const int16_t *__restrict__ noise, ptrdiff_t nstride,
                                                    uint8_t *__restrict__ dst, ptrdiff_t dstride)
 {
-    const int xe = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (xe >= wc || y >= h) return;
-    const int v = (int16_t)((int16_t)src[(ptrdiff_t)y * sstride + xe] + noise[(ptrdiff_t)y * nstride + xe]);
-    dst[(ptrdiff_t)y * dstride + xe] = (uint8_t)vkd::clamp_u8(v);
+    int xe, y;
+    if (!lane_xy(wc, h, xe, y)) return;
+    dst[(ptrdiff_t)y * dstride + xe] = (uint8_t)add_noise_px(src[(ptrdiff_t)y * sstride + xe], noise[(ptrdiff_t)y * nstride + xe]);
 }
 
-// complement / posterization / channel_permutation (photometric/color.py:299-357, 423-432): one value per lane.
-__global__ void __launch_bounds__(256) k_pointwise(const uint8_t *__restrict__ src, int h, int w, int cn, ptrdiff_t sstride,
-                                                   uint8_t *__restrict__ dst, ptrdiff_t dstride, int op, int p0, int p1,
-                                                   unsigned chmask)
-{
-    const int xe = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (xe >= w * cn || y >= h) return;
-    const int c = xe % cn;
-    const uint8_t *row = src + (ptrdiff_t)y * sstride;
-    int v = row[xe];
-    const bool on = chmask == 0 || ((chmask >> c) & 1u);
-    if (op == VKX_POINT_COMPLEMENT) {
-        if (on && (p0 < 0 || (p1 ? v <= p0 : p0 <= v))) v = 255 - v;
-    } else if (op == VKX_POINT_POSTERIZE) {
-        if (on) v &= (0xFF >> p0) << p0;
-    } else {                                     // VKX_POINT_PERMUTE: out[c] = in[perm[c]], 2 bits per channel
-        v = row[xe - c + ((p0 >> (2 * c)) & 3)];
-    }
-    dst[(ptrdiff_t)y * dstride + xe] = (uint8_t)v;
-}
-
-// impulse_noise (photometric/noise.py:125-150): per-PIXEL selector 0 keep / 1 salt (255) / 2 pepper (0).
 __global__ void __launch_bounds__(256) k_impulse_noise(const uint8_t *__restrict__ src, int h, int w, int cn, ptrdiff_t sstride,
                                                        const uint8_t *__restrict__ sel, ptrdiff_t sel_stride,
                                                        uint8_t *__restrict__ dst, ptrdiff_t dstride)
 {
-    const int xe = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (xe >= w * cn || y >= h) return;
-    const int m = sel[(ptrdiff_t)y * sel_stride + xe / cn];
-    const uint8_t v = src[(ptrdiff_t)y * sstride + xe];
-    dst[(ptrdiff_t)y * dstride + xe] = m == 1 ? (uint8_t)255 : (m == 2 ? (uint8_t)0 : v);
+    int xe, y;
+    if (!lane_xy(w * cn, h, xe, y)) return;
+    dst[(ptrdiff_t)y * dstride + xe] = (uint8_t)impulse_px(sel[(ptrdiff_t)y * sel_stride + xe / cn], src[(ptrdiff_t)y * sstride + xe]);
 }
 
 // speckle_noise (photometric/noise.py:172-183): float32(px) + float32(px) * float64 noise is a float64 expression
@@ -583,9 +638,8 @@ __global__ void __launch_bounds__(256) k_speckle_noise(const uint8_t *__restrict
                                                        const double *__restrict__ noise, ptrdiff_t nstride,
                                                        uint8_t *__restrict__ dst, ptrdiff_t dstride)
 {
-    const int xe = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (xe >= wc || y >= h) return;
+    int xe, y;
+    if (!lane_xy(wc, h, xe, y)) return;
     const double m = (double)src[(ptrdiff_t)y * sstride + xe];
     const double t = m * noise[(ptrdiff_t)y * nstride + xe];
     double v = m + t;
@@ -610,19 +664,6 @@ __global__ void __launch_bounds__(256) k_histogram(const uint8_t *__restrict__ s
     __syncthreads();
     for (int i = threadIdx.x; i < cn * 256; i += 256)
         if (lh[i]) atomicAdd(&hist[i], lh[i]);
-}
-
-// dst[c] = lut[c][src[c]] on the selected channels (the per-value half of the two equalisations).
-__global__ void __launch_bounds__(256) k_apply_lut(const uint8_t *__restrict__ src, int h, int w, int cn, ptrdiff_t sstride,
-                                                   uint8_t *__restrict__ dst, ptrdiff_t dstride,
-                                                   const uint8_t *__restrict__ lut /* [cn][256] */, unsigned chmask)
-{
-    const int xe = blockIdx.x * 64 + threadIdx.x;
-    const int y = blockIdx.y * 4 + threadIdx.y;
-    if (xe >= w * cn || y >= h) return;
-    const int c = xe % cn;
-    const uint8_t v = src[(ptrdiff_t)y * sstride + xe];
-    dst[(ptrdiff_t)y * dstride + xe] = (chmask == 0 || ((chmask >> c) & 1u)) ? lut[c * 256 + v] : v;
 }
 
 // mat[pos_y, pos_x] (numpy advanced indexing with two index planes): the pixel shuffle of glass_blur,
@@ -712,10 +753,11 @@ __global__ void __launch_bounds__(256) k_line_streak(uint8_t *img, int h, int w,
 }
 
 // ---- dense planes: 16 bytes per lane ---------------------------------------------------------------------------------
-// The kernels above take any row pitch and move one byte (or one pixel) per lane: at 8192^2 they reach 1.0 - 1.6 TB/s,
+// The pitched mappers take any row pitch and move one byte (or one pixel) per lane: at 8192^2 they reach 1.0 - 1.6 TB/s,
 // bound by the number of memory instructions.  A dense plane (row pitch == row bytes, 16-byte aligned base pointers) is one
-// flat byte string: a lane takes one aligned 16-byte group of it, so a wavefront moves 1 KiB per load.  Same arithmetic
-// per byte.  The channel of byte j of group t is (16 t + j) mod cn.
+// flat byte string: a lane takes one aligned 16-byte group of it, so a wavefront moves 1 KiB per load.  The arithmetic per
+// byte is the operator's own: the kernels below hand the mappers the functors their pitched twins use.  The channel of
+// byte j of group t is (16 t + j) mod cn.
 __device__ __forceinline__ int first_channel16(size_t t, int cn) { return cn == 3 ? (int)(t % 3) : 0; }   // 16 = 1 mod 3; 1, 2, 4 divide 16
 
 template <class F>
@@ -749,30 +791,13 @@ __device__ __forceinline__ void map_bytes16(const uint8_t *__restrict__ src, uin
 __global__ void __launch_bounds__(256) k_mean_shift16(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, size_t n, int cn,
                                                       int delta, int has_thr, int thr, int cycle, unsigned chmask)
 {
-    map_bytes16(src, dst, n, cn, [=](int v, int c, int) {
-        if ((chmask == 0 || ((chmask >> c) & 1u)) && delta != 0) {
-            bool apply = true;
-            if (has_thr) apply = delta > 0 ? (v <= thr) : (thr <= v);
-            if (apply) v += delta;
-            v = cycle ? (v & 255) : vkd::clamp_u8(v);      // python's % 256 of a two's complement int is & 255
-        }
-        return v;
-    });
+    map_bytes16(src, dst, n, cn, MeanShiftOp{delta, has_thr, thr, cycle, chmask});
 }
 
 __global__ void __launch_bounds__(256) k_pointwise16(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, size_t n, int cn,
                                                      int op, int p0, int p1, unsigned chmask)
 {
-    // complement / posterization (the permutation needs whole pixels: k_pointwise)
-    map_bytes16(src, dst, n, cn, [=](int v, int c, int) {
-        const bool on = chmask == 0 || ((chmask >> c) & 1u);
-        if (op == VKX_POINT_COMPLEMENT) {
-            if (on && (p0 < 0 || (p1 ? v <= p0 : p0 <= v))) v = 255 - v;
-        } else if (on) {
-            v &= (0xFF >> p0) << p0;
-        }
-        return v;
-    });
+    map_bytes16(src, dst, n, cn, PointOp{op, p0, p1, chmask});
 }
 
 __global__ void __launch_bounds__(256) k_apply_lut16(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, size_t n, int cn,
@@ -781,10 +806,7 @@ __global__ void __launch_bounds__(256) k_apply_lut16(const uint8_t *__restrict__
     __shared__ uint32_t table_w[256];       // the table may sit in mapped host memory: whole dwords, one round trip per workgroup
     if ((int)threadIdx.x < cn * 64) table_w[threadIdx.x] = ((const uint32_t *)lut)[threadIdx.x];
     __syncthreads();
-    const uint8_t *table = (const uint8_t *)table_w;
-    map_bytes16(src, dst, n, cn, [&](int v, int c, int) {
-        return (chmask == 0 || ((chmask >> c) & 1u)) ? (int)table[c * 256 + v] : v;
-    });
+    map_bytes16(src, dst, n, cn, LutOp{(const uint8_t *)table_w, chmask});
 }
 
 // ... and up to eight dense single-channel planes, each through its own table, in one launch (blockIdx.y = plane): PageResizingStep
@@ -801,8 +823,7 @@ __global__ void __launch_bounds__(256) k_apply_lut16_planes(LutPlanes P, const u
     if ((size_t)blockIdx.x * 4096 >= P.n[p]) return;          // (uniform per workgroup: before the barrier)
     if (threadIdx.x < 64) table_w[threadIdx.x] = ((const uint32_t *)(luts + 256 * p))[threadIdx.x];
     __syncthreads();
-    const uint8_t *table = (const uint8_t *)table_w;
-    map_bytes16(P.src[p], P.dst[p], (size_t)P.n[p], 1, [&](int v, int, int) { return (int)table[v]; });
+    map_bytes16(P.src[p], P.dst[p], (size_t)P.n[p], 1, LutOp{(const uint8_t *)table_w, 0});
 }
 
 __global__ void __launch_bounds__(256) k_add_noise16(const uint8_t *__restrict__ src, const int16_t *__restrict__ noise,
@@ -823,14 +844,12 @@ __global__ void __launch_bounds__(256) k_add_noise16(const uint8_t *__restrict__
             for (int b = 0; b < 4; b++) {
                 const int j = 4 * k + b;
                 const int16_t nz = (int16_t)(z[j >> 1] >> (16 * (j & 1)));
-                // int16 arithmetic like the reference's (uint8 -> int16) + int16 sum: wraps at 16 bits
-                const int v = (int16_t)((int16_t)((w[k] >> (8 * b)) & 0xffu) + nz);
-                o[k] |= (uint32_t)vkd::clamp_u8(v) << (8 * b);
+                o[k] |= (uint32_t)add_noise_px((int)((w[k] >> (8 * b)) & 0xffu), nz) << (8 * b);
             }
         }
         *(uint4 *)(dst + i0) = make_uint4(o[0], o[1], o[2], o[3]);
     } else {
-        for (size_t i = i0; i < n; i++) dst[i] = (uint8_t)vkd::clamp_u8((int16_t)((int16_t)src[i] + noise[i]));
+        for (size_t i = i0; i < n; i++) dst[i] = (uint8_t)add_noise_px(src[i], noise[i]);
     }
 }
 
@@ -855,21 +874,18 @@ __global__ void __launch_bounds__(256) k_impulse_noise16(const uint8_t *__restri
             const int px = j / CN;
             const uint32_t s = (m[px >> 2] >> (8 * (px & 3))) & 0xffu;
             const uint32_t keep = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-            const uint32_t v = s == 1 ? 255u : (s == 2 ? 0u : keep);
+            const uint32_t v = impulse_px(s, keep);
             w[j >> 2] = (w[j >> 2] & ~(0xffu << (8 * (j & 3)))) | (v << (8 * (j & 3)));
         }
 #pragma unroll
         for (int q = 0; q < CN; q++) *(uint4 *)(dst + p0 * CN + 16 * q) = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
     } else {
-        for (size_t p = p0; p < npix; p++) {
-            const int s = sel[p];
-            for (int c = 0; c < CN; c++) dst[p * CN + c] = s == 1 ? (uint8_t)255 : (s == 2 ? (uint8_t)0 : src[p * CN + c]);
-        }
+        for (size_t p = p0; p < npix; p++)
+            for (int c = 0; c < CN; c++) dst[p * CN + c] = (uint8_t)impulse_px(sel[p], src[p * CN + c]);
     }
 }
 
-// RGB pixel operators on a dense plane: a lane takes 4 pixels = 12 bytes = 3 dwords; the HSV division tables and the hue
-// sector selectors sit in LDS (colour shift: the arithmetic of the fused chain kernel, vkd::hue_shift_packed).
+// RGB pixel operators on a dense plane: a lane takes 4 pixels = 12 bytes = 3 dwords
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 
 template <class F>
@@ -902,21 +918,7 @@ template <int MODE>
 __global__ void __launch_bounds__(256) k_hsv4(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, size_t npix, int delta,
                                               const HsvTables *__restrict__ T)
 {
-    __shared__ int lsdiv[256], lhdiv[256];
-    __shared__ uint32_t lsel[8];
-    if (MODE != 2) {
-        lsdiv[threadIdx.x] = T->sdiv[threadIdx.x];
-        lhdiv[threadIdx.x] = T->hdiv[threadIdx.x];
-        if (threadIdx.x < 8) lsel[threadIdx.x] = vkd::kHsvSelectors[threadIdx.x];
-        __syncthreads();
-    }
-    map_rgb4(src, dst, npix, [&](uint32_t a, uint32_t b, uint32_t c) -> uint32_t {
-        if (MODE == 0) return vkd::hue_shift_packed(lsdiv, lhdiv, lsel, delta, (int)a, (int)b, (int)c);
-        int x, y, z;
-        if (MODE == 1) vkd::rgb2hsv_full(lsdiv, lhdiv, (int)a, (int)b, (int)c, x, y, z);
-        else vkd::hsv2rgb_full((int)a, (int)b, (int)c, x, y, z);
-        return (uint32_t)x | ((uint32_t)y << 8) | ((uint32_t)z << 16);
-    });
+    map_rgb4(src, dst, npix, hsv_op_staged<MODE>(T, threadIdx.x, delta));
 }
 
 // brightness_shift / RGB <-> HLS / color_balance (k_cvt modes 0, 1, 2, 5)
@@ -924,34 +926,7 @@ template <int MODE>
 __global__ void __launch_bounds__(256) k_cvt4(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, size_t npix, int delta,
                                               float w0, float w1)
 {
-    map_rgb4(src, dst, npix, [=](uint32_t ua, uint32_t ub, uint32_t uc) -> uint32_t {
-        int a = (int)ua, b = (int)ub, c = (int)uc;
-        if (MODE == 5) {
-            const float gray = (float)rgb2gray_px(a, b, c);
-            const int in[3] = {a, b, c};
-            uint32_t q = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const float t0 = w0 * gray, t1 = w1 * (float)in[k];
-                float v = t0 + t1;
-                v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
-                q |= (uint32_t)(uint8_t)v << (8 * k);
-            }
-            return q;
-        }
-        if (MODE == 0 || MODE == 1) {
-            int H, L, S;
-            rgb2hls_px(a, b, c, H, L, S);
-            a = H; b = L; c = S;
-        }
-        if (MODE == 0 && delta != 0) b = vkd::clamp_u8(b + delta);
-        if (MODE == 0 || MODE == 2) {
-            int R, G, B;
-            hls2rgb_px(a, b, c, R, G, B);
-            a = R; b = G; c = B;
-        }
-        return (uint32_t)a | ((uint32_t)b << 8) | ((uint32_t)c << 16);
-    });
+    map_rgb4(src, dst, npix, CvtOp<MODE>{delta, w0, w1});
 }
 
 // Histogram of a dense plane: a few hundred workgroups stride over the 16-byte groups, every wavefront counts into its
@@ -989,11 +964,36 @@ __global__ void __launch_bounds__(256) k_histogram16(const uint8_t *__restrict__
     }
 }
 
-// a plane qualifies when its rows follow each other without gaps and every pointer is aligned for the widest access
-inline bool dense16(const void *a, ptrdiff_t a_pitch, const void *b, ptrdiff_t b_pitch, size_t row_bytes, int h, unsigned align = 16)
+// ---- host side: dense body or pitched body ----------------------------------------------------------------------------
+// A plane as the choice sees it: base pointer, row pitch and row length, both in the plane's own unit (bytes or elements).
+struct PlaneRef {
+    const void *ptr;
+    ptrdiff_t pitch;
+    size_t row;
+};
+
+// The planes of a call (source, destination, a noise or selector plane) go to the dense body when their rows follow each
+// other without gaps and every pointer is aligned for the widest access.
+inline bool dense_planes(int h, unsigned align, std::initializer_list<PlaneRef> planes)
 {
-    return (h == 1 || ((size_t)a_pitch == row_bytes && (size_t)b_pitch == row_bytes)) &&
-           (((uintptr_t)a | (uintptr_t)b) & (align - 1)) == 0;
+    for (const PlaneRef &p : planes)
+        if ((h != 1 && (size_t)p.pitch != p.row) || ((uintptr_t)p.ptr & (align - 1)) != 0) return false;
+    return true;
+}
+
+// the launch shape of the pitched bodies (lane_xy): one element of cols x rows per lane
+const dim3 kBlock64x4(64, 4);
+inline dim3 grid64x4(size_t cols, int rows) { return dim3(vkx_blocks(cols, 64), vkx_blocks(rows, 4)); }
+
+// One element-wise launch under its timing name: on dense planes dense_body(blocks), a lane taking `per_lane` of the plane's
+// n units (bytes or pixels); otherwise its twin pitched_body(grid, block), a lane taking one of the cols x h elements.
+template <class Dense, class Pitched>
+void launch_bodies(vkx_ctx *ctx, const char *name, bool dense, size_t n, unsigned per_lane, size_t cols, int h, Dense dense_body,
+                   Pitched pitched_body)
+{
+    VKX_TIMED(ctx, name);
+    if (dense) dense_body(vkx_blocks((n + per_lane - 1) / per_lane, 256));
+    else pitched_body(grid64x4(cols, h), kBlock64x4);
 }
 
 int check_plane(vkx_ctx *ctx, const void *src, const void *dst, int h, int w)
@@ -1002,6 +1002,18 @@ int check_plane(vkx_ctx *ctx, const void *src, const void *dst, int h, int w)
     VKX_REQUIRE(h >= 0 && w >= 0, "bad shape");
     return VKX_OK;
 }
+
+// The argument checks the element-wise entry points open with, in the order their callers see the refusals: the pitches of
+// the source, of a side plane (`side_pitch`: its VKX_REQUIRE_PITCH, or empty) and of the destination, the pointers and the
+// shape, the side plane's pointer (`side_ptr`: its VKX_REQUIRE, or empty), the channel count.  A macro, because VKX_REQUIRE
+// names the entry point it stands in and VKX_REQUIRE_PITCH the argument it refuses; it returns from that entry point.
+#define VKX_CHECK_ELEMENTWISE(ctx, src, src_stride, dst, dst_stride, h, w, cn, side_pitch, side_ptr) \
+    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)(w) * (cn), h);                                            \
+    side_pitch;                                                                                         \
+    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)(w) * (cn), h);                                            \
+    if (int rc__ = check_plane(ctx, src, dst, h, w)) return rc__;                                       \
+    side_ptr;                                                                                           \
+    VKX_REQUIRE((cn) >= 1 && (cn) <= 4, "1..4 channels")
 
 } // namespace
 
@@ -1110,14 +1122,10 @@ static int launch_hsv(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t 
     const HsvTables *T = nullptr;
     rc = hsv_tables(ctx, &T);
     if (rc) return rc;
-    if (dense16(src, src_stride, dst, dst_stride, (size_t)w * 3, h, 4)) {
-        const size_t npix = (size_t)h * w;
-        { VKX_TIMED(ctx, "k_hsv"); k_hsv4<MODE><<<vkx_blocks((npix + 3) / 4, 256), 256, 0, ctx->stream>>>(src, dst, npix, delta, T); }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    dim3 block(64, 4), grid(vkx_blocks(w, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_hsv"); k_hsv<MODE><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride, delta, T); }
+    const size_t npix = (size_t)h * w, row = (size_t)w * 3;
+    launch_bodies(ctx, "k_hsv", dense_planes(h, 4, {{src, src_stride, row}, {dst, dst_stride, row}}), npix, 4, w, h,
+        [&](unsigned blocks) { k_hsv4<MODE><<<blocks, 256, 0, ctx->stream>>>(src, dst, npix, delta, T); },
+        [&](dim3 grid, dim3 block) { k_hsv<MODE><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride, delta, T); });
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1146,16 +1154,21 @@ static int launch_cvt(vkx_ctx *ctx, const uint8_t *src, int h, int w, ptrdiff_t 
     int rc = check_plane(ctx, src, dst, h, w);
     if (rc) return rc;
     if (h == 0 || w == 0) return VKX_OK;
-    if constexpr (MODE == 0 || MODE == 1 || MODE == 2 || MODE == 5) {
-        if (dense16(src, src_stride, dst, dst_stride, (size_t)w * 3, h, 4)) {
-            const size_t npix = (size_t)h * w;
-            { VKX_TIMED(ctx, "k_cvt"); k_cvt4<MODE><<<vkx_blocks((npix + 3) / 4, 256), 256, 0, ctx->stream>>>(src, dst, npix, delta, w0, w1); }
-            VKX_LAUNCH_CHECK();
-            return VKX_OK;
-        }
-    }
-    dim3 block(64, 4), grid(vkx_blocks(w, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_cvt"); k_cvt<MODE><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride, delta, w0, w1); }
+    const size_t npix = (size_t)h * w, row = (size_t)w * 3;
+    launch_bodies(ctx, "k_cvt", dense_planes(h, 4, {{src, src_stride, row}, {dst, dst_stride, row}}), npix, 4, w, h,
+        [&](unsigned blocks) { k_cvt4<MODE><<<blocks, 256, 0, ctx->stream>>>(src, dst, npix, delta, w0, w1); },
+        [&](dim3 grid, dim3 block) { k_cvt<MODE><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride, delta, w0, w1); });
+    VKX_LAUNCH_CHECK();
+    return VKX_OK;
+}
+
+// the conversions that change the channel count (k_cvt_cn), arguments checked by the caller, under the timing name each has had
+template <int MODE>
+static int launch_cvt_cn(vkx_ctx *ctx, const char *name, const uint8_t *src, int h, int w, ptrdiff_t src_stride, uint8_t *dst,
+                         ptrdiff_t dst_stride)
+{
+    if (h == 0 || w == 0) return VKX_OK;
+    { VKX_TIMED(ctx, name); k_cvt_cn<MODE><<<grid64x4(w, h), kBlock64x4, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride); }
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1175,25 +1188,22 @@ VKX_EXPORT int vkx_cvt_color_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int
     switch (code) {
     case VKX_CVT_RGB2HLS_FULL: return launch_cvt<1>(ctx, src, h, w, src_stride, 0, 0.f, 0.f, dst, dst_stride);
     case VKX_CVT_HLS2RGB_FULL: return launch_cvt<2>(ctx, src, h, w, src_stride, 0, 0.f, 0.f, dst, dst_stride);
-    case VKX_CVT_RGB2GRAY:
-        VKX_REQUIRE(src != dst, "RGB2GRAY cannot run in place");
-        return launch_cvt<3>(ctx, src, h, w, src_stride, 0, 0.f, 0.f, dst, dst_stride);
-    case VKX_CVT_GRAY2RGB:
-        VKX_REQUIRE(src != dst, "GRAY2RGB cannot run in place");
-        return launch_cvt<4>(ctx, src, h, w, src_stride, 0, 0.f, 0.f, dst, dst_stride);
+    case VKX_CVT_RGB2GRAY: case VKX_CVT_GRAY2RGB: {
+        if (code == VKX_CVT_RGB2GRAY) VKX_REQUIRE(src != dst, "RGB2GRAY cannot run in place");
+        else VKX_REQUIRE(src != dst, "GRAY2RGB cannot run in place");
+        int rc = check_plane(ctx, src, dst, h, w);
+        if (rc) return rc;
+        return code == VKX_CVT_RGB2GRAY ? launch_cvt_cn<3>(ctx, "k_cvt", src, h, w, src_stride, dst, dst_stride)
+                                        : launch_cvt_cn<4>(ctx, "k_cvt", src, h, w, src_stride, dst, dst_stride);
+    }
     case VKX_CVT_RGBA2RGB: case VKX_CVT_RGB2RGBA: case VKX_CVT_GRAY2RGBA: case VKX_CVT_RGBA2GRAY: {
         int rc = check_plane(ctx, src, dst, h, w);
         if (rc) return rc;
         VKX_REQUIRE(src != dst, "the alpha conversions cannot run in place");
-        if (h == 0 || w == 0) return VKX_OK;
-        dim3 block(64, 4), grid(vkx_blocks(w, 64), vkx_blocks(h, 4));
-        VKX_TIMED(ctx, "k_cvt_alpha");
-        if (code == VKX_CVT_RGBA2RGB) k_cvt_alpha<6><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride);
-        else if (code == VKX_CVT_RGB2RGBA) k_cvt_alpha<7><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride);
-        else if (code == VKX_CVT_GRAY2RGBA) k_cvt_alpha<8><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride);
-        else k_cvt_alpha<9><<<grid, block, 0, ctx->stream>>>(src, h, w, src_stride, dst, dst_stride);
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
+        if (code == VKX_CVT_RGBA2RGB) return launch_cvt_cn<6>(ctx, "k_cvt_alpha", src, h, w, src_stride, dst, dst_stride);
+        if (code == VKX_CVT_RGB2RGBA) return launch_cvt_cn<7>(ctx, "k_cvt_alpha", src, h, w, src_stride, dst, dst_stride);
+        if (code == VKX_CVT_GRAY2RGBA) return launch_cvt_cn<8>(ctx, "k_cvt_alpha", src, h, w, src_stride, dst, dst_stride);
+        return launch_cvt_cn<9>(ctx, "k_cvt_alpha", src, h, w, src_stride, dst, dst_stride);
     }
     case VKX_CVT_RGB2HSV_FULL: return vkx_cvt_rgb_hsv_u8_dev(ctx, src, h, w, src_stride, 1, dst, dst_stride);
     case VKX_CVT_HSV2RGB_FULL: return vkx_cvt_rgb_hsv_u8_dev(ctx, src, h, w, src_stride, 0, dst, dst_stride);
@@ -1233,9 +1243,9 @@ VKX_EXPORT int vkx_blend_u8_dev(vkx_ctx *ctx, const uint8_t *a, ptrdiff_t a_stri
     if (rc) return rc;
     VKX_REQUIRE(b != nullptr && cn >= 1 && cn <= 4, "bad argument");
     if (h == 0 || w == 0) return VKX_OK;
-    dim3 block(64, 4), grid(vkx_blocks((size_t)w * cn, 64), vkx_blocks(h, 4));
     VKX_TIMED(ctx, "k_blend_u8");
-    k_blend_u8<<<grid, block, 0, ctx->stream>>>(a, a_stride, b, b_stride, h, w * cn, cn, (float)w0, (float)w1, channel_mask, dst, dst_stride);
+    k_blend_u8<<<grid64x4((size_t)w * cn, h), kBlock64x4, 0, ctx->stream>>>(a, a_stride, b, b_stride, h, w * cn, cn, (float)w0, (float)w1, channel_mask,
+                                                                            dst, dst_stride);
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1252,9 +1262,8 @@ VKX_EXPORT int vkx_fog_f32_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w
     if (h == 0 || w == 0) return VKX_OK;
     float f[4] = {0.f, 0.f, 0.f, 0.f};
     for (int c = 0; c < cn; c++) f[c] = fog[c];
-    dim3 block(64, 4), grid(vkx_blocks(w, 64), vkx_blocks(h, 4));
     VKX_TIMED(ctx, "k_fog_f32");
-    k_fog_f32<<<grid, block, 0, ctx->stream>>>(src, src_stride, weight, weight_stride_el, h, w, cn, f[0], f[1], f[2], f[3], dst, dst_stride);
+    k_fog_f32<<<grid64x4(w, h), kBlock64x4, 0, ctx->stream>>>(src, src_stride, weight, weight_stride_el, h, w, cn, f[0], f[1], f[2], f[3], dst, dst_stride);
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1263,22 +1272,14 @@ VKX_EXPORT int vkx_mean_shift_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, in
                                      int delta, int has_threshold, int threshold, int cycle, unsigned channel_mask,
                                      uint8_t *dst, ptrdiff_t dst_stride)
 {
-    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
-    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
-    int rc = check_plane(ctx, src, dst, h, w);
-    if (rc) return rc;
-    VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
+    VKX_CHECK_ELEMENTWISE(ctx, src, src_stride, dst, dst_stride, h, w, cn, , );
     if (h == 0 || w == 0) return VKX_OK;
-    if (dense16(src, src_stride, dst, dst_stride, (size_t)w * cn, h)) {
-        const size_t n = (size_t)h * w * cn;
-        { VKX_TIMED(ctx, "k_mean_shift"); k_mean_shift16<<<vkx_blocks((n + 15) / 16, 256), 256, 0, ctx->stream>>>(src, dst, n, cn, delta, has_threshold,
-                                                                                                           threshold, cycle, channel_mask); }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    dim3 block(64, 4), grid(vkx_blocks((size_t)w * cn, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_mean_shift"); k_mean_shift<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, dst, dst_stride, delta, has_threshold,
-                                                  threshold, cycle, channel_mask); }
+    const size_t row = (size_t)w * cn, n = h * row;
+    launch_bodies(ctx, "k_mean_shift", dense_planes(h, 16, {{src, src_stride, row}, {dst, dst_stride, row}}), n, 16, row, h,
+        [&](unsigned blocks) { k_mean_shift16<<<blocks, 256, 0, ctx->stream>>>(src, dst, n, cn, delta, has_threshold, threshold, cycle, channel_mask); },
+        [&](dim3 grid, dim3 block) {
+            k_mean_shift<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, dst, dst_stride, delta, has_threshold, threshold, cycle, channel_mask);
+        });
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1286,6 +1287,7 @@ VKX_EXPORT int vkx_mean_shift_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, in
 VKX_EXPORT int vkx_pointwise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride, int op,
                                     int p0, int p1, unsigned channel_mask, uint8_t *dst, ptrdiff_t dst_stride)
 {
+    // not VKX_CHECK_ELEMENTWISE: the permutation's overlap test has its place between the pitches and the pointers
     VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
     VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
     if (op == VKX_POINT_PERMUTE) VKX_REQUIRE_DISJOINT(src, h, src_stride, (size_t)w * cn, dst, h, dst_stride, (size_t)w * cn);
@@ -1300,14 +1302,17 @@ VKX_EXPORT int vkx_pointwise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int
         for (int c = 0; c < cn; c++) VKX_REQUIRE(((p0 >> (2 * c)) & 3) < cn, "permutation index out of range");
     }
     if (h == 0 || w == 0) return VKX_OK;
-    if (op != VKX_POINT_PERMUTE && dense16(src, src_stride, dst, dst_stride, (size_t)w * cn, h)) {
-        const size_t n = (size_t)h * w * cn;
-        { VKX_TIMED(ctx, "k_pointwise"); k_pointwise16<<<vkx_blocks((n + 15) / 16, 256), 256, 0, ctx->stream>>>(src, dst, n, cn, op, p0, p1, channel_mask); }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
+    const size_t row = (size_t)w * cn, n = h * row;
+    if (op == VKX_POINT_PERMUTE) {
+        VKX_TIMED(ctx, "k_pointwise");
+        k_permute<<<grid64x4(row, h), kBlock64x4, 0, ctx->stream>>>(src, h, w, cn, src_stride, dst, dst_stride, p0);
+    } else {
+        launch_bodies(ctx, "k_pointwise", dense_planes(h, 16, {{src, src_stride, row}, {dst, dst_stride, row}}), n, 16, row, h,
+            [&](unsigned blocks) { k_pointwise16<<<blocks, 256, 0, ctx->stream>>>(src, dst, n, cn, op, p0, p1, channel_mask); },
+            [&](dim3 grid, dim3 block) {
+                k_pointwise<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, dst, dst_stride, op, p0, p1, channel_mask);
+            });
     }
-    dim3 block(64, 4), grid(vkx_blocks((size_t)w * cn, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_pointwise"); k_pointwise<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, dst, dst_stride, op, p0, p1, channel_mask); }
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1316,27 +1321,21 @@ VKX_EXPORT int vkx_impulse_noise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h,
                                         const uint8_t *selector, ptrdiff_t selector_stride, uint8_t *dst,
                                         ptrdiff_t dst_stride)
 {
-    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
-    VKX_REQUIRE_PITCH(selector_stride, w, h);
-    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
-    int rc = check_plane(ctx, src, dst, h, w);
-    if (rc) return rc;
-    VKX_REQUIRE(selector != nullptr, "NULL selector plane");
-    VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
+    VKX_CHECK_ELEMENTWISE(ctx, src, src_stride, dst, dst_stride, h, w, cn, VKX_REQUIRE_PITCH(selector_stride, w, h),
+                          VKX_REQUIRE(selector != nullptr, "NULL selector plane"));
     if (h == 0 || w == 0) return VKX_OK;
-    if (cn != 2 && dense16(src, src_stride, dst, dst_stride, (size_t)w * cn, h) && (h == 1 || selector_stride == w) &&
-        ((uintptr_t)selector & 15) == 0) {
-        const size_t npix = (size_t)h * w;
-        const unsigned blocks = vkx_blocks((npix + 15) / 16, 256);
-        VKX_TIMED(ctx, "k_impulse_noise");
-        if (cn == 1) k_impulse_noise16<1><<<blocks, 256, 0, ctx->stream>>>(src, selector, dst, npix);
-        else if (cn == 3) k_impulse_noise16<3><<<blocks, 256, 0, ctx->stream>>>(src, selector, dst, npix);
-        else k_impulse_noise16<4><<<blocks, 256, 0, ctx->stream>>>(src, selector, dst, npix);
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    dim3 block(64, 4), grid(vkx_blocks((size_t)w * cn, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_impulse_noise"); k_impulse_noise<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, selector, selector_stride, dst, dst_stride); }
+    const size_t row = (size_t)w * cn, npix = (size_t)h * w;
+    // the dense body takes 16 whole pixels per lane, written for 1, 3 and 4 channels
+    const bool dense = cn != 2 && dense_planes(h, 16, {{src, src_stride, row}, {dst, dst_stride, row}, {selector, selector_stride, (size_t)w}});
+    launch_bodies(ctx, "k_impulse_noise", dense, npix, 16, row, h,
+        [&](unsigned blocks) {
+            if (cn == 1) k_impulse_noise16<1><<<blocks, 256, 0, ctx->stream>>>(src, selector, dst, npix);
+            else if (cn == 3) k_impulse_noise16<3><<<blocks, 256, 0, ctx->stream>>>(src, selector, dst, npix);
+            else k_impulse_noise16<4><<<blocks, 256, 0, ctx->stream>>>(src, selector, dst, npix);
+        },
+        [&](dim3 grid, dim3 block) {
+            k_impulse_noise<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, selector, selector_stride, dst, dst_stride);
+        });
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1344,16 +1343,13 @@ VKX_EXPORT int vkx_impulse_noise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h,
 VKX_EXPORT int vkx_speckle_noise_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                         const double *noise, ptrdiff_t noise_stride_el, uint8_t *dst, ptrdiff_t dst_stride)
 {
-    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
-    VKX_REQUIRE_PITCH(noise_stride_el, (ptrdiff_t)w * cn, h);
-    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
-    int rc = check_plane(ctx, src, dst, h, w);
-    if (rc) return rc;
-    VKX_REQUIRE(noise != nullptr, "NULL noise plane");
-    VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
+    VKX_CHECK_ELEMENTWISE(ctx, src, src_stride, dst, dst_stride, h, w, cn, VKX_REQUIRE_PITCH(noise_stride_el, (ptrdiff_t)w * cn, h),
+                          VKX_REQUIRE(noise != nullptr, "NULL noise plane"));
     if (h == 0 || w == 0) return VKX_OK;
-    dim3 block(64, 4), grid(vkx_blocks((size_t)w * cn, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_speckle_noise"); k_speckle_noise<<<grid, block, 0, ctx->stream>>>(src, h, w * cn, src_stride, noise, noise_stride_el, dst, dst_stride); }
+    {
+        VKX_TIMED(ctx, "k_speckle_noise");
+        k_speckle_noise<<<grid64x4((size_t)w * cn, h), kBlock64x4, 0, ctx->stream>>>(src, h, w * cn, src_stride, noise, noise_stride_el, dst, dst_stride);
+    }
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1383,33 +1379,25 @@ VKX_EXPORT int vkx_histogram_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int
 VKX_EXPORT int vkx_apply_lut_u8_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                     const uint8_t *lut_host, unsigned channel_mask, uint8_t *dst, ptrdiff_t dst_stride)
 {
-    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
-    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
-    int rc = check_plane(ctx, src, dst, h, w);
-    if (rc) return rc;
-    VKX_REQUIRE(lut_host != nullptr, "NULL table");
-    VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
+    VKX_CHECK_ELEMENTWISE(ctx, src, src_stride, dst, dst_stride, h, w, cn, , VKX_REQUIRE(lut_host != nullptr, "NULL table"));
     if (h == 0 || w == 0) return VKX_OK;
     // the table is the caller's memory: it travels through the page-locked descriptor ring, no stream synchronisation.  The dense
     // kernel stages it to LDS once per workgroup straight from the (mapped) ring: no copy, one dispatch per call instead of two
     // (PageResizingStep binarises seven planes per page through this entry)
     vkx_tables tab(ctx);
-    if ((rc = tab.take((size_t)256 * cn))) return rc;
+    int rc = tab.take((size_t)256 * cn);
+    if (rc) return rc;
     memcpy(tab.host, lut_host, tab.bytes);
-    const bool dense = dense16(src, src_stride, dst, dst_stride, (size_t)w * cn, h);
+    const size_t row = (size_t)w * cn, n = h * row;
+    const bool dense = dense_planes(h, 16, {{src, src_stride, row}, {dst, dst_stride, row}});
     const uint8_t *table = dense ? tab.mapped() : nullptr;
     if (!table) {                    // the strided kernel reads the table per pixel: from device memory
         if ((rc = tab.copy_to(&ctx->misc, 1024))) return rc;
         table = (const uint8_t *)ctx->misc.ptr;
     }
-    if (dense) {
-        const size_t n = (size_t)h * w * cn;
-        { VKX_TIMED(ctx, "k_apply_lut"); k_apply_lut16<<<vkx_blocks((n + 15) / 16, 256), 256, 0, ctx->stream>>>(src, dst, n, cn, table, channel_mask); }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    dim3 block(64, 4), grid(vkx_blocks((size_t)w * cn, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_apply_lut"); k_apply_lut<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, dst, dst_stride, table, channel_mask); }
+    launch_bodies(ctx, "k_apply_lut", dense, n, 16, row, h,
+        [&](unsigned blocks) { k_apply_lut16<<<blocks, 256, 0, ctx->stream>>>(src, dst, n, cn, table, channel_mask); },
+        [&](dim3 grid, dim3 block) { k_apply_lut<<<grid, block, 0, ctx->stream>>>(src, h, w, cn, src_stride, dst, dst_stride, table, channel_mask); });
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1494,23 +1482,13 @@ VKX_EXPORT int vkx_saturate_i64_u8_dev(vkx_ctx *ctx, const int64_t *src, size_t 
 VKX_EXPORT int vkx_add_noise_i16_dev(vkx_ctx *ctx, const uint8_t *src, int h, int w, int cn, ptrdiff_t src_stride,
                                      const int16_t *noise, ptrdiff_t noise_stride_el, uint8_t *dst, ptrdiff_t dst_stride)
 {
-    VKX_REQUIRE_PITCH(src_stride, (ptrdiff_t)w * cn, h);
-    VKX_REQUIRE_PITCH(noise_stride_el, (ptrdiff_t)w * cn, h);
-    VKX_REQUIRE_PITCH(dst_stride, (ptrdiff_t)w * cn, h);
-    int rc = check_plane(ctx, src, dst, h, w);
-    if (rc) return rc;
-    VKX_REQUIRE(noise != nullptr, "NULL noise plane");
-    VKX_REQUIRE(cn >= 1 && cn <= 4, "1..4 channels");
+    VKX_CHECK_ELEMENTWISE(ctx, src, src_stride, dst, dst_stride, h, w, cn, VKX_REQUIRE_PITCH(noise_stride_el, (ptrdiff_t)w * cn, h),
+                          VKX_REQUIRE(noise != nullptr, "NULL noise plane"));
     if (h == 0 || w == 0) return VKX_OK;
-    if (dense16(src, src_stride, dst, dst_stride, (size_t)w * cn, h) && (h == 1 || noise_stride_el == (ptrdiff_t)w * cn) &&
-        ((uintptr_t)noise & 15) == 0) {
-        const size_t n = (size_t)h * w * cn;
-        { VKX_TIMED(ctx, "k_add_noise"); k_add_noise16<<<vkx_blocks((n + 15) / 16, 256), 256, 0, ctx->stream>>>(src, noise, dst, n); }
-        VKX_LAUNCH_CHECK();
-        return VKX_OK;
-    }
-    dim3 block(64, 4), grid(vkx_blocks((size_t)w * cn, 64), vkx_blocks(h, 4));
-    { VKX_TIMED(ctx, "k_add_noise"); k_add_noise<<<grid, block, 0, ctx->stream>>>(src, h, w * cn, src_stride, noise, noise_stride_el, dst, dst_stride); }
+    const size_t row = (size_t)w * cn, n = h * row;
+    launch_bodies(ctx, "k_add_noise", dense_planes(h, 16, {{src, src_stride, row}, {dst, dst_stride, row}, {noise, noise_stride_el, row}}), n, 16, row, h,
+        [&](unsigned blocks) { k_add_noise16<<<blocks, 256, 0, ctx->stream>>>(src, noise, dst, n); },
+        [&](dim3 grid, dim3 block) { k_add_noise<<<grid, block, 0, ctx->stream>>>(src, h, w * cn, src_stride, noise, noise_stride_el, dst, dst_stride); });
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
