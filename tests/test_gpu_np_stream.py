@@ -273,6 +273,37 @@ def test_large_call_runs_in_pipelined_chunks():
                 assert N.pcg64_jump(*N.np_stream(np.random.default_rng(300 + i)), res_array[i].draws) == ref.bit_generator.state['state']['state']
 
 
+def test_large_speckle_call_runs_in_pipelined_chunks():
+    """VKX_NP_SPECKLE_U8 through the same chunked form: the one kind whose tiles leave the draw pass as raw-draw records and masks
+    and go through the placement pass (k_np_draw / k_np_place, nprand.hip).  83 streams in place, lengths on both sides of one and
+    two tiles of 3 072 raw draws, every third pixel black; the expected pixels are numpy's alone."""
+    ctx = N.default_ctx()
+    rng = np.random.default_rng(78)
+    B = 83
+    sizes = [1, 2, 63, 64, 65, 3_000, 3_072, 3_073, 6_200, 20_011]
+    sizes += [int(v) for v in rng.integers(1, 20_000, B - len(sizes))]
+    stds = [float(v) for v in rng.uniform(0.05, 0.5, B)]
+    jobs = (N.VkxNpJob * B)()
+    res = N.NpResults(ctx, B)
+    planes, pixels = [], []
+    for i in range(B):
+        px = np.random.default_rng(900 + i).integers(0, 256, sizes[i], dtype=np.uint8)
+        px[::3] = 0
+        d = ctx.to_device(px)
+        pixels.append(px)
+        planes.append(d)
+        jobs[i] = N.np_job(N.NP_SPECKLE_U8, N.np_stream(np.random.default_rng(500 + i)), sizes[i], stds[i], src=d.ptr, dst=d.ptr)
+    N.check(N.lib().vkx_np_draw_batch_dev(ctx.handle, jobs, B, res.array))
+    ctx.sync()
+    for i in range(B):
+        ref = np.random.default_rng(500 + i)
+        m = pixels[i].astype(np.float32)
+        want = np.clip(m + m * ref.normal(0, stds[i], sizes[i]), 0, 255).astype(np.uint8)
+        assert (planes[i].host() == want).all(), (i, sizes[i])
+        assert res[i].flags == 0 and res[i].samples >= sizes[i]
+        assert N.pcg64_jump(*N.np_stream(np.random.default_rng(500 + i)), res[i].draws) == ref.bit_generator.state['state']['state']
+
+
 def test_a_billion_samples():
     """>= 1e9 samples over seeds / lengths / deviations, every one compared with numpy (about a minute of host draws)."""
     ctx = N.default_ctx()

@@ -944,11 +944,8 @@ _ctx_lock = threading.Lock()
 
 
 def default_device():
-    for key in ('VKX_DEVICE', 'LOCAL_RANK'):
-        if os.environ.get(key, '') != '':
-            n = device_count()
-            return int(os.environ[key]) % max(n, 1)
-    return 0
+    value = os.environ.get('VKX_DEVICE', '') or os.environ.get('LOCAL_RANK', '')
+    return int(value) % max(device_count(), 1) if value != '' else 0
 
 
 def default_ctx():

@@ -6,7 +6,6 @@ planes) and issues the whole batch with ONE ``vkx_chain_rgb_batch_dev`` call.  I
 giving every process (one per GPU) its own ``ChainBatch``; there is no exchange step.
 """
 import ctypes
-import os
 import time
 from typing import List, Optional, Tuple
 
@@ -48,7 +47,7 @@ class ChainBatch:
         self.stream_chunk = 4096     # planes per vkx_np_draw_batch_dev call (the library pipelines a call in chunks of 32 planes)
         self.stream_fallbacks = 0    # planes the device declared ambiguous and the host drew instead
         self._runs = 0
-        self.joint_call = os.environ.get('VKX_CHAIN_JOINT', '1') != '0'       # tile-buffer streams + chain through vkx_chain_rgb_batch_np_dev (False: two calls, as in round 4)
+        self.joint_call = True       # tile-buffer streams + chain through vkx_chain_rgb_batch_np_dev (False: two calls, as in round 4)
         self._marked = False
         self._cam = []               # (item index, VkxCameraConfig, noise std or None, stream): items whose state is built on the device
         self._cam_state = None       # _CameraStates: records, lattice sets, page-locked results

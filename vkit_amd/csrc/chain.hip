@@ -49,7 +49,7 @@ VKX_EXPORT int vkx_chain_rgb_batch_dev(vkx_ctx *ctx, const vkx_chain_item *items
         if (bytes > max_plane) max_plane = bytes;
     }
     // Preferred: the tile-fused kernel (fused.hip).  VKX_CHAIN_STAGED=1 forces the per-stage kernels (A/B runs).
-    static const bool staged_only = [] { const char *e = getenv("VKX_CHAIN_STAGED"); return e && e[0] == '1'; }();
+    static const bool staged_only = vkx_env_on("VKX_CHAIN_STAGED", 0);
     if (!staged_only) {
         const int frc = vkx_chain_fused_try(ctx, items, n_items);
         if (frc != VKX_ERR_UNSUPPORTED) return frc;
@@ -157,9 +157,9 @@ VKX_EXPORT int vkx_chain_rgb_batch_np_dev(vkx_ctx *ctx, const vkx_chain_item *it
         if (it == item_of.end() || (k > 0 && it->second <= job_item[k - 1])) pipelined = false;    // unknown buffer / not in item order
         else job_item[k] = it->second;
     }
-    static const bool staged_only = [] { const char *e = getenv("VKX_CHAIN_STAGED"); return e && e[0] == '1'; }();
-    static const int want_chunks = [] { const char *e = getenv("VKX_CHAIN_CHUNKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2; }();
-    static const int overlap = [] { const char *e = getenv("VKX_CHAIN_OVERLAP"); return e ? atoi(e) : 0; }();
+    static const bool staged_only = vkx_env_on("VKX_CHAIN_STAGED", 0);
+    static const int chunks_env = vkx_env_int("VKX_CHAIN_CHUNKS", 0);
+    const int want_chunks = chunks_env > 0 ? chunks_env : 2;
     vkx_chain_plan *raw = nullptr;
     if (pipelined && !staged_only) {
         rc = vkx_chain_plan_build(ctx, items, n_items, &raw);
@@ -199,17 +199,6 @@ VKX_EXPORT int vkx_chain_rgb_batch_np_dev(vkx_ctx *ctx, const vkx_chain_item *it
         int rc = VKX_OK;
         hipStream_t aux = vkx_stream_by_id(ctx, VKX_STREAM_COPY_IN, &rc);
         if (rc) return rc;
-        hipStream_t side = vkx_stream_by_id(ctx, VKX_STREAM_COPY_OUT, &rc);
-        if (rc) return rc;
-        // what the caller queued before this call (the sources may be its product)
-        hipEvent_t entry = nullptr;
-        if (overlap) {
-            VKX_HIP(hipEventCreateWithFlags(&entry, hipEventDisableTiming));
-            hipError_t e = hipEventRecord(entry, main_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(side, entry, 0);
-            (void)hipEventDestroy(entry);       // (deferred until the event has completed)
-            VKX_HIP(e);
-        }
         // side stream: the cell setup of the whole batch (the compute stream is ordered after it by the call)
         hipEvent_t setup_done = nullptr;
         if ((rc = vkx_chain_plan_setup_aside(ctx, raw, &setup_done))) return rc;
@@ -232,20 +221,14 @@ VKX_EXPORT int vkx_chain_rgb_batch_np_dev(vkx_ctx *ctx, const vkx_chain_item *it
                 return VKX_ERR_INVALID;
             }
         }
-        // VKX_CHAIN_OVERLAP=1: the pixel kernels on the side stream, so that pixels(c) shares the device with draw(c + 1 ..)
-        hipStream_t pix = overlap ? side : main_stream;
-        if (setup_done && pix != side) VKX_HIP(hipStreamWaitEvent(pix, setup_done, 0));
+        // the pixel kernels, on the compute stream after the draws
+        if (setup_done) VKX_HIP(hipStreamWaitEvent(main_stream, setup_done, 0));
         for (int c = 0; c < n_chunks; c++) {
             Chunk &ch = chunks[c];
-            VKX_HIP(hipStreamWaitEvent(pix, ch.posted, 0));
-            ctx->stream = pix;
-            rc = vkx_chain_plan_tiles(ctx, raw, ch.item0, ch.nitems);
-            ctx->stream = main_stream;
-            if (rc) return rc;
+            VKX_HIP(hipStreamWaitEvent(main_stream, ch.posted, 0));
+            if ((rc = vkx_chain_plan_tiles(ctx, raw, ch.item0, ch.nitems))) return rc;
         }
-        if ((rc = vkx_chain_mark_done(ctx, pix))) return rc;
-        if (pix != main_stream && (rc = vkx_stream_order(ctx, main_stream, pix))) return rc;
-        return VKX_OK;
+        return vkx_chain_mark_done(ctx, main_stream);
     };
     rc = schedule();
     if (rc) vkx_ctx_join_streams(ctx, main_stream);

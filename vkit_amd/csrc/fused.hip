@@ -1499,7 +1499,7 @@ int vkx_chain_plan_tiles(vkx_ctx *ctx, vkx_chain_plan *p, int first, int count)
     // profiling aids: VKX_FUSED_PHASES=1|2 stops the kernel after phase A | C+D, 10..13 inside phase A (tools/phases_a.sh),
     // 20 writes the horizontal sums of the centre row instead of the finished pixel, 3 sends every non-empty rectangle tile
     // through the overfull list to the generic variant
-    static const int phase_limit = [] { const char *e = getenv("VKX_FUSED_PHASES"); return e ? atoi(e) : 0; }();
+    static const int phase_limit = vkx_env_int("VKX_FUSED_PHASES", 0);
     const ItemDev *items = p->d_items + first;
     const TileBin *bins = p->bins + (size_t)first * p->slots;      // bins are laid out [image][slot]
     if (p->elements) {
@@ -1530,8 +1530,7 @@ int vkx_chain_plan_tiles(vkx_ctx *ctx, vkx_chain_plan *p, int first, int count)
         // about 3 ms of kernel, i.e. 85 pages of 2048^2 = 100 000 tiles.  VKX_CHAIN_SPLIT=0 / 1 forces one way (profiling at small batches).
         constexpr long long kSplitMinTiles = 65536;
         // (read at every call: the tests of the split kernels set it around their small batches)
-        const char *split_e = getenv("VKX_CHAIN_SPLIT");
-        const int split_env = split_e && split_e[0] ? (split_e[0] == '0' ? 0 : 1) : -1;
+        const int split_env = vkx_env_on("VKX_CHAIN_SPLIT", -1);
         if (split_env >= 0 ? split_env == 0 : all_tiles < kSplitMinTiles) {
             const dim3 grid(p->slots, count);
             if (p->streak) k_chain_fused_whole<true><<<grid, NTHREADS, kFusedLds, ctx->stream>>>(items, p->cells, bins, p->lut, phase_limit);
@@ -1664,7 +1663,7 @@ int vkx_chain_plan_setup_aside(vkx_ctx *ctx, vkx_chain_plan *p, hipEvent_t *done
     // compute stream: the events that order two streams cost more than the setup of one image (tens of microseconds), and cross-stream events between a
     // lane's copies and kernels serialise the two copy directions on this stack (tools/pipe_probe2.py) -- with every lane's setup aside the pipeline's
     // chain legs ran at half their rate (device noise 8.5 -> 4.1 Gpx/s; found in the round-5 records, profiles/r5a .. r5j `dropin`).
-    static const int aside_env = [] { const char *e = getenv("VKX_CHAIN_SETUP_ASIDE"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+    static const int aside_env = vkx_env_on("VKX_CHAIN_SETUP_ASIDE", -1);
     constexpr size_t kAsideMinItems = 16;
     const bool aside = aside_env >= 0 ? aside_env != 0 : p->dev.size() >= kAsideMinItems;
     *done = nullptr;

@@ -315,7 +315,7 @@ VKX_EXPORT int vkx_grid_remap_dev(vkx_ctx *ctx, const vkx_elem *elems, int n_ele
     if (int rc = vkx_check_elems(elems, n_elems, sh, sw, dh, dw)) return rc;
     // tile kernel first (ownership in LDS, one launch for all elements); the global-ownership-plane kernels below take
     // whatever it declines (VKX_GRID_GLOBAL=1 forces them: the two paths must agree bit for bit)
-    static const bool force_global = getenv("VKX_GRID_GLOBAL") != nullptr;
+    static const bool force_global = vkx_env_on("VKX_GRID_GLOBAL", 0);
     int rc = force_global ? VKX_ERR_UNSUPPORTED
                           : vkx_tile_remap_try(ctx, elems, n_elems, sh, sw, src_vertices, dst_vertices, rows, cols, dh, dw);
     if (rc != VKX_ERR_UNSUPPORTED) return rc;

@@ -282,7 +282,7 @@ VKX_EXPORT int vkx_fill_u8_dev_host_layers(vkx_ctx *ctx, uint8_t *dst_dev, int h
     // a page's worth (MBs) is copied to device memory by a DMA engine (commit(): one copy out of the ring) and read from HBM: the
     // composite kernel holding CUs for 0.6 ms while 16 MB cross the link was the largest kernel of a page (profiles/r6c_page_dispatches.txt)
     // and, with several workers on the GPU, compute-queue time is what the workers share.  VKX_LAYERS_MAPPED=1 / 0 forces one way.
-    static const int map_env = [] { const char *e = getenv("VKX_LAYERS_MAPPED"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+    static const int map_env = vkx_env_on("VKX_LAYERS_MAPPED", -1);
     const bool mapped = map_env >= 0 ? map_env != 0 : st.total_bytes() <= ((size_t)64 << 10);
     if (!mapped || !st.commit_mapped()) VKX_TRY(st.commit(true));
     auto composite = [&] {

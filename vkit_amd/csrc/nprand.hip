@@ -17,13 +17,17 @@
 // rounds / tiles only one number travels: how many leading positions the previous attempt already consumed.
 //
 //   k_np_tile_states  one lane per tile: LCG state at the tile's first draw (binary jump with the constant powers of A)
-//   k_np_scan         pass 1, one wavefront per tile of 64 * kRounds draws, assuming no carry-in: number of samples the
-//                     tile emits, its carry-out, and the start / emit masks of its first round
+//   the draw pass     pass 1, one wavefront per tile of 64 * kRounds draws, assuming no carry-in: number of samples the
+//                     tile emits, its carry-out, and the start / emit masks of its first round.  The three int16 kinds
+//                     (k_np_draw_compact) leave the tile's samples squeezed together in the tile's slot; speckle, the one
+//                     float64 kind (k_np_draw), records what every raw draw would emit and the emit masks of every round
 //   k_np_resolve      one workgroup per stream: a tile's carry-in is its predecessor's carry-out; when that position is a
 //                     start of the tile's speculative chain (all but ~2e-4 of the tiles) the chain merges there and count
 //                     and carry-out follow from pass 1's masks; the rare other tiles are re-simulated in order by one
 //                     wavefront; then an exclusive scan of the counts = the index of every tile's first sample
-//   k_np_emit         pass 2, same walk with the true carry-in, samples written at their final index
+//   pass 2            the samples go to their final index: a copy out of the slots (k_np_apply; nothing for tile buffers,
+//                     whose reader takes the slots), or the placement of speckle's raw-draw records by rank (k_np_place)
+//   k_np_place_walk   the few tiles pass 2 leaves out, walked again with the true carry-in, samples written at their final index
 //
 // libm: the wedge test compares against exp(), the tail draws go through log1p().  The device versions are within an
 // ulp or two of glibc's, not identical; every decision and every emitted integer that could depend on those last bits
@@ -306,8 +310,8 @@ __device__ __forceinline__ void tile_lane_states(const JumpTabs &g_jump, const N
 //            round with one active lane
 //   phase 3  per round: the scalar walk over the multi-draw attempts that gives the true starts, then the emission
 //   MODE kCount   the walk only: samples the tile yields and its carry-out for the given carry-in
-//   MODE kRecord  carry-in 0: besides the count, what every draw would emit (`rec_val`, 1024 per tile, in draw order) and
-//                 the 16 emit masks (`rec_mask`) go to global memory for k_np_place
+//   MODE kRecord  carry-in 0: besides the count, what every draw would emit (`rec_val`, kTile per tile, in draw order) and
+//                 the kRounds emit masks (`rec_mask`) go to global memory for k_np_place (speckle)
 //   MODE kEmit    the samples are stored at their final index of `emit_dst`
 //   MODE kCompact carry-in 0: the samples the tile yields, squeezed together in LDS, go to the tile's slot `rec_val` as whole
 //                 16-byte groups (int16 emitters; the consumer drops the leading samples a carry-in takes away)
@@ -1003,14 +1007,19 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
     }
 }
 
-// The fast path of pass 2 for one tile: m = (lane r < 16) the emit mask of round r.
-// Element-granular version (speckle: float64 records, byte traffic; a rare single-image operator).
+// Pass 2 leaves some tiles to k_np_place_walk, which walks them again from the generator state: tiles whose carry-in does not
+// merge into the recorded chain (~2e-4 of them), the tile holding a job's last sample (its draw count is reported) and, for
+// emitters that check a tail sample against its pixel, tiles with a tail sample.
+__device__ __forceinline__ bool tile_needs_walk(const NpJob &job, const TilePlan &p, uint32_t out0, bool check_at_store)
+{
+    return (p.c_in & kIrregular) || (long long)p.prefix + p.count >= job.n || (check_at_store && (out0 >> 31));
+}
+
+// Pass 2 of the one kind that records raw draws, speckle (float64 records, byte traffic; a rare single-image operator): the
+// recorded draws of a tile go to their final index, one wavefront per tile, nothing but the tile's records, masks and plan
+// to read.  m = (lane r < kRounds) the emit mask of round r; a sample's index is the tile's prefix plus its rank among them.
 template <class Emit>
-struct Placer {
-    struct Draws {};
-    __device__ static Draws load(const typename Emit::Store *) { return Draws(); }
-    __device__ static void place(const NpJob &job, const Draws &, const typename Emit::Store *__restrict__ rec, uint64_t m, long long prefix,
-                                 typename Emit::Store *, uint32_t &flags)
+__device__ __forceinline__ void place_tile(const NpJob &job, const typename Emit::Store *__restrict__ rec, uint64_t m, long long prefix, uint32_t &flags)
 {
     const typename Emit::Store VKX_GLOBAL *vals = (const typename Emit::Store VKX_GLOBAL *)rec;
     const int lane = __lane_id();
@@ -1024,168 +1033,6 @@ struct Placer {
         count += (uint32_t)__builtin_popcountll(emits);
     }
 }
-};
-
-// int16 records: sub-dword global accesses cost the texture path one lane per cycle, so the records are read as dwords
-// (two consecutive draws per lane), compacted into LDS at their rank, and leave as whole dwords.
-// `shift` = (index of the tile's first sample) mod (elements per dword): LDS slot i holds element (prefix - shift) + i.
-struct TileDraws { uint32_t v[kRounds / 2]; };     // lane l: draws 128 q + 2 l, + 1 of the tile as int16 pairs
-__device__ __forceinline__ TileDraws load_tile_i16(const int16_t *__restrict__ rec)
-{
-    const uint32_t VKX_GLOBAL *vals = (const uint32_t VKX_GLOBAL *)rec;
-    const int lane = __lane_id();
-    TileDraws d;
-#pragma unroll
-    for (int q = 0; q < kRounds / 2; q++) d.v[q] = vals[64 * q + lane];
-    return d;
-}
-// The compaction, with the records parked in the staging row first (8 elements further up, so that a rank -- at most
-// shift + position, shift < 8 -- never overtakes a record that has not been read): per round two v_readlane (the round's mask
-// lives in lane r), two v_mbcnt whose addend carries the running count, one address op, a 2-byte LDS read and a write that is
-// masked through exec instead of a per-lane bit test -- a quarter of the VALU instructions of a compaction out of registers
-// (rank of each of a lane's two draws by popcounts and selects), in a pass that shares the SIMDs with the draw pass of the
-// next chunk.
-constexpr int kRawOff = 8;
-__device__ __forceinline__ uint32_t stage_tile_lds(const TileDraws &d, uint64_t m, uint32_t shift, int16_t *st)
-{
-    const uint32_t lane = (uint32_t)__lane_id();
-    uint32_t *raw32 = (uint32_t *)(st + kRawOff);
-#pragma unroll
-    for (int q = 0; q < kRounds / 2; q++) raw32[64 * q + lane] = d.v[q];
-    __builtin_amdgcn_wave_barrier();
-    const int16_t *raw = st + kRawOff;
-    const uint32_t st_addr = lds_offset(st);
-    uint32_t run = shift;
-#pragma unroll
-    for (int r = 0; r < kRounds; r++) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)m, r), hi = (uint32_t)__builtin_amdgcn_readlane((int)(m >> 32), r);
-        const uint32_t rank = (uint32_t)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, run));
-        const uint32_t v = (uint16_t)raw[64 * r + lane];
-        const uint32_t addr = st_addr + 2 * rank;
-        const uint64_t mask = ((uint64_t)hi << 32) | lo;
-        uint64_t saved;
-        asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\tds_write_b16 %[a], %[v]\n\ts_mov_b64 exec, %[sv]"
-                     : [sv] "=&s"(saved) : [m] "s"(mask), [a] "v"(addr), [v] "v"(v) : "memory");
-        run += (uint32_t)__builtin_popcountll(mask);
-    }
-    __builtin_amdgcn_wave_barrier();
-    return run - shift;
-}
-
-
-template <>
-struct Placer<EmitI16> {
-    typedef TileDraws Draws;
-    __device__ static Draws load(const int16_t *rec) { return load_tile_i16(rec); }
-    __device__ static void place(const NpJob &job, const Draws &d, const int16_t *, uint64_t m, long long prefix, int16_t *st, uint32_t &)
-{
-    const uint32_t shift = (uint32_t)prefix & 1u;
-    uint32_t total = stage_tile_lds(d, m, shift, st);
-    if (prefix + total > job.n) total = (uint32_t)(job.n - prefix);
-    finish(job, total, shift, prefix, st);
-}
-    // slots [shift, shift + total) of `st` hold the tile's samples: whole dwords to dst[prefix ...]
-    __device__ static void finish(const NpJob &job, uint32_t total, uint32_t shift, long long prefix, int16_t *st)
-{
-    const uint32_t lane = (uint32_t)__lane_id();
-    int16_t VKX_GLOBAL *dst = (int16_t VKX_GLOBAL *)job.dst + (prefix - shift);
-    const uint32_t end = shift + total;                // slots [shift, end) are valid
-    const uint32_t full_hi = end >> 1;                 // dwords [shift, full_hi) are whole
-    uint32_t VKX_GLOBAL *dst32 = (uint32_t VKX_GLOBAL *)dst + lane;
-    const uint32_t *st32 = (const uint32_t *)st + lane;
-    if (lane >= shift && lane < full_hi) dst32[0] = st32[0];
-#pragma unroll
-    for (uint32_t i = 1; i < kTile / 128; i++)
-        if (lane + 64 * i < full_hi) dst32[64 * i] = st32[64 * i];
-    if (lane == 0) {
-        if (shift && end > 1) dst[1] = st[1];
-        if ((end & 1) && end - 1 >= shift) dst[end - 1] = st[end - 1];
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-};
-
-template <>
-struct Placer<EmitAddU8> {
-    typedef TileDraws Draws;
-    __device__ static Draws load(const int16_t *rec) { return load_tile_i16(rec); }
-    __device__ static void place(const NpJob &job, const Draws &d, const int16_t *, uint64_t m, long long prefix, int16_t *st, uint32_t &)
-{
-    const uint32_t shift = (uint32_t)prefix & 3u;
-    // the pixels the tile's samples go onto are requested before the samples are compacted: their latency hides behind
-    // the staging (every whole dword of the plane that the tile can reach; what the count leaves unused is dropped)
-    const uint32_t lane = (uint32_t)__lane_id();
-    const long long first = prefix - shift;
-    const uint32_t VKX_GLOBAL *src32 = (const uint32_t VKX_GLOBAL *)((const uint8_t VKX_GLOBAL *)job.src + first) + lane;
-    uint32_t px[kTile / 256];
-#pragma unroll
-    for (uint32_t i = 0; i < kTile / 256; i++) {      // shift + total <= 1027: whole dwords 0 .. 255
-        px[i] = 0;
-        if (first + 4 * (long long)(lane + 64 * i) + 3 < job.n) px[i] = src32[64 * i];
-    }
-    uint32_t total = stage_tile_lds(d, m, shift, st);
-    if (prefix + total > job.n) total = (uint32_t)(job.n - prefix);
-    finish_px(job, total, shift, prefix, st, px);
-}
-    __device__ static void finish(const NpJob &job, uint32_t total, uint32_t shift, long long prefix, int16_t *st)
-{
-    const uint32_t lane = (uint32_t)__lane_id();
-    const long long first = prefix - shift;
-    const uint32_t VKX_GLOBAL *src32 = (const uint32_t VKX_GLOBAL *)((const uint8_t VKX_GLOBAL *)job.src + first) + lane;
-    uint32_t px[kTile / 256];
-#pragma unroll
-    for (uint32_t i = 0; i < kTile / 256; i++) {      // shift + total <= 1027: whole dwords 0 .. 255
-        px[i] = 0;
-        if (first + 4 * (long long)(lane + 64 * i) + 3 < job.n) px[i] = src32[64 * i];
-    }
-    finish_px(job, total, shift, prefix, st, px);
-}
-    __device__ static void finish_px(const NpJob &job, uint32_t total, uint32_t shift, long long prefix, int16_t *st,
-                                     const uint32_t (&pxs)[kTile / 256])
-{
-    typedef short pk16 __attribute__((ext_vector_type(2)));
-    const uint32_t lane = (uint32_t)__lane_id();
-    const uint8_t VKX_GLOBAL *src = (const uint8_t VKX_GLOBAL *)job.src + (prefix - shift);
-    uint8_t VKX_GLOBAL *dst = (uint8_t VKX_GLOBAL *)job.dst + (prefix - shift);
-    const uint32_t end = shift + total;
-    const uint32_t full_lo = (shift + 3) >> 2, full_hi = end >> 2;      // dwords [full_lo, full_hi) are whole
-    uint32_t VKX_GLOBAL *dst32 = (uint32_t VKX_GLOBAL *)dst + lane;
-    const uint2 *st64 = (const uint2 *)st + lane;
-    auto whole = [&](uint32_t i) {
-        const uint32_t px = pxs[i];
-        const uint2 nz = st64[64 * i];
-        // bytes 0 1 | 2 3 of the pixel dword as int16 pairs, + noise, clamp, repack
-        pk16 lo = __builtin_bit_cast(pk16, __builtin_amdgcn_perm(0u, px, 0x0c010c00u));
-        pk16 hi = __builtin_bit_cast(pk16, __builtin_amdgcn_perm(0u, px, 0x0c030c02u));
-        lo += __builtin_bit_cast(pk16, nz.x);
-        hi += __builtin_bit_cast(pk16, nz.y);
-        const pk16 zero = {0, 0}, top = {255, 255};
-        lo = __builtin_elementwise_min(__builtin_elementwise_max(lo, zero), top);
-        hi = __builtin_elementwise_min(__builtin_elementwise_max(hi, zero), top);
-        dst32[64 * i] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x06040200u);
-    };
-    if (lane >= full_lo && lane < full_hi) whole(0);
-#pragma unroll
-    for (uint32_t i = 1; i < kTile / 256; i++)
-        if (lane + 64 * i < full_hi) whole(i);
-    // the bytes of the partial dwords at both ends
-    if (lane < 8) {
-        const uint32_t e = lane < 4 ? lane : 4 * full_hi + (lane - 4);
-        const bool mine = lane < 4 ? (shift > 0 && e >= shift && e < end) : (e < end && !(full_hi == 0 && shift > 0));
-        if (mine) dst[e] = (uint8_t)vkd::clamp_u8((int16_t)((int)src[e] + (int)st[e]));
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-};
-
-// Pass 2: the recorded draws of a tile go to their final index (k_np_place, one wavefront per tile, nothing but the
-// tile's records, masks and plan to read).  Tiles whose carry-in does not merge into the recorded chain (~2e-4 of them),
-// the tile holding a job's last sample (its draw count is reported) and, for emitters that check a tail sample against
-// its pixel, tiles with a tail sample are left to k_np_place_walk, which walks them again from the generator state.
-__device__ __forceinline__ bool tile_needs_walk(const NpJob &job, const TilePlan &p, uint32_t out0, bool check_at_store)
-{
-    return (p.c_in & kIrregular) || (long long)p.prefix + p.count >= job.n || (check_at_store && (out0 >> 31));
-}
 
 template <class Emit>
 __global__ void __launch_bounds__(256) k_np_place(const NpJob *__restrict__ jobs, int n_jobs, long long total_tiles,
@@ -1193,14 +1040,13 @@ __global__ void __launch_bounds__(256) k_np_place(const NpJob *__restrict__ jobs
                                                   const typename Emit::Store *__restrict__ rec_val, const uint64_t *__restrict__ rec_mask,
                                                   vkx_np_result *__restrict__ results)
 {
-    __shared__ __attribute__((aligned(16))) typename Emit::Store stage[4][kTile + 64];
     const int lane = __lane_id();
     const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= total_tiles) return;
-    // everything the tile reads is requested before the plan decides (one memory round trip per tile)
+    // the plan, the masks and the tile's info are requested together, before the plan decides
     const TilePlan p = plan[tile];
     uint64_t m = lane < kRounds ? ((const uint64_t VKX_GLOBAL *)rec_mask)[tile * kRounds + lane] : 0ull;
-    const typename Placer<Emit>::Draws draws = Placer<Emit>::load(rec_val + tile * kTile);
+    const typename Emit::Store *rec = rec_val + tile * kTile;
     const uint32_t out0 = Emit::kCheckAtStore ? info[tile].out0 : 0u;
     const int j = job_of_tile(jobs, n_jobs, tile);
     const NpJob &job = jobs[j];
@@ -1213,7 +1059,7 @@ __global__ void __launch_bounds__(256) k_np_place(const NpJob *__restrict__ jobs
     if (tile_needs_walk(job, pu, (uint32_t)__builtin_amdgcn_readfirstlane((int)out0), Emit::kCheckAtStore)) return;
     uint32_t flags = 0;
     if (lane == 0) m &= ~((1ull << pu.c_in) - 1);     // c_in < 64 is a start of the recorded chain: the draws before it belong to the previous tile
-    Placer<Emit>::place(job, draws, rec_val + tile * kTile, m, prefix, stage[threadIdx.x >> 6], flags);
+    place_tile<Emit>(job, rec, m, prefix, flags);
     if (flags) atomicOr(&results[j].flags, flags);
 }
 
@@ -1495,11 +1341,10 @@ VKX_EXPORT int vkx_np_tiles_layout(int64_t n, int64_t *n_tiles, int64_t *slot_el
     return VKX_OK;
 }
 
-// VKX_NP_COMPACT=0: the int16 kinds through the raw-draw records and the placement pass of round 3 (A/B).
+// The three int16 kinds leave the draw pass as compacted tile slots; speckle records raw draws for the placement pass.
 static bool np_compact_records(int kind)
 {
-    static const bool on = [] { const char *e = getenv("VKX_NP_COMPACT"); return !(e && e[0] == '0'); }();
-    return kind == VKX_NP_NORMAL_TILES || (on && (kind == VKX_NP_NORMAL_I16 || kind == VKX_NP_NORMAL_ADD_U8));
+    return kind == VKX_NP_NORMAL_TILES || kind == VKX_NP_NORMAL_I16 || kind == VKX_NP_NORMAL_ADD_U8;
 }
 
 // One chunk of a call: its tile arrays in one of the two scratch slots, its jobs, its slice of the results.
@@ -1530,10 +1375,12 @@ static int np_chunk_prepare(vkx_ctx *ctx, NpChunk &c)
     c.o_states = take((size_t)c.total_tiles * 16);
     c.o_info = take(uniform ? 0 : (size_t)c.total_tiles * sizeof(TileInfo));
     c.o_plan = take(uniform ? 0 : (size_t)c.total_tiles * sizeof(TilePlan));
-    const size_t val_bytes = c.kind == VKX_NP_SPECKLE_U8 ? 8 : 2;
-    const bool compact = !uniform && np_compact_records(c.kind);
-    c.o_rmask = take(uniform || compact ? 0 : (size_t)c.total_tiles * kRounds * 8);
-    c.o_rval = take(uniform || c.kind == VKX_NP_NORMAL_TILES ? 0 : (size_t)c.total_tiles * (compact ? kSlot : kTile) * val_bytes);
+    // speckle alone records raw draws: a float64 per draw and the emit masks of every round; the two int16 kinds that own
+    // no tile buffer keep their slots here
+    const bool speckle = c.kind == VKX_NP_SPECKLE_U8;
+    const bool slots = c.kind == VKX_NP_NORMAL_I16 || c.kind == VKX_NP_NORMAL_ADD_U8;
+    c.o_rmask = take(speckle ? (size_t)c.total_tiles * kRounds * 8 : 0);
+    c.o_rval = take(speckle ? (size_t)c.total_tiles * kTile * 8 : slots ? (size_t)c.total_tiles * kSlot * 2 : 0);
     c.o_jobs = take((size_t)c.n_jobs * sizeof(NpJob));
     c.o_results = take((size_t)c.n_jobs * sizeof(vkx_np_result) + sizeof(unsigned));    // + the completion counter
     int rc = vkx_scratch_reserve(ctx, &ctx->np_work[c.slot], off);
@@ -1577,7 +1424,7 @@ static int np_chunk_prepare(vkx_ctx *ctx, NpChunk &c)
             const vkx_np_tiles_shape shape = vkx_np_tiles_shape_of(j.n);
             d.rec = (int16_t *)((unsigned char *)j.dst + shape.slots_offset);
             d.table = (uint2 *)((unsigned char *)j.dst + shape.table_offset);
-        } else if (compact) {
+        } else if (slots) {
             d.rec = (int16_t *)(c.base + c.o_rval) + d.tile_base * kSlot;
         }
     }
@@ -1609,8 +1456,8 @@ static int np_chunk_front(vkx_ctx *ctx, NpChunk &c)
     // (round 5, swept again under the joint call: 1 / 2 / 4 tiles per wavefront draw ONE 2048^2 plane in 0.050 / 0.064 / 0.083 ms, four planes in 0.132 /
     //  0.139 / 0.172, sixteen in 0.475 / 0.466 / 0.471, and the bench's chunk of 128 planes -- with the step's small kernels under it -- in 3.79 / 3.67 / 3.63:
     //  the step 16.77 / 16.52 / 16.41 ms; 8 and 12: 16.55 / 16.60)
-    static const int tpw_env = [] { const char *e = getenv("VKX_NP_TPW"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
-    const int tiles_per_wave = tpw_env ? tpw_env : (total_tiles >= 160000 ? 4 : total_tiles >= 40000 ? 2 : 1);
+    static const int tpw_env = vkx_env_int("VKX_NP_TPW", 0);
+    const int tiles_per_wave = tpw_env > 0 ? tpw_env : (total_tiles >= 160000 ? 4 : total_tiles >= 40000 ? 2 : 1);
     const unsigned wg = (unsigned)((total_tiles + 4 * tiles_per_wave - 1) / (4 * tiles_per_wave));
     {
         VKX_TIMED(ctx, "k_np_tile_states");
@@ -1635,15 +1482,10 @@ static int np_chunk_front(vkx_ctx *ctx, NpChunk &c)
         VKX_LAUNCH_CHECK();
         return VKX_OK;
     }
-    uint64_t *rmask = (uint64_t *)(base + c.o_rmask);
-    void *rval = base + c.o_rval;
+    // speckle: raw-draw records and emit masks for k_np_place
     VKX_TIMED_MAJOR(ctx, "k_np_draw");
-    if (kind == VKX_NP_SPECKLE_U8)
-        k_np_draw<EmitSpeckle><<<wg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, states, info, (double *)rval, rmask, res, tabs);
-    else if (kind == VKX_NP_NORMAL_ADD_U8)
-        k_np_draw<EmitAddU8><<<wg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, states, info, (int16_t *)rval, rmask, res, tabs);
-    else
-        k_np_draw<EmitI16><<<wg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, states, info, (int16_t *)rval, rmask, res, tabs);
+    k_np_draw<EmitSpeckle><<<wg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, states, info, (double *)(base + c.o_rval),
+                                                        (uint64_t *)(base + c.o_rmask), res, tabs);
     VKX_LAUNCH_CHECK();
     return VKX_OK;
 }
@@ -1663,8 +1505,6 @@ static int np_chunk_back(vkx_ctx *ctx, NpChunk &c)
     TilePlan *plan = (TilePlan *)(base + c.o_plan);
     vkx_np_result *res = (vkx_np_result *)(base + c.o_results);
     unsigned *done = (unsigned *)(res + c.n_jobs);
-    uint64_t *rmask = (uint64_t *)(base + c.o_rmask);
-    void *rval = base + c.o_rval;
     const long long total_tiles = c.total_tiles;
     const int n_jobs = c.n_jobs, kind = c.kind;
     const NpTabs *tabs = c.tabs;
@@ -1674,23 +1514,16 @@ static int np_chunk_back(vkx_ctx *ctx, NpChunk &c)
         k_np_resolve<<<n_jobs, 1024, bits, ctx->stream>>>(dj, states, info, plan, res, tabs);
         VKX_LAUNCH_CHECK();
     }
-    if (np_compact_records(kind)) {
-        const unsigned pg = vkx_blocks((size_t)total_tiles, 4);
-        if (kind != VKX_NP_NORMAL_TILES) {
-            VKX_TIMED(ctx, "k_np_apply");
-            if (kind == VKX_NP_NORMAL_ADD_U8) k_np_apply<true><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan);
-            else k_np_apply<false><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan);
-            VKX_LAUNCH_CHECK();
-        }
-    } else {
+    const unsigned pg = vkx_blocks((size_t)total_tiles, 4);
+    if (!np_compact_records(kind)) {
         VKX_TIMED(ctx, "k_np_place");
-        const unsigned pg = vkx_blocks((size_t)total_tiles, 4);
-        if (kind == VKX_NP_SPECKLE_U8)
-            k_np_place<EmitSpeckle><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan, (const double *)rval, rmask, res);
-        else if (kind == VKX_NP_NORMAL_ADD_U8)
-            k_np_place<EmitAddU8><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan, (const int16_t *)rval, rmask, res);
-        else
-            k_np_place<EmitI16><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan, (const int16_t *)rval, rmask, res);
+        k_np_place<EmitSpeckle><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan, (const double *)(base + c.o_rval),
+                                                             (const uint64_t *)(base + c.o_rmask), res);
+        VKX_LAUNCH_CHECK();
+    } else if (kind != VKX_NP_NORMAL_TILES) {
+        VKX_TIMED(ctx, "k_np_apply");
+        if (kind == VKX_NP_NORMAL_ADD_U8) k_np_apply<true><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan);
+        else k_np_apply<false><<<pg, 256, 0, ctx->stream>>>(dj, n_jobs, total_tiles, info, plan);
         VKX_LAUNCH_CHECK();
     }
     {
@@ -1806,9 +1639,8 @@ VKX_EXPORT int vkx_np_draw_batch_dev(vkx_ctx *ctx, const vkx_np_job *jobs, int n
     const NpTabs *tabs = nullptr;
     if ((rc = np_tables(ctx, &tabs))) return rc;
     vkx_device_guard guard(ctx);
-    static const bool pipelined = [] { const char *e = getenv("VKX_NP_PIPELINE"); return !(e && e[0] == '0'); }();
     // (tile buffers: what follows the draw pass is a few microseconds per stream and no scratch grows with the records -- one chunk)
-    const int n_chunks = (!uniform && pipelined && kind != VKX_NP_NORMAL_TILES && n_jobs >= 2 * kChunkJobs) ? (n_jobs + kChunkJobs - 1) / kChunkJobs : 1;
+    const int n_chunks = (!uniform && kind != VKX_NP_NORMAL_TILES && n_jobs >= 2 * kChunkJobs) ? (n_jobs + kChunkJobs - 1) / kChunkJobs : 1;
     auto chunk_of = [&](int k, NpChunk &c) {
         const int per = (n_jobs + n_chunks - 1) / n_chunks, first = k * per;
         c.jobs = jobs + first;

@@ -835,7 +835,7 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
     long long *d_bpos = (long long *)(work + o_bpos), *d_pos = (long long *)(work + o_pos);
     PzReply *d_reply = (PzReply *)(work + o_reply);
     unsigned *d_counter = (unsigned *)(work + o_counter);
-    static const bool probing = getenv("VKX_PZ_PROBE") != nullptr;       // phase timestamps of every superblock (tools/poisson_probe.py)
+    static const bool probing = vkx_env_on("VKX_PZ_PROBE", 0);      // phase timestamps of every superblock (tools/poisson_probe.py)
     long long *d_probe = nullptr;
 
     const auto t_begin = std::chrono::steady_clock::now();
@@ -859,13 +859,11 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
     // relative to the start of the superblock d - 1 before, so that the tables and walks of d superblocks are in flight and a chain runs
     // under the tables of the next d - 1.  Wider windows are the price -- sqrt(d) more table states --, so dark images (the multiplication
     // method: a variance of lam per element against PTRS's 0.7 - 1.8) stay at depth 1.  VKX_PZ_DEPTH overrides.
-    static const int depth_env = getenv("VKX_PZ_DEPTH") ? std::max(1, std::min(3, atoi(getenv("VKX_PZ_DEPTH")))) : 0;
+    static const int depth_env = std::max(0, std::min(3, vkx_env_int("VKX_PZ_DEPTH", 0)));     // 0: not set
     double var_sum = 0.0;
     for (long long b = 0; b < n_blk; b++) var_sum += bvar[(size_t)b];
     const double var_per_element = var_sum / (double)n;
     const int depth = depth_env ? depth_env : (var_per_element > 7.0 ? 1 : 2);
-    static const int max_blocks_env = getenv("VKX_PZ_BLOCKS") ? std::max(16, std::min(kMaxBlocks, atoi(getenv("VKX_PZ_BLOCKS")))) : 0;
-    const int max_blocks = max_blocks_env ? max_blocks_env : kMaxBlocks;
     std::vector<std::pair<double, double>> before;         // (mean, variance) of the depth - 1 superblocks before this one
     static thread_local std::vector<PzBlock> plan;
     static thread_local std::vector<PzSuper> supers;
@@ -882,7 +880,7 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
         long long e_off = 0;
         int max_band = 0, last_W = 1;
         long long j = s0;
-        for (; j < n_blk && j - s0 < max_blocks; j++) {
+        for (; j < n_blk && j - s0 < kMaxBlocks; j++) {
             const bool exact = j == s0 && base_v == 0.0 && base_m == 0.0 && supers.empty();      // the stream's own start
             const int H = (j == s0 && depth == 1) || exact ? 0 : (int)ceil(sigmas * sqrt(base_v + cv)) + 3;
             const int W = 2 * H + 1;
@@ -939,14 +937,9 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
     // block of a superblock starts when most light ones are done and the superblock's chain waits a whole table pass for it.
     static thread_local std::vector<int> order;
     order.resize((size_t)n_blk);
-    static const bool heavy_first = !(getenv("VKX_PZ_ORDER") && atoi(getenv("VKX_PZ_ORDER")) == 0);
     // (a counting sort by table rows, more rows first; among equals the later block first: its window, hence its band, is the wider)
     for (const PzSuper &S : supers) {
         int *o = order.data() + S.first_block;
-        if (!heavy_first) {
-            for (int b = 0; b < S.n_blocks; b++) o[b] = S.first_block + b;
-            continue;
-        }
         int start[kB + 2];
         for (int r = 0; r <= kB + 1; r++) start[r] = 0;
         for (int b = 0; b < S.n_blocks; b++) start[kB - std::min(kB, (int)brows[(size_t)(S.first_block + b)]) + 1]++;
@@ -988,9 +981,8 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = 256;
             return v;
         }();
-        static const int grid_env = getenv("VKX_PZ_GRID") ? atoi(getenv("VKX_PZ_GRID")) : 0;      // fewer workgroups than CUs: every wait of the kernel is exercised
-        static const int g_global = getenv("VKX_PZ_G_GLOBAL") ? atoi(getenv("VKX_PZ_G_GLOBAL")) : 0;
-        static const int resolve_rows = getenv("VKX_PZ_RESOLVE_ROWS") ? atoi(getenv("VKX_PZ_RESOLVE_ROWS")) : kResolveRows;
+        static const int grid_env = vkx_env_int("VKX_PZ_GRID", 0);      // fewer workgroups than CUs: every wait of the kernel is exercised
+        static const int g_global = vkx_env_int("VKX_PZ_G_GLOBAL", 0);
         // By default the kernel leaves one CU in eight alone (VKX_PZ_GRID=<CUs> takes them all).  Its workgroups are persistent, hold ~150
         // of a CU's 160 KB of LDS and spin on each other's published positions for 7 - 9 ms per page: with every CU taken, the kernels of the
         // OTHER worker processes sharing the GPU (the reference scales by processes) wait that long for a slot.  Measured with 8 workers on
@@ -1000,7 +992,7 @@ VKX_EXPORT int vkx_np_poisson_u8_dev(vkx_ctx *ctx, const uint64_t *state, const 
         const int grid = (int)std::min<long long>(n_blk, grid_env > 0 ? grid_env : grid_default);
         VKX_TIMED(ctx, "k_pz_super");
         k_pz_super<<<grid, kCandThreads, 0, ctx->stream>>>(src, n, (int)n_blk, d_order, d_plan, d_sup, d_pos, d_draws, M, tabs, d_E, d_P, d_G, (long long)e_stride, d_bpos,
-                                                          d_ticket, d_grpcnt, d_supcnt, d_done, &d_reply->fail, d_probe, g_global, resolve_rows);
+                                                          d_ticket, d_grpcnt, d_supcnt, d_done, &d_reply->fail, d_probe, g_global, kResolveRows);
     }
     VKX_LAUNCH_CHECK();
     { VKX_TIMED(ctx, "k_pz_final");

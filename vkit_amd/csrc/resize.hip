@@ -403,7 +403,7 @@ __global__ void __launch_bounds__(256) k_resize_sep(const T *__restrict__ src, i
 // the most source rows a tile of the separable form needs; 0: more than kSepRows somewhere (the direct kernels take the call)
 int separable_rows(const std::vector<int> &yofs, int sh, int dh, int ks)
 {
-    static const bool force_direct = getenv("VKX_RESIZE_DIRECT") != nullptr;   // parity aid: the two forms must agree
+    static const bool force_direct = vkx_env_on("VKX_RESIZE_DIRECT", 0);   // parity aid: the two forms must agree
     if (force_direct) return 0;
     const int left = ks / 2 - 1;
     auto clip = [sh](int v) { return v < 0 ? 0 : (v >= sh ? sh - 1 : v); };

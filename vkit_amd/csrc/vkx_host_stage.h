@@ -58,12 +58,11 @@ public:
         // has queued (the staging block may still be read) and before what it queues next.  In line on the compute stream, behind
         // kernels, the runtime executes the copy as a copy KERNEL (8 MB: 0.2 ms of the compute queue per page); on a stream of its own it
         // goes to a DMA engine: kernel time per C4 page 0.74 -> 0.52 ms, eight workers sharing the GPU 1 202 -> 1 563 pages/s
-        // (profiles/r6h0_ / r6h1_page_dispatches.txt).  VKX_STAGE_COPY_STREAM=0 keeps it in line.
-        static const bool aside = [] { const char *e = getenv("VKX_STAGE_COPY_STREAM"); return !(e && e[0] == '0'); }();
+        // (profiles/r6h0_ / r6h1_page_dispatches.txt).
         hipStream_t copy_stream = ctx_->stream;
         // (only for calls that return without reading anything back: behind a synchronous call -- similarity_mls.distort on one 2048^2
         //  image -- the DMA engine's start-up latency is what the caller waits for: 1.5 -> 2.1 ms per call)
-        if (aside && copy_aside && ring && in_total >= ((size_t)256 << 10)) {
+        if (copy_aside && ring && in_total >= ((size_t)256 << 10)) {
             int src = VKX_OK;
             hipStream_t cs = vkx_stream_by_id(ctx_, VKX_STREAM_COPY_IN, &src);
             if (src == VKX_OK && cs && vkx_stream_order(ctx_, cs, ctx_->stream) == VKX_OK) copy_stream = cs;

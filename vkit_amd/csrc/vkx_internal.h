@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <limits.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -206,6 +207,12 @@ hipStream_t vkx_stream_by_id(vkx_ctx *ctx, int id, int *rc);
 const void *vkx_ring_device_ptr(const void *ring_host);              // a ring block as kernels address it (mapped host memory), or nullptr
 
 static inline size_t vkx_align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The environment switches of INTEGRATION.md as the library reads them (a site keeps the value in a `static const`: once per process).
+// vkx_env_int: the integer the variable holds, `unset` without it.  vkx_env_on: 0 for a value that begins with '0', 1 for any other,
+// `unset` without the variable (-1 where a site tells "forced off" from "not set").
+static inline int vkx_env_int(const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; }
+static inline int vkx_env_on(const char *name, int unset) { const char *e = getenv(name); return e ? (e[0] == '0' ? 0 : 1) : unset; }
 
 // The small tables a call builds on the host (edge lists, tile bins, descriptors, LUTs) on their way to the device: lay the
 // parts out with add() (each starts on a 256-byte boundary), take() ONE ring block for all of them, write each part where
