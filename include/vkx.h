@@ -1216,6 +1216,49 @@ typedef struct vkx_text_line {
 int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host, int n_chars, const vkx_text_line *lines_host, int n_lines,
                        const void *blob_host, size_t blob_bytes, uint8_t *dst, size_t dst_bytes);
 
+/* ---- text-line labels: quad interpolation and the box masks (element/score_map.py:139-283, :562-588;
+ * pipeline/text_detection/page_text_line_label.py:156-306) ---------------------------------------------------------------------
+ * One HOST record a quad, its vertices point0 .. point3 as ScoreMap.from_quad_interpolation holds them: x / y the rounded
+ * integer vertices in plane coordinates (their extremes are the polygon's bounding box, and moved to its corner they are what
+ * cv.fillPoly rasterises: vkx_fill_poly_mask_u8's raster), sx / sy the float32 NpVec.from_point values of the self-relative
+ * vertices, and which of the two interpolated components the quad stores.
+ * Per pixel (px, py) of the bounding box, the reference's arithmetic as numpy 2 evaluates it: q = (px, py) - vertex 0 in
+ * float64; b1 = v1 - v0, b2 = v3 - v0, b3 = ((v0 - v1) - v3) + v2 and a = b2 x b3 in float32; b = float32(b3 x q - b1 x b2) and
+ * c = float32(b1 x q) from float64 cross products; |a| < 0.001: v = -c / b, else the two roots (-b +- sqrt(b * b - (4a) * c)) *
+ * float32(0.5 / a) in float32, every product, difference, root and quotient rounded once; of the two roots the one that lies in
+ * [0, 1] on more pixels of the quad's raster is kept for the WHOLE quad, the positive one on a tie.  v is clipped to [0, 1];
+ * u = float32((q.x - b2.x * v) / dx) in float64 where |dx| > |dy| and dx != 0 (dx = b1.x + b3.x * v, dy likewise), else the same
+ * from y where dy != 0, else 0, clipped.  Outside the raster both are 0.
+ * vkx_quad_interp_fill_dev: the stored component of every quad, in list order, onto dst (DEVICE float32, dense [h][w]) where
+ * it is > 0 (a NaN never is): VKX_FILL_PLAIN overwrites, VKX_FILL_KEEP_MAX writes where dst < value, VKX_FILL_KEEP_MIN where
+ * dst > value; with VKX_QUAD_FRESH_ONE ORed into mode dst is not read: it counts as 1.0f everywhere before the fills and every
+ * element of it is written (a map born by ScoreMap.from_shape(value=1.0)).  zero_where (optional; DEVICE uint8, dense [h][w]): after the fills dst is 0.0f where it is 0.  At most two
+ * launches whatever n_quads (the count of the roots, then the fill over the tiles of dst), no synchronisation.
+ * vkx_quad_interp_uv_dev: (u, v) of ONE quad over its bounding box, DEVICE float32 dense [bh][bw][2], every element written.
+ * Refused (VKX_ERR_INVALID, nothing launched): a NULL pointer, h or w outside 1 .. 32768, n_quads outside 0 .. 2^24 - 1, an
+ * unknown component or mode, a quad whose bounding box leaves the plane (for the uv form: a side above 32768, or uv_floats
+ * other than 2 * bh * bw), dst and zero_where that overlap. */
+#define VKX_QUAD_U 0
+#define VKX_QUAD_V 1
+#define VKX_QUAD_FRESH_ONE 0x100
+typedef struct vkx_quad {
+    int32_t x[4], y[4];
+    float sx[4], sy[4];
+    int32_t component;                  /* VKX_QUAD_U or VKX_QUAD_V */
+    int32_t reserved[3];
+} vkx_quad;
+int vkx_quad_interp_fill_dev(vkx_ctx *ctx, const vkx_quad *quads_host, int n_quads, int mode, int h, int w, float *dst,
+                             const uint8_t *zero_where);
+int vkx_quad_interp_uv_dev(vkx_ctx *ctx, const vkx_quad *quad_host, float *uv, size_t uv_floats);
+/* The three masks of PageTextLineLabelStep in ONE launch whatever the number of boxes, no synchronisation.  boxes_host: HOST
+ * int32 {up, left, height, width} records, the first n_text the text-line boxes, the next n_dilated the dilated-only boxes.
+ * DEVICE uint8 dense [h][w], every byte written: text_mask = 1 under a text-line box; boundary_mask (optional) = 1 under a
+ * dilated-only box and no text-line box; both_mask (optional) = 1 under either.  Refused: a NULL ctx, text_mask or (with
+ * boxes) table, h or w outside 1 .. 32768, a count outside 0 .. 2^24 - 1, a box with a side below 1 or outside the plane,
+ * masks that overlap. */
+int vkx_box_label_masks_dev(vkx_ctx *ctx, const int32_t *boxes_host, int n_text, int n_dilated, int h, int w, uint8_t *text_mask,
+                            uint8_t *boundary_mask, uint8_t *both_mask);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

@@ -402,6 +402,9 @@ _SIGNATURES['vkx_text_lines_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int,
 _SIGNATURES['vkx_set_mask_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ssize, c_void_p,
                                    ctypes.c_size_t]
 _SIGNATURES['vkx_set_mask'] = _SIGNATURES['vkx_set_mask_dev']
+_SIGNATURES['vkx_quad_interp_fill_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+_SIGNATURES['vkx_quad_interp_uv_dev'] = [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]
+_SIGNATURES['vkx_box_label_masks_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
 _lib = None
@@ -2777,3 +2780,75 @@ def set_mask(elements, shape, mode, want_windows=False, ctx=None, gated=False):
         return dst, [DevView(block, off, (wh, ww)) for off, wh, ww in layout]
     packed = block.host()
     return dst.host(), [packed[off:off + wh * ww].reshape(wh, ww) for off, wh, ww in layout]
+
+
+# --------------------------------------------------------------------------------------------------------------
+# text-line labels: quad interpolation and the box masks (csrc/quad_interp.hip): vkx_quad of include/vkx.h
+# --------------------------------------------------------------------------------------------------------------
+QUAD_U, QUAD_V, QUAD_FRESH_ONE = 0, 1, 0x100
+QUAD_DTYPE = np.dtype([('x', np.int32, (4,)), ('y', np.int32, (4,)), ('sx', np.float32, (4,)), ('sy', np.float32, (4,)),
+                       ('component', np.int32), ('reserved', np.int32, (3,))], align=True)
+assert QUAD_DTYPE.itemsize == 80
+
+
+def quad_records(quads, components):
+    """The QUAD_DTYPE table of ``quads`` -- each four points (``x`` / ``y``: the rounded integer position) in the order
+    point0 .. point3 of ScoreMap.from_quad_interpolation -- storing ``components`` (QUAD_U / QUAD_V, one or one a quad).  The float32
+    vertices are the self-relative polygon's: integer positions minus the bounding box's corner (reference polygon.py:109-118)."""
+    xy = np.array([[(p.x, p.y) for p in quad] for quad in quads], np.int64).reshape(-1, 4, 2)
+    recs = np.zeros(len(xy), QUAD_DTYPE)
+    if len(xy):
+        if np.abs(xy).max() >= 1 << 24:
+            raise ValueError('a quad vertex outside +-2^24')
+        # (a quad whose first and last vertex coincide loses one in the reference's PointTuple.from_np_array and fails there)
+        if ((xy[:, 0] == xy[:, 3]).all(axis=1)).any():
+            raise IndexError('a quad whose point0 and point3 round to one pixel')
+        recs['x'], recs['y'] = xy[:, :, 0], xy[:, :, 1]
+        rel = (xy - xy.min(axis=1, keepdims=True)).astype(np.float32)
+        recs['sx'], recs['sy'] = rel[:, :, 0], rel[:, :, 1]
+        recs['component'] = components
+    return recs
+
+
+def quad_interp_fill(dst, records, mode=FILL_PLAIN, zero_where=None):
+    """vkx_quad_interp_fill_dev: the stored component of every QUAD_DTYPE record onto the float32 DevArray ``dst`` in list order
+    where it is > 0 (FILL_PLAIN / FILL_KEEP_MAX / FILL_KEEP_MIN; | QUAD_FRESH_ONE: ``dst`` is born 1.0 by the call), then 0.0 where the uint8 DevArray ``zero_where`` is 0.  At most
+    TWO launches whatever the number of quads, asynchronous."""
+    records = _records(records, QUAD_DTYPE)
+    if dst.dtype != np.float32 or dst.ndim != 2:
+        raise TypeError('dst must be a float32 (h, w) DevArray')
+    if zero_where is not None and (zero_where.dtype != np.uint8 or zero_where.shape != dst.shape or zero_where.ctx is not dst.ctx):
+        raise TypeError('zero_where must be a uint8 DevArray of the shape and context of dst')
+    h, w = dst.shape
+    check(lib().vkx_quad_interp_fill_dev(dst.ctx.handle, records.ctypes.data if len(records) else None, len(records), int(mode), h, w,
+                                         c_void_p(dst.ptr), c_void_p(zero_where.ptr) if zero_where is not None else None))
+    dst.invalidate_host()
+
+
+def quad_interp_uv(record, ctx=None):
+    """vkx_quad_interp_uv_dev: the float32 DevArray (bh, bw, 2) of (u, v) of ONE QUAD_DTYPE record over its bounding box."""
+    record = _records(record, QUAD_DTYPE)
+    if len(record) != 1:
+        raise ValueError('one quad')
+    ctx = ctx or default_ctx()
+    bh = int(record['y'].max()) - int(record['y'].min()) + 1
+    bw = int(record['x'].max()) - int(record['x'].min()) + 1
+    uv = ctx.dev_empty((bh, bw, 2), np.float32)
+    check(lib().vkx_quad_interp_uv_dev(ctx.handle, record.ctypes.data, c_void_p(uv.ptr), uv.size))
+    return uv
+
+
+def box_label_masks(shape, text_boxes, dilated_boxes=None, ctx=None):
+    """vkx_box_label_masks_dev: the uint8 DevArrays (text mask, boundary mask, text-and-boundary mask) of a page of ``shape``
+    from its text-line boxes and, unless None (then the last two are None), its dilated-only boxes; int (n, 4) tables of
+    {up, left, height, width}.  ONE launch, asynchronous."""
+    ctx = ctx or default_ctx()
+    h, w = int(shape[0]), int(shape[1])
+    text_boxes = np.asarray(text_boxes, np.int32).reshape(-1, 4)
+    both = dilated_boxes is not None
+    dilated_boxes = np.asarray(dilated_boxes if both else [], np.int32).reshape(-1, 4)
+    table = np.ascontiguousarray(np.concatenate([text_boxes, dilated_boxes]))
+    masks = [ctx.dev_empty((h, w), np.uint8) for _ in range(3 if both else 1)] + [None] * (0 if both else 2)
+    check(lib().vkx_box_label_masks_dev(ctx.handle, table.ctypes.data if len(table) else None, len(text_boxes), len(dilated_boxes),
+                                        h, w, *(c_void_p(m.ptr) if m is not None else None for m in masks)))
+    return tuple(masks)

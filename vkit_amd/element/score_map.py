@@ -3,7 +3,7 @@
 On the hot path a ScoreMap is (a) an element that grid / affine distortions remap with float32 bilinear
 weights and (b) the per-pixel alpha of a text-line layer in the page composite.
 """
-from typing import Iterable, Optional, Tuple, Union
+from typing import Callable, Iterable, Optional, Tuple, Union
 
 import attrs
 import numpy as np
@@ -19,6 +19,37 @@ class ScoreMapSetItemConfig:
     value: Union['ScoreMap', np.ndarray, float] = 1.0
     keep_max_value: bool = False
     keep_min_value: bool = False
+
+
+@attrs.define
+class NpVec:
+    """A 2-D vector of numpy values with the cross product as ``*`` (reference score_map.py:36-56)."""
+    x: np.ndarray
+    y: np.ndarray
+
+    @classmethod
+    def from_point(cls, point: 'Point'):
+        return cls(x=np.asarray(point.smooth_x, dtype=np.float32), y=np.asarray(point.smooth_y, dtype=np.float32))
+
+    def __add__(self, other: 'NpVec'):
+        return NpVec(x=self.x + other.x, y=self.y + other.y)
+
+    def __sub__(self, other: 'NpVec'):
+        return NpVec(x=self.x - other.x, y=self.y - other.y)
+
+    def __mul__(self, other: 'NpVec') -> np.ndarray:
+        return self.x * other.y - self.y * other.x
+
+
+def quad_u(np_uv: np.ndarray) -> np.ndarray:
+    """The u plane of a (h, w, 2) array of (u, v): as ``func_np_uv_to_mat`` it is recognised by identity and keeps
+    ``fill_by_quad_interpolation`` on the device."""
+    return np_uv[:, :, 0]
+
+
+def quad_v(np_uv: np.ndarray) -> np.ndarray:
+    """The v plane; see ``quad_u``."""
+    return np_uv[:, :, 1]
 
 
 @attrs.define(frozen=True, eq=False)
@@ -149,6 +180,66 @@ class ScoreMap(LazyMat, Shapable):
     def __getitem__(self, element):
         return element.extract_score_map(self)
 
+    # ---- quad interpolation (reference score_map.py:139-283, :562-588): csrc/quad_interp.hip
+    @classmethod
+    def from_quad_interpolation(cls, point0: 'Point', point1: 'Point', point2: 'Point', point3: 'Point',
+                                func_np_uv_to_mat: Callable[[np.ndarray], np.ndarray], is_prob: bool = True):
+        """The inverse bilinear map of the quad point0 (u 0, v 0), point1 (u 1, v 0), point2 (u 1, v 1), point3 (u 0, v 1) over
+        its bounding box, computed on the device; ``func_np_uv_to_mat`` takes the float32 (h, w, 2) array of (u, v).  With
+        ``quad_u`` / ``quad_v`` are the callables the reference's callers write as lambdas."""
+        record = _native.quad_records([(point0, point1, point2, point3)], _native.QUAD_V)
+        mat = func_np_uv_to_mat(_native.quad_interp_uv(record).host())
+        return cls(mat=mat, box=Polygon.create((point0, point1, point2, point3)).bounding_box, is_prob=is_prob)
+
+    def fill_by_quad_interpolation(self, point0: 'Point', point1: 'Point', point2: 'Point', point3: 'Point',
+                                   func_np_uv_to_mat: Callable[[np.ndarray], np.ndarray], keep_max_value: bool = False,
+                                   keep_min_value: bool = False):
+        """``from_quad_interpolation`` filled where it is > 0 (the destination's own box is not consulted: the quad's bounding box
+        addresses the array, as in the reference).  With ``quad_u`` / ``quad_v`` the whole operation stays on the device."""
+        if func_np_uv_to_mat is quad_u or func_np_uv_to_mat is quad_v:
+            self.fill_by_quad_interpolations([(point0, point1, point2, point3)], func_np_uv_to_mat, keep_max_value=keep_max_value,
+                                             keep_min_value=keep_min_value)
+            return
+        score_map = self.from_quad_interpolation(point0, point1, point2, point3, func_np_uv_to_mat, is_prob=self.is_prob)
+        assert score_map.box
+        fill = _sets._Fill(self, keep_max_value, keep_min_value)
+        box = score_map.box
+        if self.box:        # (_Fill addresses through the destination's box)
+            box = box.to_shifted_box(offset_y=self.box.up, offset_x=self.box.left)
+        fill.add(box, score_map.mat, mask=(score_map.mat > 0.0))
+        fill.commit()
+
+    def fill_by_quad_interpolations(self, quads, selector, keep_max_value: bool = False, keep_min_value: bool = False,
+                                    zero_where=None):
+        """``fill_by_quad_interpolation`` of every (point0, point1, point2, point3) of ``quads`` in list order with ``selector``
+        (``quad_u`` / ``quad_v``, one or one a quad) in ONE device call of at most two launches.  ``zero_where``: a Mask (or uint8
+        plane) of the destination's shape; where it is 0 the destination is 0.0 after the fills."""
+        assert not (keep_max_value and keep_min_value)
+        quads = list(quads)
+        selectors = [selector] * len(quads) if callable(selector) else list(selector)
+        assert len(selectors) == len(quads)
+        components = []
+        for one in selectors:
+            if one is not quad_u and one is not quad_v:
+                raise NotImplementedError('fill_by_quad_interpolations takes the selectors quad_u and quad_v')
+            components.append(_native.QUAD_U if one is quad_u else _native.QUAD_V)
+        records = _native.quad_records(quads, components)
+        mode = _native.FILL_KEEP_MAX if keep_max_value else (_native.FILL_KEEP_MIN if keep_min_value else _native.FILL_PLAIN)
+        if isinstance(zero_where, Mask):
+            zero_where = zero_where._mat
+        if isinstance(zero_where, np.ndarray) and zero_where.dtype == np.bool_:
+            zero_where = zero_where.view(np.uint8)
+        target = self._mat
+        if isinstance(target, _native.DevArray):
+            _native.quad_interp_fill(target, records, mode, None if zero_where is None else target.ctx.to_device(zero_where))
+            return
+        # a host destination is staged for the call and comes back on the host
+        ctx = zero_where.ctx if isinstance(zero_where, _native.DevArray) else _native.default_ctx()
+        staged = ctx.to_device(target)
+        _native.quad_interp_fill(staged, records, mode, None if zero_where is None else ctx.to_device(zero_where))
+        with self.writable_context:
+            np.copyto(self._mat, staged.host())
+
     def to_shifted_score_map(self, offset_y: int = 0, offset_x: int = 0):
         assert self.box
         return attrs.evolve(self, box=self.box.to_shifted_box(offset_y=offset_y, offset_x=offset_x))
@@ -215,4 +306,6 @@ def generate_fill_by_score_maps_mask(shape, score_maps, mode: ElementSetOperatio
 from .box import Box  # noqa: E402
 from .mask import Mask  # noqa: E402
 from .image import Image  # noqa: E402
+from .point import Point  # noqa: E402,F401
+from .polygon import Polygon  # noqa: E402
 from . import _sets  # noqa: E402

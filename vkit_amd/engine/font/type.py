@@ -10,7 +10,7 @@ from typing import Any, List, Mapping, Optional, Sequence, Tuple
 import attrs
 import numpy as np
 
-from vkit_amd.element import Box, Image, Mask, Polygon, ScoreMap, Shapable
+from vkit_amd.element import Box, Image, Mask, Point, PointList, Polygon, ScoreMap, Shapable
 
 _CV_INTER_CUBIC = 2
 
@@ -226,6 +226,71 @@ class TextLine:
             score_map=self.score_map.to_shifted_score_map(offset_y=offset_y, offset_x=offset_x) if self.score_map else None,
             char_boxes=[char_box.to_shifted_char_box(offset_y=offset_y, offset_x=offset_x) for char_box in self.char_boxes],
         )
+
+    def to_polygon(self):
+        """The outline of the line through the ends of its char boxes along the writing direction, with one point in the middle
+        of each short side when the line is more than two pixels thick (reference :560-613)."""
+        box = self.box
+        if self.is_hori:
+            begin, end, edges = box.left, box.right, [(char_box.left, char_box.right) for char_box in self.char_boxes]
+        else:
+            begin, end, edges = box.up, box.down, [(char_box.up, char_box.down) for char_box in self.char_boxes]
+        stops = [begin]
+        for lo, hi in edges:
+            if stops[-1] < lo:
+                stops.append(lo)
+            if lo < hi:
+                stops.append(hi)
+        if stops[-1] < end:
+            stops.append(end)
+        points = PointList()
+        if self.is_hori:
+            mid = (box.up + box.down) // 2
+            thick = box.up < mid < box.down
+            points.extend(Point.create(y=box.up, x=x) for x in stops)
+            if thick:
+                points.append(Point.create(y=mid, x=stops[-1]))
+            points.extend(Point.create(y=box.down, x=x) for x in reversed(stops))
+            if thick:
+                points.append(Point.create(y=mid, x=stops[0]))
+        else:
+            mid = (box.left + box.right) // 2
+            thick = box.left < mid < box.right
+            points.extend(Point.create(y=y, x=box.right) for y in stops)
+            if thick:
+                points.append(Point.create(y=stops[-1], x=mid))
+            points.extend(Point.create(y=y, x=box.left) for y in reversed(stops))
+            if thick:
+                points.append(Point.create(y=stops[0], x=mid))
+        return Polygon.create(points=points)
+
+    def get_height_points(self, num_points: int, is_up: bool):
+        """``num_points`` sample points along the up (a vertical line: right) or down (left) side (reference :701-732; a
+        horizontal line samples x from 0, not from its left end, as the reference does)."""
+        box = self.box
+        if self.is_hori:
+            stops = list(range(0, box.right + 1, max(1, box.width // num_points)))
+            last = box.right
+        else:
+            stops = list(range(box.up, box.down + 1, max(1, box.height // num_points)))
+            last = box.down
+        if len(stops) >= num_points:
+            stops = stops[:num_points - 1]
+            stops.append(last)
+        if self.is_hori:
+            y = box.up if is_up else box.down
+            return PointList(Point.create(y=y, x=x) for x in stops)
+        x = box.right if is_up else box.left
+        return PointList(Point.create(y=y, x=x) for y in stops)
+
+    def get_char_level_height_points(self, is_up: bool):
+        """One point a char at the middle of its box along the writing direction, on the up or down side (reference :734-755)."""
+        box = self.box
+        if self.is_hori:
+            y = box.up if is_up else box.down
+            return PointList(Point.create(y=y, x=(char_box.left + char_box.right) / 2) for char_box in self.char_boxes)
+        x = box.right if is_up else box.left
+        return PointList(Point.create(y=(char_box.up + char_box.down) / 2, x=x) for char_box in self.char_boxes)
 
     @classmethod
     def build_char_polygon(cls, up: float, down: float, left: float, right: float):

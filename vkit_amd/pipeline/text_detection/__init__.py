@@ -32,6 +32,12 @@ from .page_cropping import (  # noqa: F401
     PageCroppingStepOutput,
     page_cropping_step_factory,
 )
+from .page_text_line_label import (  # noqa: F401
+    PageTextLineLabelStep,
+    PageTextLineLabelStepConfig,
+    PageTextLineLabelStepInput,
+    page_text_line_label_step_factory,
+)
 from .page_text_region import (  # noqa: F401
     ColumnPacker,
     FlattenedTextRegion,

@@ -187,6 +187,11 @@ class PageCharPolygonCollection:
 class PageTextLineLabelStepOutput:
     page_char_polygon_collection: PageCharPolygonCollection
     page_text_line_polygon_collection: PageTextLinePolygonCollection
+    # the planes of PageTextLineLabelStep (page_text_line_label.py), each built only on request
+    page_text_line_mask: Optional[Mask] = None
+    page_text_line_boundary_mask: Optional[Mask] = None
+    page_text_line_and_boundary_mask: Optional[Mask] = None
+    page_text_line_boundary_score_map: Optional[ScoreMap] = None
 
 
 # ---- the step ---------------------------------------------------------------------------------------------------
