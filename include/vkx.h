@@ -959,7 +959,8 @@ int vkx_region_label_deviate_dev(vkx_ctx *ctx, const double *quads_host, const i
  * generate_page_char_mask (:406) and generate_page_char_height_score_map (:439): box_mask = 1 inside any of the boxes
  * (up, down, left, right), 0 elsewhere; char_mask = 0 and char_height = 0.0f where active_mask == 0.  Dense device planes
  * [h, w].  One launch, no synchronisation.  Refused for a NULL pointer, n_boxes outside 0 .. 2^24 - 1, h or w outside
- * 1 .. 32768, a box not inside the page and planes that overlap one another. */
+ * 1 .. 32768, a box not inside the page, planes that overlap one another, and more than 2^28 (box, 32 x 32 tile) pairs over
+ * the tiles that no box covers whole ("too many (box, tile) pairs"). */
 int vkx_region_label_planes_dev(vkx_ctx *ctx, const int32_t *boxes_host, int n_boxes, int h, int w, const uint8_t *active_mask,
                                 uint8_t *char_mask, float *char_height, uint8_t *box_mask);
 

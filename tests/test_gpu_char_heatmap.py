@@ -111,6 +111,19 @@ def test_overlap_mask_of_doubled_quads_is_the_union_of_fill_poly(seed):
     assert np.array_equal(out.debug.char_overlapped_mask.mat, want)
 
 
+@pytest.mark.parametrize('bw,bh', [(32, 8), (33, 9)])
+def test_boxes_at_the_tile_borders(bw, bh):
+    """axis-aligned chars whose boxes are exactly one 32 x 8 tile, and 33 x 9: one pixel into a second tile row and column; two
+    overlapping chars and one in the page's last rows and columns, against the restatement"""
+    shape = (40, 100)
+    quads = np.array([[(x, y), (x + bw - 1, y), (x + bw - 1, y + bh - 1), (x, y + bh - 1)]
+                      for x, y in ((5, 3), (20, 7), (shape[1] - bw, shape[0] - bh))], np.float64)
+    assert all(R.char_geometry(q)[1] == (int(q[0, 1]), int(q[0, 1]) + bh - 1, int(q[0, 0]), int(q[0, 0]) + bw - 1) for q in quads)
+    want = R.run(quads, shape)
+    assert want['char_overlapped_mask'].any()
+    _assert_bitwise(_planes(_run(quads, shape, True)), want, ('score',) + R.DEBUG_NAMES)
+
+
 def test_permuted_chars_give_identical_planes():
     rng = default_rng(9)
     quads = R.text_line_quads(rng, (512, 640), 500, step=(0.6, 0.9))

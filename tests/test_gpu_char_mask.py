@@ -62,6 +62,19 @@ def test_engine_equals_the_reference(case, resident):
     assert all(m.mat.shape == m.box.shape for m in out.char_masks)
 
 
+@pytest.mark.parametrize('L,side,box_side', [(20, 10, 16), (32, 11, 17)])
+def test_boxes_at_the_tile_borders(L, side, box_side):
+    """axis-aligned square chars whose trimmed boxes are exactly one 16 x 16 tile, and 17 x 17: one pixel into a second tile row and
+    column; two overlapping chars, against the restatement"""
+    quads = np.array([[(x, y), (x + side, y), (x + side, y + side), (x, y + side)] for x, y in ((30, 20), (38, 25))], np.float64)
+    want, chars = R.run(quads, L, (64, 96))
+    assert all((down - up + 1, right - left + 1) == (box_side, box_side) for (up, down, left, right), _ in chars)
+    out = _run_engine({'shape': (64, 96), 'quads': quads, 'L': L}, True)
+    assert np.array_equal(out.combined_chars_mask.mat, want)
+    assert [(m.box.up, m.box.down, m.box.left, m.box.right) for m in out.char_masks] == [tuple(box) for box, _ in chars]
+    assert all(np.array_equal(m.mat, mat) for m, (_, mat) in zip(out.char_masks, chars))
+
+
 def test_planes_are_fresh_after_a_refused_call():
     """a raising char leaves no plane behind, and the next call paints as if nothing had happened (ownership planes clean)"""
     bad = next(c for c in ENGINE if c.get('raises') == 'RuntimeError')

@@ -192,6 +192,20 @@ def test_raw_entry_equals_the_restatement(shape, ksize):
         assert np.array_equal(got, R.combine(tiles, sources, shape, ksize, half=half_width, sigma=sigma)), half_width
 
 
+def test_raw_entry_at_the_block_borders():
+    """A 40 x 150 page (3 x 3 blocks of 64 x 16), ksize 5 and half 3, so a tile reaches 3 pixels beyond its edges: tiles whose right
+    edge is 60 (the reach ends on the block's last column), 61 (one column into the next block) and 64 (inside it), and whose lower
+    edge is 12, 13 and 16 likewise; each alone, and the nine in one table."""
+    from vkit_amd import _native as N
+    rng = default_rng(405)
+    shape, ksize, half = (40, 150), 5, 3
+    sources = [rng.integers(0, 256, (20, 70, 3), dtype=np.uint8), rng.integers(0, 256, (18, 66, 3), dtype=np.uint8)]
+    tiles = [(1, down, 2, right, (down + right) % 2) for down in (15 - half, 16 - half, 16) for right in (63 - half, 64 - half, 64)]
+    for k, table in enumerate([[t] for t in tiles] + [tiles]):
+        got = N.image_combine(table, sources, shape, ksize, 1.0, half=half)
+        assert np.array_equal(got, R.combine(table, sources, shape, ksize, half=half, sigma=1.0)), k
+
+
 # ---- budget ----------------------------------------------------------------------------------------------------------------
 def _big_folder(tmp_path, n=6, side=256, seed=0):
     rng = default_rng(seed)

@@ -315,3 +315,56 @@ def test_random_quads_and_pages_equal_the_restatement():
         want = R.step_planes(lines, (h, w), (True, True, True))
         for key, attr in PLANE_KEYS.items():
             assert R.same_values(getattr(out, attr).mat, want[key]), (page, key)
+
+
+# ---- tile borders -------------------------------------------------------------------------------------------------------
+BORDER_BOXES = [(8, 32, 8, 32),         # exactly one 32 x 8 tile
+                (7, 31, 10, 34),        # one pixel over it on every side
+                (44, 69, 1, 1),         # the last pixel
+                (0, 0, 45, 70)]         # the whole plane
+BORDER_LISTS = [([box], []) for box in BORDER_BOXES] + [([], [box]) for box in BORDER_BOXES] + \
+               [([], []), (BORDER_BOXES[:1] + BORDER_BOXES[2:3], BORDER_BOXES[1:2]), (BORDER_BOXES[1:2], BORDER_BOXES[:1] + BORDER_BOXES[2:3])]
+
+
+@pytest.mark.parametrize('case', range(len(BORDER_LISTS)))
+def test_box_masks_at_the_tile_borders(case):
+    """vkx_box_label_masks_dev on a 45 x 70 plane (6 x 3 tiles of 32 x 8, ragged last row and column): each box alone as a text
+    box and alone as a dilated box, both lists empty, and two mixed lists, against the numpy union of the rectangles."""
+    from vkit_amd import _native as N
+    h, w = 45, 70
+    text_boxes, dilated_boxes = BORDER_LISTS[case]
+    want_text, want_dilated = np.zeros((h, w), np.uint8), np.zeros((h, w), np.uint8)
+    for want, boxes in ((want_text, text_boxes), (want_dilated, dilated_boxes)):
+        for up, left, bh, bw in boxes:
+            want[up:up + bh, left:left + bw] = 1
+    text, boundary, both = N.box_label_masks((h, w), text_boxes, dilated_boxes)
+    assert np.array_equal(text.host(), want_text)
+    assert np.array_equal(boundary.host(), want_dilated & (1 - want_text))
+    assert np.array_equal(both.host(), want_dilated | want_text)
+
+
+@pytest.mark.parametrize('mode', [R.PLAIN, R.KEEP_MAX, R.KEEP_MIN], ids=['plain', 'max', 'min'])
+@pytest.mark.parametrize('y0,x0', [(7, 31), (7, 32), (8, 31), (8, 32)])
+def test_quad_fill_at_the_tile_borders(y0, x0, mode):
+    """vkx_quad_interp_fill_dev on a 40 x 70 plane: the quads of quad_cases() translated so that their bounding boxes start one
+    pixel before and exactly at the second tile column (x = 31, 32) and the second tile row (y = 7, 8), all in one call, against
+    R.quad_fill one by one.  Every quad of quad_cases() whose bounding box fits the plane from (8, 32) takes part (at most 32 x 38:
+    the side trapezoids and strips, the one-row quad and the thin one; the others are wider or taller than what is left)."""
+    from vkit_amd import _native as N
+    h, w = 40, 70
+    quads, components = [], []
+    for k, (name, quad) in enumerate(R.quad_cases().items()):
+        (up, left, bh, bw), _ = R.quad_geometry(quad)
+        if bh > h - 8 or bw > w - 32:
+            continue
+        quads.append([(y - up + y0, x - left + x0) for y, x in quad])
+        components.append(k % 2)
+    assert len(quads) >= 6
+    want = R.fill_plane((h, w)).copy()
+    for quad, component in zip(quads, components):
+        assert R.quad_geometry(quad)[0][:2] == (y0, x0)
+        R.quad_fill(want, quad, component, mode)
+    got = N.default_ctx().to_device(R.fill_plane((h, w)).copy())
+    N.quad_interp_fill(got, N.quad_records([points_of(q) for q in quads], np.array(components, np.int32)), mode)
+    got = got.host()
+    assert got.dtype == want.dtype and np.array_equal(got, want, equal_nan=True)     # (the one-row quad leaves NaNs)

@@ -248,6 +248,66 @@ def test_abi_refusals_leave_canaries():
     assert (rec['status'] == 0).all() and rec['iy'].tolist() == [11, 15, 19] and rec['ix'].tolist() == [11, 15, 19]
 
 
+def _planes_against_numpy(shape, boxes, active):
+    """vkx_region_label_planes_dev on planes of ``shape`` that start from fixed patterns, against numpy"""
+    from vkit_amd import _native as N
+    ctx = N.default_ctx()
+    ys, xs = np.indices(shape)
+    cmask0 = ((ys + xs) % 3 != 0).astype(np.uint8)
+    height0 = ((ys * 5 + xs) % 7 + 1).astype(np.float32)
+    cmask, height, bmask = ctx.to_device(cmask0), ctx.to_device(height0), N.dev_full(shape, 0xCD, ctx=ctx)
+    N.region_label_planes(boxes, ctx.to_device(active), cmask, height, bmask)
+    want = np.zeros(shape, np.uint8)
+    for up, down, left, right in boxes:
+        want[up:down + 1, left:right + 1] = 1
+    assert np.array_equal(bmask.host(), want)
+    assert np.array_equal(cmask.host(), np.where(active == 0, 0, cmask0).astype(np.uint8))
+    assert np.array_equal(height.host(), np.where(active == 0, 0, height0).astype(np.float32))
+
+
+SMALL, WHOLE_TILE = (40, 50, 40, 50), (32, 63, 32, 63)
+TILE_BOXES = [SMALL, WHOLE_TILE, (32, 63, 32, 62), (64, 69, 96, 99), (0, 69, 0, 99), SMALL]
+TILE_BOX_LISTS = [[box] for box in TILE_BOXES[:5]] + [
+    [SMALL, WHOLE_TILE, SMALL], [SMALL, (32, 63, 32, 62), SMALL], [SMALL, WHOLE_TILE, (32, 63, 32, 62), (64, 69, 96, 99), SMALL],
+    [SMALL, (64, 69, 96, 99), (32, 63, 32, 62)], TILE_BOXES, []]
+
+
+@pytest.mark.parametrize('backwards', [False, True], ids=['listed', 'reversed'])
+@pytest.mark.parametrize('case', range(len(TILE_BOX_LISTS)))
+def test_planes_at_the_tile_borders(case, backwards):
+    """A 70 x 100 page (3 x 4 tiles of 32 x 32, the last row and column clipped): a box that is a whole tile, one a column short of
+    it, the clipped corner tile covered whole, the whole page, and a small box listed before and after the box that makes its tile
+    whole, in both orders; the active mask has a zero band across tile borders."""
+    active = np.ones((70, 100), np.uint8)
+    active[30:35, :] = 0
+    active[:, 60:66] = 0
+    boxes = TILE_BOX_LISTS[case][::-1] if backwards else TILE_BOX_LISTS[case]
+    _planes_against_numpy((70, 100), np.array(boxes, np.int32).reshape(-1, 4), active)
+
+
+def test_planes_refuse_too_many_box_tile_pairs():
+    """One more row of 1024 (box, tile) pairs than the bound of 2^28: refused while the pairs are counted, nothing written; the same
+    table cut to 8 boxes is a call like any other.  (No success case near the bound: it would stage a gigabyte.)"""
+    from vkit_amd import _native as N
+    ctx = N.default_ctx()
+    h, w = 32, 32768
+    n = (1 << 28) // 1024 + 1
+    boxes = np.zeros((n, 4), np.int32)
+    boxes[:, 3] = w - 1                                    # row 0 of every tile: no tile is covered whole
+    active = ctx.to_device(np.zeros((h, w), np.uint8))
+    cmask, bmask = N.dev_full((h, w), 0xAB, ctx=ctx), N.dev_full((h, w), 0xCD, ctx=ctx)
+    height = ctx.to_device(np.full((h, w), 7.5, np.float32))
+    rc = N.lib().vkx_region_label_planes_dev(ctx.handle, boxes.ctypes.data, n, h, w, active.ptr, cmask.ptr, height.ptr, bmask.ptr)
+    assert rc == N.ERR_INVALID and 'too many (box, tile) pairs' in N.last_error()
+    ctx.sync()
+    for p in (cmask, bmask, height):
+        p.invalidate_host()
+    assert (cmask.host() == 0xAB).all() and (bmask.host() == 0xCD).all() and (height.host() == np.float32(7.5)).all()
+    band = np.ones((h, w), np.uint8)
+    band[:, 1000:1100] = 0
+    _planes_against_numpy((h, w), boxes[:8], band)
+
+
 def test_soak_seeded_pages():
     """seeded pages of varying size, char count, config, activity and placement: every one equals the restatement"""
     rng = default_rng(2027)

@@ -4,10 +4,11 @@
 // char's bounding box), keeps the max and the min of the warped values over the char's fillPoly raster, counts the chars
 // that cover every pixel (Mask.from_polygons INTERSECT), and mixes the page planes with numpy.  Here one call takes every
 // char of one page and writes fresh planes in three launches and no synchronisation:
-//   k_char_heatmap_setup    one lane per char: the homography (vkc::perspective_transform, shared with char_mask.hip), the
-//                           warpPerspective coordinate map of the char's box and the 4 edges of its fillPoly test;
-//   k_char_heatmap_raster   one workgroup per 32 x 8 tile of a char's box (the host lays the tiles out from the boxes it
-//                           computes itself): a lane decides the fillPoly membership of its pixel in closed form (the
+//   k_char_heatmap_setup    one lane per char: the homography (vkc::quad_internals and vkc::perspective_transform, shared with
+//                           char_mask.hip), the warpPerspective coordinate map of the char's box and the 4 edges of its
+//                           fillPoly test;
+//   k_char_heatmap_raster   one workgroup per 32 x 8 tile of a char's box (the host computes the boxes itself, vkx_quad_box, and
+//                           lays the tiles out from them, vkb::box_tile_starts; vkd::box_tile_pixel): a lane decides the fillPoly membership of its pixel in closed form (the
 //                           LINE_8 outline by vkc::bres_minor, or inside an even-odd span of the 16.16 crossings), samples
 //                           the template (vkd::CoordPerspective + vkd::sample_f32) and takes atomicMax / atomicMin of the
 //                           float bits into two page-sized int planes and atomicAdd into a count plane;
@@ -18,6 +19,7 @@
 #include "vkx_cell.h"
 #include "vkx_internal.h"
 #include "vkx_poly_raster.h"
+#include "vkx_tile_bins.h"
 
 #include <algorithm>
 #include <cmath>
@@ -43,12 +45,8 @@ __global__ void __launch_bounds__(256) k_char_heatmap_setup(const double *__rest
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
     const double *q = quads + (size_t)g * 8;
-    // Polygon.internals: the INTEGER points round(smooth) as float32, minus their min (the box's up / left)
-    float ip[8], rel[8];
-    for (int k = 0; k < 8; k++) ip[k] = (float)rint(q[k]);
-    float mx = ip[0], my = ip[1];
-    for (int k = 1; k < 4; k++) { mx = fminf(mx, ip[2 * k]); my = fminf(my, ip[2 * k + 1]); }
-    for (int k = 0; k < 4; k++) { rel[2 * k] = ip[2 * k] - mx; rel[2 * k + 1] = ip[2 * k + 1] - my; }
+    float rel[8];                        // Polygon.internals: relative to the box's up / left
+    vkc::quad_internals(q, rel);
     const float s = (float)(2 * r);
     const float tmpl_pts[8] = {0.f, 0.f, s, 0.f, s, s, 0.f, s};
     double H[9];
@@ -69,11 +67,9 @@ __global__ void __launch_bounds__(256) k_char_heatmap_raster(const CharHeat *__r
                                                              int *__restrict__ max_bits, int *__restrict__ min_bits,
                                                              int *__restrict__ count)
 {
-    const int t = blockIdx.x;
-    const int lo = vkd::last_at_most(n, t, [&](int g) { return tile_start[g]; });     // the char of tile t
+    int rx, ry;
+    const int lo = vkd::box_tile_pixel<kTileW, kTileH>(n, tile_start, [&](int g) { return heat[g].bw; }, rx, ry);     // the char of the tile
     const CharHeat &C = heat[lo];
-    const int tiles_x = (C.bw + kTileW - 1) / kTileW, lt = t - tile_start[lo];
-    const int ry = (lt / tiles_x) * kTileH + (threadIdx.x / kTileW), rx = (lt % tiles_x) * kTileW + (threadIdx.x % kTileW);
     if (ry >= C.bh || rx >= C.bw) return;
     if (!vkp::quad_covers(C.e, rx, ry)) return;
     int X, Y;
@@ -155,23 +151,15 @@ int check_call(const vkx_char_heatmap_config *config, const double *quads, int n
     int rc = collect_outputs(score, debug, out, &n_out);
     if (rc) return rc;
     const size_t page = (size_t)h * w;
-    for (int a = 0; a < n_out; a++)
-        for (int b = a + 1; b < n_out; b++)
-            VKX_REQUIRE(!vkx_planes_overlap(out[a].p, 1, 0, page * out[a].elem, out[b].p, 1, 0, page * out[b].elem),
-                        "output planes overlap");
+    vkx_plane_bytes planes[7];
+    for (int k = 0; k < n_out; k++) planes[k] = {out[k].p, page * out[k].elem};
+    VKX_REQUIRE(vkx_planes_disjoint(planes, n_out), "output planes overlap");
     boxes->assign((size_t)4 * n, 0);
     for (int g = 0; g < n; g++) {
-        const double *q = quads + (size_t)g * 8;
-        double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-        for (int k = 0; k < 4; k++) {
-            VKX_REQUIRE(std::isfinite(q[2 * k]) && std::isfinite(q[2 * k + 1]), "non-finite char point");
-            const double x = std::nearbyint(q[2 * k]), y = std::nearbyint(q[2 * k + 1]);   // round half to even
-            x0 = std::min(x0, x); x1 = std::max(x1, x);
-            y0 = std::min(y0, y); y1 = std::max(y1, y);
-        }
-        VKX_REQUIRE(y0 >= 0 && y1 < h && x0 >= 0 && x1 < w, "a char box outside the page");
-        int *b = boxes->data() + (size_t)4 * g;
-        b[0] = (int)y0; b[1] = (int)x0; b[2] = (int)(y1 - y0) + 1; b[3] = (int)(x1 - x0) + 1;
+        double box[4];
+        VKX_REQUIRE(vkx_quad_box(quads + (size_t)g * 8, box), "non-finite char point");
+        VKX_REQUIRE(box[0] >= 0 && box[0] + box[2] <= h && box[1] >= 0 && box[1] + box[3] <= w, "a char box outside the page");
+        for (int k = 0; k < 4; k++) (*boxes)[(size_t)4 * g + k] = (int)box[k];
     }
     return VKX_OK;
 }
@@ -188,15 +176,11 @@ VKX_EXPORT int vkx_char_heatmap_fresh_dev(vkx_ctx *ctx, const vkx_char_heatmap_c
     const int n = n_chars, r = config->radius, E = 2 * r + 1;
 
     // the tile layout, from the boxes
-    std::vector<int> tile_start((size_t)n + 1);
-    long long tiles = 0;
-    for (int g = 0; g < n; g++) {
-        const int *b = boxes.data() + (size_t)4 * g;
-        tile_start[g] = (int)tiles;
-        tiles += (long long)((b[2] + kTileH - 1) / kTileH) * ((b[3] + kTileW - 1) / kTileW);
-        VKX_REQUIRE(tiles < (1LL << 31), "too many tiles");
-    }
-    tile_start[n] = (int)tiles;
+    std::vector<int> tile_start;
+    VKX_REQUIRE((vkb::box_tile_starts<kTileW, kTileH>(n, [&](int g, long long &bh, long long &bw) {
+                    bh = boxes[(size_t)4 * g + 2]; bw = boxes[(size_t)4 * g + 3]; }, tile_start)),
+                "too many tiles");
+    const int tiles = tile_start[n];
 
     // one staged block: template, quads, boxes, tile starts
     vkx_tables tab(ctx);

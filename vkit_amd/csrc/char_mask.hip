@@ -5,14 +5,16 @@
 // call takes every char of up to 8 sets of one page and paints fresh planes in three launches and one synchronisation:
 //   k_char_mask_setup    one lane per char: the two homographies, the placement and the trim, a status for the cases where
 //                        the reference raises; the boxes travel to the host (the one synchronisation), which raises or
-//                        lays the trimmed boxes out as 16 x 16 tiles;
-//   k_char_mask_raster   one workgroup per tile: the warpPerspective sample of the disc (vkd::CoordPerspective and
-//                        vkd::sample_u8, shared with remap.hip) at each pixel; coverage (sample != 0) takes an atomicMax of
-//                        the char's rank in the set's ownership plane, and the packed per-char masks take the sample itself;
+//                        lays the trimmed boxes out as 16 x 16 tiles (vkb::box_tile_starts);
+//   k_char_mask_raster   one workgroup per tile (vkd::box_tile_pixel): the warpPerspective sample of the disc
+//                        (vkd::CoordPerspective and vkd::sample_u8, shared with remap.hip) at each pixel; coverage (sample != 0)
+//                        takes an atomicMax of the char's rank in the set's ownership plane, and the packed per-char masks take
+//                        the sample itself;
 //   k_char_mask_resolve  every pixel of every set: mask = owner != 0, score = value of the owner (0 where none), and the
 //                        ownership plane back to zero for the next call.
 #include "vkx_cell.h"
 #include "vkx_internal.h"
+#include "vkx_tile_bins.h"
 
 #include <algorithm>
 #include <cmath>
@@ -116,26 +118,15 @@ __global__ void __launch_bounds__(256) k_char_mask_setup(const CharIn *__restric
     G.pad = 0;
     int out_box[4] = {0, -1, 0, -1};
 
-    // 1. H1: char points -> the polygon's self-relative points (Polygon.internals: PointTuple.to_smooth_np_array holds the
-    // INTEGER points round(smooth) as float32 (element/point.py:251), minus their min)
-    float ip[8], rel[8];
-    for (int k = 0; k < 8; k++) ip[k] = (float)rint(c.q[k]);
-    float mx = ip[0], my = ip[1];
-    for (int k = 1; k < 4; k++) { mx = fminf(mx, ip[2 * k]); my = fminf(my, ip[2 * k + 1]); }
-    for (int k = 0; k < 4; k++) { rel[2 * k] = ip[2 * k] - mx; rel[2 * k + 1] = ip[2 * k + 1] - my; }
+    // 1. H1: char points -> the polygon's self-relative points (Polygon.internals)
+    float rel[8];
+    vkc::quad_internals(c.q, rel);
     double H[9];
     vkc::perspective_transform(char_pts, rel, H);
 
-    // affine_np_points: float64 H times the float32 (x, y, 1) columns -- numpy's matmul sums as fma(a2, x2, fma(a1, x1, a0 x0))
+    // affine_np_points of the four external points (four columns)
     double px[4], py[4];
-    for (int k = 0; k < 4; k++) {
-        const double x = ext_pts[2 * k], y = ext_pts[2 * k + 1];
-        const double u = fma(H[2], 1.0, fma(H[1], y, H[0] * x));
-        const double v = fma(H[5], 1.0, fma(H[4], y, H[3] * x));
-        const double w = fma(H[8], 1.0, fma(H[7], y, H[6] * x));
-        px[k] = u / w;
-        py[k] = v / w;
-    }
+    for (int k = 0; k < 4; k++) vkc::affine_point(H, ext_pts[2 * k], ext_pts[2 * k + 1], false, px[k], py[k]);
     const double y_off = nan_min4(py), x_off = nan_min4(px);
     float tp[8], tx[4], ty[4];
     for (int k = 0; k < 4; k++) {
@@ -188,11 +179,9 @@ __global__ void __launch_bounds__(256) k_char_mask_raster(const CharIn *__restri
                                                           const int *__restrict__ tile_start, const long long *__restrict__ packed_off,
                                                           int n, int R, int w, const SetDev *__restrict__ sets)
 {
-    const int t = blockIdx.x;
-    const int lo = vkd::last_at_most(n, t, [&](int g) { return tile_start[g]; });     // the char of tile t
+    int rx, ry;
+    const int lo = vkd::box_tile_pixel<kTile, kTile>(n, tile_start, [&](int g) { return geo[g].bw; }, rx, ry);     // the char of the tile
     const CharGeo &G = geo[lo];
-    const int tiles_x = (G.bw + kTile - 1) / kTile, lt = t - tile_start[lo];
-    const int ry = (lt / tiles_x) * kTile + (threadIdx.x >> 4), rx = (lt % tiles_x) * kTile + (threadIdx.x & 15);
     if (ry >= G.bh || rx >= G.bw) return;
     const int E = 2 * R + 1;
     int X, Y;
@@ -217,11 +206,6 @@ __global__ void __launch_bounds__(256) k_char_mask_resolve(const CharIn *__restr
     if (o) S.owner[i] = 0;
 }
 
-bool bytes_overlap(const void *a, size_t an, const void *b, size_t bn)
-{
-    return vkx_planes_overlap(a, 1, 0, an, b, 1, 0, bn);
-}
-
 // Argument checks shared by both forms.
 int check_sets(const vkx_char_set *sets, int n_sets, int L, int h, int w, long long *total)
 {
@@ -230,7 +214,7 @@ int check_sets(const vkx_char_set *sets, int n_sets, int L, int h, int w, long l
     VKX_REQUIRE(L >= 1 && L <= kMaxSide, "internal_side_length 1 .. 2048");
     VKX_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < (1LL << 31), "bad page shape");
     long long n = 0;
-    std::vector<std::pair<const void *, size_t>> outs;
+    std::vector<vkx_plane_bytes> outs;
     for (int s = 0; s < n_sets; s++) {
         const vkx_char_set &S = sets[s];
         VKX_REQUIRE(S.n_chars >= 0, "negative char count");
@@ -253,9 +237,7 @@ int check_sets(const vkx_char_set *sets, int n_sets, int L, int h, int w, long l
         if (S.char_masks && S.char_masks_cap) outs.push_back({S.char_masks, (size_t)S.char_masks_cap});
         n += S.n_chars;
     }
-    for (size_t a = 0; a < outs.size(); a++)
-        for (size_t b = a + 1; b < outs.size(); b++)
-            VKX_REQUIRE(!bytes_overlap(outs[a].first, outs[a].second, outs[b].first, outs[b].second), "output planes overlap");
+    VKX_REQUIRE(vkx_planes_disjoint(outs.data(), outs.size()), "output planes overlap");
     VKX_REQUIRE(n < (1LL << 24), "at most 2^24 chars");
     *total = n;
     return VKX_OK;
@@ -326,23 +308,25 @@ VKX_EXPORT int vkx_char_mask_ellipse_sets_fresh_dev(vkx_ctx *ctx, int internal_s
     if (failed) return VKX_ERR_CHAR_MASK;      // the reference raises: no plane written
 
     // 2. the tile and packed-mask layout
-    std::vector<int> tile_start((size_t)n + 1);
+    auto box_sides = [&](int k, long long &bh, long long &bw) {
+        const int *b = host_boxes.data() + (size_t)5 * k;
+        bh = b[1] - b[0] + 1;
+        bw = b[3] - b[2] + 1;
+    };
     std::vector<long long> packed((size_t)std::max(n, 1));
-    long long tiles = 0;
     for (int s = 0, k = 0; s < n_sets; s++) {
         long long off = 0;
         for (int i = 0; i < sets[s].n_chars; i++, k++) {
-            const int *b = host_boxes.data() + (size_t)5 * k;
-            const long long bh = b[1] - b[0] + 1, bw = b[3] - b[2] + 1;
-            tile_start[k] = (int)tiles;
-            tiles += ((bh + kTile - 1) / kTile) * ((bw + kTile - 1) / kTile);
+            long long bh, bw;
+            box_sides(k, bh, bw);
             packed[k] = off;
             off += bh * bw;
         }
         if (sets[s].char_masks) VKX_REQUIRE(off <= sets[s].char_masks_cap, "char mask buffer too small for the packed masks");
     }
-    tile_start[n] = (int)tiles;
-    VKX_REQUIRE(tiles < (1LL << 31), "too many tiles");
+    std::vector<int> tile_start;
+    VKX_REQUIRE((vkb::box_tile_starts<kTile, kTile>(n, box_sides, tile_start)), "too many tiles");
+    const int tiles = tile_start[n];
 
     // 3. the ownership planes (all zero between calls: the resolve clears what it reads)
     const size_t owner_bytes = sizeof(int) * page * n_sets;

@@ -7,7 +7,7 @@
 // lane writes its pixel -- the 8.8 fixed-point separable blur of the window where the pixel lies on a band, the window's
 // centre everywhere else.  No intermediate page, no second launch, no atomics.
 //
-// The tile table is binned on the host into the blocks (CSR, as k_composite's layers are): a block lists, in table order,
+// The tile table is binned on the host into the blocks (vkb::TileBins of vkx_tile_bins.h): a block lists, in table order,
 // the tiles whose rectangle widened by max(half, ksize / 2) meets it -- every tile that can cover a pixel of its window or
 // put it on a band.  A lane walks that list backwards for the covering tile (the later tile wins) and forwards for the band.
 // The first 32 records of a block's list are staged in LDS; a lane resolves the addresses of all its window pixels from them
@@ -19,6 +19,7 @@
 // banks and split every pixel read in two).  The kernel moves the bytes of a page copy plus the halo, but it is bound by
 // instruction issue (address work per window pixel), not by those bytes: DESIGN.md, 'Image combiner'.
 #include "vkx_internal.h"
+#include "vkx_tile_bins.h"
 
 #include <algorithm>
 #include <cmath>
@@ -191,55 +192,32 @@ VKX_EXPORT int vkx_image_combine_u8c3_dev(vkx_ctx *ctx, const vkx_combine_tile *
         return VKX_ERR_INVALID;
     }
 
-    // bin the tiles into the blocks their widened rectangle meets: counts, prefix sums, fill (table order inside a block)
+    // bin the tiles into the blocks their widened rectangle meets (table order inside a block); refused while the pairs are
+    // counted, before the counting (and the filling) can run long
     const int reach = std::max(half, ksize / 2);
-    const int gw = (int)vkx_blocks(w, kBlockW), gh = (int)vkx_blocks(h, kBlockH);
-    const size_t n_bins = (size_t)gw * gh;
-    auto span = [&](const vkx_combine_tile &t, int &bx0, int &bx1, int &by0, int &by1) {
-        bx0 = std::max(0, t.left - reach) / kBlockW;
-        bx1 = std::min(w - 1, t.right + reach) / kBlockW;
-        by0 = std::max(0, t.up - reach) / kBlockH;
-        by1 = std::min(h - 1, t.down + reach) / kBlockH;
+    vkb::TileBins<kBlockW, kBlockH> bins(h, w);
+    auto span_of = [&](int i) {
+        const vkx_combine_tile &t = tiles_host[i];
+        return bins.rect(std::max(0, t.up - reach), std::min(h - 1, t.down + reach), std::max(0, t.left - reach),
+                         std::min(w - 1, t.right + reach));
     };
-    std::vector<int> start(n_bins + 1, 0);
-    long long entries = 0;
-    for (int i = 0; i < n_tiles; i++) {
-        int bx0, bx1, by0, by1;
-        span(tiles_host[i], bx0, bx1, by0, by1);
-        // refused before the counting (and the filling) can run long: the entries are bounded here, tile by tile
-        entries += (long long)(by1 - by0 + 1) * (bx1 - bx0 + 1);
-        VKX_REQUIRE(entries < kMaxEntries, "tile table too large for its page");
-        for (int by = by0; by <= by1; by++)
-            for (int bx = bx0; bx <= bx1; bx++) start[(size_t)by * gw + bx + 1]++;
-    }
-    long long total = 0;
-    for (size_t b = 0; b < n_bins; b++) {
-        total += start[b + 1];
-        start[b + 1] = (int)total;
-    }
+    VKX_REQUIRE(bins.count(n_tiles, kMaxEntries - 1, span_of), "tile table too large for its page");
     vkx_tables tab(ctx);
-    const size_t off_start = tab.add(sizeof(int) * (n_bins + 1));
-    const size_t off_items = tab.add(sizeof(int) * (size_t)std::max<long long>(total, 1));
+    const size_t off_start = tab.add(sizeof(int) * bins.start.size());
+    const size_t off_items = tab.add(sizeof(int) * std::max<size_t>(bins.pairs(), 1));
     const size_t off_tiles = tab.add(sizeof(CombineTile) * (size_t)std::max(n_tiles, 1));
     int rc = tab.take();
     if (rc) return rc;
-    memcpy(tab.at<int>(off_start), start.data(), sizeof(int) * (n_bins + 1));
-    {
-        std::vector<int> cursor(start.begin(), start.end() - 1);
-        int *items = tab.at<int>(off_items);
-        CombineTile *recs = tab.at<CombineTile>(off_tiles);
-        for (int i = 0; i < n_tiles; i++) {
-            const vkx_combine_tile &t = tiles_host[i];
-            int bx0, bx1, by0, by1;
-            span(t, bx0, bx1, by0, by1);
-            for (int by = by0; by <= by1; by++)
-                for (int bx = bx0; bx <= bx1; bx++) items[cursor[(size_t)by * gw + bx]++] = i;
-            recs[i] = CombineTile{t.up, t.down, t.left, t.right, sources_host[t.source].image, sources_host[t.source].width, 0};
-        }
+    memcpy(tab.at<int>(off_start), bins.start.data(), sizeof(int) * bins.start.size());
+    bins.fill(n_tiles, tab.at<int>(off_items), span_of);
+    CombineTile *recs = tab.at<CombineTile>(off_tiles);
+    for (int i = 0; i < n_tiles; i++) {
+        const vkx_combine_tile &t = tiles_host[i];
+        recs[i] = CombineTile{t.up, t.down, t.left, t.right, sources_host[t.source].image, sources_host[t.source].width, 0};
     }
     if ((rc = tab.copy_to(&ctx->combine_tables, (size_t)256 << 10))) return rc;   // grows (and syncs) rarely
     const unsigned char *base = (const unsigned char *)ctx->combine_tables.ptr;
-    dim3 grid(gw, gh);
+    dim3 grid(bins.tiles_x, bins.tiles_y);
     {
         VKX_TIMED(ctx, "k_image_combine");
         k_image_combine<<<grid, 256, 0, ctx->stream>>>((const int *)(base + off_start), (const int *)(base + off_items),

@@ -7,7 +7,7 @@
 //                 "my positive / negative root lies in [0, 1]", lane 0 adds the two popcounts to the quad's int32 pair.  Integer
 //                 sums: the result does not depend on the order of the atomics.
 //   k_quad_fill   one workgroup per 32 x 8 tile of dst; a pixel keeps dst in a register, walks the quads binned to its tile IN
-//                 LIST ORDER (the host bins them; a tile's list has any length, it is read entry by entry, not in chunks),
+//                 LIST ORDER (the host bins them, vkb::TileBins; a tile's list has any length, it is read entry by entry, not in chunks),
 //                 applies the fill rule of each, then the zeroing plane, and stores once.
 //   k_quad_uv     the raw (u, v) planes of one quad (an arbitrary func_np_uv_to_mat runs on the host).
 //   k_box_masks   the three masks of PageTextLineLabelStep over the same tile bins: one launch.
@@ -17,6 +17,7 @@
 // with -ffp-contract=off: no product below is fused into a sum.  Vector atomics and plain vector stores only.
 #include "vkx_internal.h"
 #include "vkx_poly_raster.h"
+#include "vkx_tile_bins.h"
 
 #include <algorithm>
 #include <cmath>
@@ -29,6 +30,7 @@ constexpr int kMaxSide = 32768;
 constexpr int kMaxQuads = (1 << 24) - 1;
 constexpr int kTileW = 32, kTileH = 8;
 constexpr long long kMaxEntries = 1ll << 28;     // (record, tile) pairs of one call
+typedef vkb::TileBins<kTileW, kTileH> Bins;      // every tile lists its quads, or boxes, in ascending index
 
 struct QuadRec {
     vkp::Edge e[4];                  // of the self-relative integer quad, vertex (i + 3) & 3 -> vertex i
@@ -123,21 +125,13 @@ __global__ void __launch_bounds__(256) k_quad_vote(const QuadRec *__restrict__ r
     }
 }
 
-__device__ __forceinline__ bool tile_pixel(int tiles_x, int h, int w, int &x, int &y)
-{
-    const int t = blockIdx.x, ty = t / tiles_x, tx = t - ty * tiles_x;
-    y = ty * kTileH + (int)threadIdx.x / kTileW;
-    x = tx * kTileW + (int)threadIdx.x % kTileW;
-    return y < h && x < w;
-}
-
 // grid: the tiles of dst
 __global__ void __launch_bounds__(256) k_quad_fill(const QuadRec *__restrict__ recs, const int *__restrict__ tile_start,
                                                    const int *__restrict__ tile_list, const int *__restrict__ votes, int mode, int fresh,
                                                    int h, int w, int tiles_x, float *__restrict__ dst, const uint8_t *__restrict__ zero_where)
 {
     int x, y;
-    if (!tile_pixel(tiles_x, h, w, x, y)) return;
+    if (!vkd::tile_pixel<kTileW, kTileH>(tiles_x, h, w, x, y)) return;
     const int begin = tile_start[blockIdx.x], end = tile_start[blockIdx.x + 1];
     const size_t p = (size_t)y * w + x;
     if (zero_where && zero_where[p] == 0) {             // whatever the quads leave here is zeroed after them
@@ -184,7 +178,7 @@ __global__ void __launch_bounds__(256) k_box_masks(const int4 *__restrict__ boxe
                                                    uint8_t *__restrict__ both_mask)
 {
     int x, y;
-    if (!tile_pixel(tiles_x, h, w, x, y)) return;
+    if (!vkd::tile_pixel<kTileW, kTileH>(tiles_x, h, w, x, y)) return;
     bool text = false, dilated = false;
     for (int i = tile_start[blockIdx.x]; i < tile_start[blockIdx.x + 1]; i++) {
         const int bi = tile_list[i];
@@ -200,37 +194,6 @@ __global__ void __launch_bounds__(256) k_box_masks(const int4 *__restrict__ boxe
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// CSR bins of n rectangles over the 32 x 8 tiles of an h x w plane, every tile's entries in ascending index
-struct Bins {
-    int tiles_x = 0, tiles_y = 0;
-    std::vector<int> start, list;
-    template <class RectOf> bool build(int n, int h, int w, RectOf rect_of)     // rect_of(i, up, left, bh, bw); false: too many pairs
-    {
-        tiles_x = (w + kTileW - 1) / kTileW;
-        tiles_y = (h + kTileH - 1) / kTileH;
-        const size_t n_tiles = (size_t)tiles_x * tiles_y;
-        std::vector<long long> count(n_tiles + 1, 0);
-        auto each = [&](auto visit) {
-            for (int i = 0; i < n; i++) {
-                int up, left, bh, bw;
-                rect_of(i, up, left, bh, bw);
-                for (int ty = up / kTileH; ty <= (up + bh - 1) / kTileH; ty++)
-                    for (int tx = left / kTileW; tx <= (left + bw - 1) / kTileW; tx++) visit((size_t)ty * tiles_x + tx, i);
-            }
-        };
-        long long total = 0;
-        bool ok = true;
-        each([&](size_t t, int) { count[t + 1]++; if (++total > kMaxEntries) ok = false; });
-        if (!ok) return false;
-        start.resize(n_tiles + 1);
-        for (size_t t = 0; t < n_tiles; t++) count[t + 1] += count[t];
-        for (size_t t = 0; t <= n_tiles; t++) start[t] = (int)count[t];
-        list.resize((size_t)total);
-        each([&](size_t t, int i) { list[(size_t)count[t]++] = i; });
-        return true;
-    }
-};
-
 // the record of a quad whose bounding box has been checked
 void make_rec(const vkx_quad &q, QuadRec &r)
 {
@@ -296,23 +259,25 @@ VKX_EXPORT int vkx_quad_interp_fill_dev(vkx_ctx *ctx, const vkx_quad *quads_host
         waves += ((long long)recs[i].bh * recs[i].bw + 63) / 64;
         VKX_REQUIRE(waves < 0x7fffffff, "bounding boxes too large in total");
     }
-    Bins bins;
-    VKX_REQUIRE(bins.build(n_quads, h, w, [&](int i, int &up, int &left, int &bh, int &bw) {
-                    up = recs[i].up; left = recs[i].left; bh = recs[i].bh; bw = recs[i].bw; }),
-                "too many (quad, tile) pairs");
+    Bins bins(h, w);
+    auto span_of = [&](int i) {
+        const QuadRec &r = recs[i];
+        return bins.rect(r.up, r.up + r.bh - 1, r.left, r.left + r.bw - 1);
+    };
+    VKX_REQUIRE(bins.count(n_quads, kMaxEntries, span_of), "too many (quad, tile) pairs");
 
     // one staged block: records, bins, voters and the zeroed vote counts travel as ONE asynchronous copy
     vkx_tables tab(ctx);
     const size_t r_off = tab.add(sizeof(QuadRec) * std::max<size_t>(recs.size(), 1));
     const size_t s_off = tab.add(sizeof(int) * bins.start.size());
-    const size_t l_off = tab.add(sizeof(int) * std::max<size_t>(bins.list.size(), 1));
+    const size_t l_off = tab.add(sizeof(int) * std::max<size_t>(bins.pairs(), 1));
     const size_t v_off = tab.add(sizeof(VoteRec) * std::max<size_t>(voters.size(), 1));
     const size_t c_off = tab.add(sizeof(int) * 2 * std::max<size_t>(recs.size(), 1));
     int rc;
     if ((rc = tab.take())) return rc;
     if (!recs.empty()) memcpy(tab.at<QuadRec>(r_off), recs.data(), sizeof(QuadRec) * recs.size());
     memcpy(tab.at<int>(s_off), bins.start.data(), sizeof(int) * bins.start.size());
-    if (!bins.list.empty()) memcpy(tab.at<int>(l_off), bins.list.data(), sizeof(int) * bins.list.size());
+    bins.fill(n_quads, tab.at<int>(l_off), span_of);
     if (!voters.empty()) memcpy(tab.at<VoteRec>(v_off), voters.data(), sizeof(VoteRec) * voters.size());
     memset(tab.at<int>(c_off), 0, sizeof(int) * 2 * std::max<size_t>(recs.size(), 1));
     if ((rc = tab.copy_to(&ctx->quad_tables, (size_t)64 << 10))) return rc;
@@ -376,24 +341,23 @@ VKX_EXPORT int vkx_box_label_masks_dev(vkx_ctx *ctx, const int32_t *boxes_host, 
         VKX_REQUIRE(b[2] >= 1 && b[3] >= 1 && b[0] >= 0 && b[1] >= 0 && b[0] <= h - b[2] && b[1] <= w - b[3], "a box outside the plane");
     }
     const size_t bytes = (size_t)h * w;
-    uint8_t *const planes[3] = {text_mask, boundary_mask, both_mask};
-    for (int i = 0; i < 3; i++)
-        for (int j = i + 1; j < 3; j++)
-            VKX_REQUIRE(!planes[i] || !planes[j] || !vkx_planes_overlap(planes[i], 1, 0, bytes, planes[j], 1, 0, bytes), "masks overlap");
-    Bins bins;
-    VKX_REQUIRE(bins.build(n, h, w, [&](int i, int &up, int &left, int &bh, int &bw) {
-                    const int32_t *b = boxes_host + 4 * (size_t)i;
-                    up = b[0]; left = b[1]; bh = b[2]; bw = b[3]; }),
-                "too many (box, tile) pairs");
+    const vkx_plane_bytes planes[3] = {{text_mask, bytes}, {boundary_mask, bytes}, {both_mask, bytes}};
+    VKX_REQUIRE(vkx_planes_disjoint(planes, 3), "masks overlap");
+    Bins bins(h, w);
+    auto span_of = [&](int i) {
+        const int32_t *b = boxes_host + 4 * (size_t)i;
+        return bins.rect(b[0], b[0] + b[2] - 1, b[1], b[1] + b[3] - 1);
+    };
+    VKX_REQUIRE(bins.count(n, kMaxEntries, span_of), "too many (box, tile) pairs");
     vkx_tables tab(ctx);
     const size_t b_off = tab.add(sizeof(int32_t) * 4 * std::max(n, 1));
     const size_t s_off = tab.add(sizeof(int) * bins.start.size());
-    const size_t l_off = tab.add(sizeof(int) * std::max<size_t>(bins.list.size(), 1));
+    const size_t l_off = tab.add(sizeof(int) * std::max<size_t>(bins.pairs(), 1));
     int rc;
     if ((rc = tab.take())) return rc;
     if (n) memcpy(tab.at<int32_t>(b_off), boxes_host, sizeof(int32_t) * 4 * (size_t)n);
     memcpy(tab.at<int>(s_off), bins.start.data(), sizeof(int) * bins.start.size());
-    if (!bins.list.empty()) memcpy(tab.at<int>(l_off), bins.list.data(), sizeof(int) * bins.list.size());
+    bins.fill(n, tab.at<int>(l_off), span_of);
     if ((rc = tab.copy_to(&ctx->quad_tables, (size_t)64 << 10))) return rc;
     const unsigned char *base = (const unsigned char *)ctx->quad_tables.ptr;
     { VKX_TIMED(ctx, "k_box_masks"); k_box_masks<<<(unsigned)(bins.tiles_x * bins.tiles_y), 256, 0, ctx->stream>>>((const int4 *)(base + b_off), (const int *)(base + s_off), (const int *)(base + l_off), n_text, h, w, bins.tiles_x, text_mask, boundary_mask, both_mask); }

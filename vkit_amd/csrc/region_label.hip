@@ -3,19 +3,20 @@
 // Two entry points, one launch each:
 //   k_region_label_deviate  the deviate candidates of the char regression labels (:498-575).  One workgroup takes a run of
 //                           chars: one lane per char computes the homography bbox corners -> the polygon's self-relative
-//                           integer points (vkc::perspective_transform, shared with char_mask.hip and char_heatmap.hip) into
-//                           LDS, then one lane per candidate maps its drawn point as affine_points does (float64 H times
-//                           the float32 (x, y, 1) in numpy's matmul order, then the two divisions), adds the box origin,
+//                           integer points (vkc::quad_internals and vkc::perspective_transform, shared with char_mask.hip
+//                           and char_heatmap.hip) into LDS, then one lane per candidate maps its drawn point as
+//                           affine_points does (vkc::affine_point), adds the box origin,
 //                           reports the page status and the rounded point, and compares its squared distance to every
 //                           centre (staged through LDS tiles, exact 64-bit integers) with the distance to its own char's
 //                           centre: keep (own strictly nearest), drop (another strictly nearer) or tie (left to the host).
 //   k_region_label_planes   the char bounding-box mask (the union of the chars' floor / ceil boxes) and the inactive region:
-//                           one workgroup per 32 x 32 page tile; the host bins the boxes into tiles (a tile a box covers whole
-//                           is only flagged), a lane writes 4 pixels: the mask, and 0 into the char mask and the height map
+//                           one workgroup per 32 x 32 page tile; the host bins the boxes into tiles (vkb::TileBins; a tile a
+//                           box covers whole is only flagged and lists nothing), a lane writes 4 pixels: the mask, and 0 into the char mask and the height map
 //                           where the active mask is 0.
 // Every value is written with plain vector stores; no atomics.
 #include "vkx_cell.h"
 #include "vkx_internal.h"
+#include "vkx_tile_bins.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,25 +31,7 @@ constexpr int kMaxSide = 32768;       // page sides: rounded points and their sq
 constexpr int kMaxCandidates = 4096;  // candidates per char
 constexpr long long kMaxCentre = 1LL << 30;
 constexpr int kTile = 32;             // planes: 32 x 32 pixels per workgroup, 4 per lane
-
-__device__ __forceinline__ void affine(const double *H, double x, double y, bool single, double &px, double &py)
-{
-    // affine_np_points: np.matmul(H, (x, y, 1)) then u / w, v / w.  numpy's matmul sums a row as fma(a2, x2, fma(a1, x1,
-    // a0 x0)) (char_mask.hip) over two or more columns; a single column takes its matrix-vector path, which sums
-    // fma(a2, x2, fma(a0, x0, a1 x1)) (tests/test_text_region_label_golden.py pins both against np.matmul)
-    double u, v, q;
-    if (single) {
-        u = fma(H[2], 1.0, fma(H[0], x, H[1] * y));
-        v = fma(H[5], 1.0, fma(H[3], x, H[4] * y));
-        q = fma(H[8], 1.0, fma(H[6], x, H[7] * y));
-    } else {
-        u = fma(H[2], 1.0, fma(H[1], y, H[0] * x));
-        v = fma(H[5], 1.0, fma(H[4], y, H[3] * x));
-        q = fma(H[8], 1.0, fma(H[7], y, H[6] * x));
-    }
-    px = u / q;
-    py = v / q;
-}
+constexpr long long kMaxEntries = 1ll << 28;     // (box, tile) pairs of one call, as quad_interp.hip has it
 
 __global__ void __launch_bounds__(kDevBlock) k_region_label_deviate(const double *__restrict__ quads, const int *__restrict__ boxes,
                                                                    const int2 *__restrict__ centres, int n_centres, int n_chars,
@@ -62,12 +45,8 @@ __global__ void __launch_bounds__(kDevBlock) k_region_label_deviate(const double
     if ((int)threadIdx.x < nc) {
         const int g = c0 + threadIdx.x;
         const double *q = quads + (size_t)g * 8;
-        // Polygon.internals: the INTEGER points round(smooth) as float32, minus their min
-        float ip[8], rel[8];
-        for (int k = 0; k < 8; k++) ip[k] = (float)rint(q[k]);
-        float mx = ip[0], my = ip[1];
-        for (int k = 1; k < 4; k++) { mx = fminf(mx, ip[2 * k]); my = fminf(my, ip[2 * k + 1]); }
-        for (int k = 0; k < 4; k++) { rel[2 * k] = ip[2 * k] - mx; rel[2 * k + 1] = ip[2 * k + 1] - my; }
+        float rel[8];
+        vkc::quad_internals(q, rel);
         const int *b = boxes + (size_t)g * 4;
         const float ex = (float)(b[3] - 1), ey = (float)(b[2] - 1);
         const float src[8] = {0.f, 0.f, ex, 0.f, ex, ey, 0.f, ey};
@@ -90,7 +69,7 @@ __global__ void __launch_bounds__(kDevBlock) k_region_label_deviate(const double
             const double *H = sH[lc];
             const int2 d = draws[(size_t)g * m + j];           // (x, y) in the shifted bounding box
             double px, py;
-            affine(H, (double)d.x, (double)d.y, m == 1, px, py);
+            vkc::affine_point(H, (double)d.x, (double)d.y, m == 1, px, py);
             const int *b = boxes + (size_t)g * 4;
             if (!isfinite(px) || !isfinite(py)) {
                 status = 3;                                     // round() of the point raises
@@ -99,7 +78,7 @@ __global__ void __launch_bounds__(kDevBlock) k_region_label_deviate(const double
                     // PointTuple.from_np_array drops a last point equal (as integers) to the first one
                     const int2 d0 = draws[(size_t)g * m];
                     double px0, py0;
-                    affine(H, (double)d0.x, (double)d0.y, false, px0, py0);
+                    vkc::affine_point(H, (double)d0.x, (double)d0.y, false, px0, py0);
                     if (isfinite(px0) && isfinite(py0) && rint(px0) == rint(px) && rint(py0) == rint(py)) status = 1;
                 }
                 ay = (double)b[0] + py;
@@ -147,9 +126,8 @@ __global__ void __launch_bounds__(256) k_region_label_planes(const int4 *__restr
                                                              uint8_t *__restrict__ box_mask)
 {
     const int t = blockIdx.x;
-    const int x = (t % tiles_x) * kTile + (threadIdx.x & 31);
-    const int y0 = (t / tiles_x) * kTile + (threadIdx.x >> 5);
-    if (x >= w) return;
+    int x, y0;                                                 // 256 lanes: the first 8 rows of the tile
+    if (!vkd::tile_pixel<kTile, kTile>(tiles_x, h, w, x, y0)) return;
     const bool whole = full[t] != 0;
     const int e0 = tile_start[t], e1 = tile_start[t + 1];
     for (int r = 0; r < kTile; r += 8) {
@@ -189,16 +167,11 @@ VKX_EXPORT int vkx_region_label_deviate_dev(vkx_ctx *ctx, const double *quads_ho
     std::vector<int> boxes((size_t)4 * n_chars);
     for (int g = 0; g < n_chars; g++) {
         const double *q = quads_host + (size_t)g * 8;
-        double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-        for (int k = 0; k < 4; k++) {
-            VKX_REQUIRE(std::isfinite(q[2 * k]) && std::isfinite(q[2 * k + 1]), "non-finite char point");
-            VKX_REQUIRE(std::fabs(q[2 * k]) < kMaxCentre && std::fabs(q[2 * k + 1]) < kMaxCentre, "char point outside +-2^30");
-            const double x = std::nearbyint(q[2 * k]), y = std::nearbyint(q[2 * k + 1]);
-            x0 = std::min(x0, x); x1 = std::max(x1, x);
-            y0 = std::min(y0, y); y1 = std::max(y1, y);
-        }
+        double box[4];
+        VKX_REQUIRE(vkx_quad_box(q, box), "non-finite char point");
+        for (int k = 0; k < 8; k++) VKX_REQUIRE(std::fabs(q[k]) < kMaxCentre, "char point outside +-2^30");
         int *b = boxes.data() + (size_t)4 * g;
-        b[0] = (int)y0; b[1] = (int)x0; b[2] = (int)(y1 - y0) + 1; b[3] = (int)(x1 - x0) + 1;
+        for (int k = 0; k < 4; k++) b[k] = (int)box[k];
         VKX_REQUIRE(b[2] >= 3 && b[3] >= 3, "a char box narrower than 3 pixels has no candidates");
         for (int j = 0; j < m; j++) {
             const int32_t *d = draws_host + ((size_t)g * m + j) * 2;
@@ -235,47 +208,45 @@ VKX_EXPORT int vkx_region_label_planes_dev(vkx_ctx *ctx, const int32_t *boxes_ho
     VKX_REQUIRE(n_boxes >= 0 && n_boxes < (1 << 24), "0 .. 2^24 - 1 boxes");
     VKX_REQUIRE(h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide, "page sides 1 .. 32768");
     const size_t page = (size_t)h * w;
-    const void *planes[4] = {active_mask, char_mask, char_height, box_mask};
-    const size_t bytes[4] = {page, page, page * 4, page};
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++)
-            VKX_REQUIRE(!vkx_planes_overlap(planes[a], 1, 0, bytes[a], planes[b], 1, 0, bytes[b]), "planes overlap");
+    const vkx_plane_bytes planes[4] = {{active_mask, page}, {char_mask, page}, {char_height, page * 4}, {box_mask, page}};
+    VKX_REQUIRE(vkx_planes_disjoint(planes, 4), "planes overlap");
     for (int k = 0; k < n_boxes; k++) {
         const int32_t *b = boxes_host + (size_t)4 * k;
         VKX_REQUIRE(0 <= b[0] && b[0] <= b[1] && b[1] < h && 0 <= b[2] && b[2] <= b[3] && b[3] < w, "a box outside the page");
     }
     // bin the boxes into 32 x 32 tiles: a tile a box covers whole is flagged, the others list the box
-    const int tiles_x = (w + kTile - 1) / kTile, tiles_y = (h + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
-    std::vector<int> tile_start((size_t)tiles + 1, 0);
+    vkb::TileBins<kTile, kTile> bins(h, w);
+    const int tiles = (int)bins.n_tiles();
     std::vector<uint8_t> full((size_t)tiles, 0);
-    auto visit = [&](auto &&emit) {
-        for (int k = 0; k < n_boxes; k++) {
-            const int32_t *b = boxes_host + (size_t)4 * k;
-            for (int ty = b[0] / kTile; ty <= b[1] / kTile; ty++) {
-                const int r0 = ty * kTile, r1 = std::min(r0 + kTile, h) - 1;
-                for (int tx = b[2] / kTile; tx <= b[3] / kTile; tx++) {
-                    const int t = ty * tiles_x + tx;
-                    if (full[t]) continue;
-                    const int q0 = tx * kTile, q1 = std::min(q0 + kTile, w) - 1;
-                    emit(t, k, b[0] <= r0 && r1 <= b[1] && b[2] <= q0 && q1 <= b[3]);
-                }
-            }
-        }
+    // the tiles with every row inside lo .. hi: a clipped last tile ends where the page does
+    auto whole = [](int lo, int hi, int len, int &t0, int &t1) {
+        t0 = (lo + kTile - 1) / kTile;
+        t1 = hi == len - 1 ? (len - 1) / kTile : (hi + 1) / kTile - 1;
     };
-    visit([&](int t, int, bool whole) { if (whole) full[t] = 1; });
-    visit([&](int t, int, bool) { tile_start[t + 1]++; });
-    for (int t = 0; t < tiles; t++) tile_start[t + 1] += tile_start[t];
-    std::vector<int> entries((size_t)std::max(tile_start[tiles], 1)), fill(tile_start.begin(), tile_start.end() - 1);
-    visit([&](int t, int k, bool) { entries[fill[t]++] = k; });
+    for (int k = 0; k < n_boxes; k++) {
+        const int32_t *b = boxes_host + (size_t)4 * k;
+        int ty0, ty1, tx0, tx1;
+        whole(b[0], b[1], h, ty0, ty1);
+        whole(b[2], b[3], w, tx0, tx1);
+        for (int ty = ty0; ty <= ty1; ty++)
+            for (int tx = tx0; tx <= tx1; tx++) full[(size_t)ty * bins.tiles_x + tx] = 1;
+    }
+    auto span_of = [&](int k) {
+        const int32_t *b = boxes_host + (size_t)4 * k;
+        return bins.rect(b[0], b[1], b[2], b[3]);
+    };
+    auto listed = [&](size_t t, int) { return !full[t]; };
+    VKX_REQUIRE(bins.count(n_boxes, kMaxEntries, span_of, listed), "too many (box, tile) pairs");
 
     vkx_tables tab(ctx);
     const size_t box_off = tab.add((size_t)n_boxes * 16), start_off = tab.add(((size_t)tiles + 1) * 4);
-    const size_t entry_off = tab.add(entries.size() * 4), full_off = tab.add((size_t)tiles);
+    const size_t entry_off = tab.add(std::max<size_t>(bins.pairs(), 1) * 4), full_off = tab.add((size_t)tiles);
     int rc = tab.take();
     if (rc) return rc;
     if (n_boxes) memcpy(tab.at<int32_t>(box_off), boxes_host, (size_t)n_boxes * 16);
-    memcpy(tab.at<int>(start_off), tile_start.data(), ((size_t)tiles + 1) * 4);
-    memcpy(tab.at<int>(entry_off), entries.data(), entries.size() * 4);
+    memcpy(tab.at<int>(start_off), bins.start.data(), ((size_t)tiles + 1) * 4);
+    *tab.at<int>(entry_off) = 0;                               // (a call without pairs stages one entry)
+    bins.fill(n_boxes, tab.at<int>(entry_off), span_of, listed);
     memcpy(tab.at<uint8_t>(full_off), full.data(), (size_t)tiles);
     if ((rc = tab.copy_to(&ctx->rl_planes, (size_t)64 << 10))) return rc;
     char *base = (char *)ctx->rl_planes.ptr;
@@ -283,7 +254,7 @@ VKX_EXPORT int vkx_region_label_planes_dev(vkx_ctx *ctx, const int32_t *boxes_ho
         VKX_TIMED(ctx, "k_region_label_planes");
         k_region_label_planes<<<(unsigned)tiles, 256, 0, ctx->stream>>>(
             (const int4 *)(base + box_off), (const int *)(base + start_off), (const int *)(base + entry_off),
-            (const uint8_t *)(base + full_off), tiles_x, h, w, active_mask, char_mask, char_height, box_mask);
+            (const uint8_t *)(base + full_off), bins.tiles_x, h, w, active_mask, char_mask, char_height, box_mask);
     }
     VKX_LAUNCH_CHECK();
     return VKX_OK;

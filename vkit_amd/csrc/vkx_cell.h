@@ -295,6 +295,38 @@ __device__ inline void perspective_transform(const float from[8], const float to
     if (!homography_direct(qf, qt, H)) homography_jacobi(from, to, H);
 }
 
+// Polygon.internals of a char quad q ((x, y) of 4 smooth points): PointTuple.to_smooth_np_array holds the INTEGER points
+// round(smooth) as float32 (element/point.py:251); rel is those minus their min, the quad relative to its own bounding box.
+// Shared by the setup passes of char_mask.hip, char_heatmap.hip and region_label.hip.
+__device__ __forceinline__ void quad_internals(const double q[8], float rel[8])
+{
+    float ip[8];
+    for (int k = 0; k < 8; k++) ip[k] = (float)rint(q[k]);
+    float mx = ip[0], my = ip[1];
+    for (int k = 1; k < 4; k++) { mx = fminf(mx, ip[2 * k]); my = fminf(my, ip[2 * k + 1]); }
+    for (int k = 0; k < 4; k++) { rel[2 * k] = ip[2 * k] - mx; rel[2 * k + 1] = ip[2 * k + 1] - my; }
+}
+
+// affine_np_points of one point: np.matmul(H, (x, y, 1)) then u / w, v / w, the float64 H times the float32 coordinates.
+// numpy's matmul sums a row as fma(a2, x2, fma(a1, x1, a0 x0)) over two or more columns; a single column takes its
+// matrix-vector path, which sums fma(a2, x2, fma(a0, x0, a1 x1)) (tests/test_text_region_label_golden.py pins both against
+// np.matmul).  `single`: the point is the only column.
+__device__ __forceinline__ void affine_point(const double *H, double x, double y, bool single, double &px, double &py)
+{
+    double u, v, q;
+    if (single) {
+        u = fma(H[2], 1.0, fma(H[0], x, H[1] * y));
+        v = fma(H[5], 1.0, fma(H[3], x, H[4] * y));
+        q = fma(H[8], 1.0, fma(H[6], x, H[7] * y));
+    } else {
+        u = fma(H[2], 1.0, fma(H[1], y, H[0] * x));
+        v = fma(H[5], 1.0, fma(H[4], y, H[3] * x));
+        q = fma(H[8], 1.0, fma(H[7], y, H[6] * x));
+    }
+    px = u / q;
+    py = v / q;
+}
+
 // Number of minor-axis steps an 8-connected Bresenham line (cv::LineIterator, walked from its left end) has
 // taken after k major steps: ceil((2 k dmin - dmaj) / (2 dmaj)), never negative.
 __device__ __forceinline__ int bres_minor(int k, int dmaj, int dmin)

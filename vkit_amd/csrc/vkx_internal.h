@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <limits.h>
 #include <stdlib.h>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -47,6 +48,34 @@ static inline bool vkx_planes_overlap(const void *a, int a_rows, ptrdiff_t a_pit
     const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (size_t)(a_rows - 1) * (size_t)a_pitch + a_row;
     const uintptr_t b0 = (uintptr_t)b, b1 = b0 + (size_t)(b_rows - 1) * (size_t)b_pitch + b_row;
     return a0 < b1 && b0 < a1;
+}
+// The dense planes a call writes (and the ones it reads beside them): no two may share a byte.  NULL planes are skipped.
+struct vkx_plane_bytes {
+    const void *ptr;
+    size_t bytes;
+};
+static inline bool vkx_planes_disjoint(const vkx_plane_bytes *planes, size_t n)
+{
+    for (size_t a = 0; a < n; a++)
+        for (size_t b = a + 1; b < n; b++)
+            if (planes[a].ptr && planes[b].ptr &&
+                vkx_planes_overlap(planes[a].ptr, 1, 0, planes[a].bytes, planes[b].ptr, 1, 0, planes[b].bytes))
+                return false;
+    return true;
+}
+// Polygon.bounding_box of a char quad ((x, y) of 4 points): box = (up, left, height, width) of the points rounded half to even, still
+// as doubles (exact): the site checks their range before it makes them ints.  False: a non-finite point.
+static inline bool vkx_quad_box(const double q[8], double box[4])
+{
+    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    for (int k = 0; k < 4; k++) {
+        if (!std::isfinite(q[2 * k]) || !std::isfinite(q[2 * k + 1])) return false;
+        const double x = std::nearbyint(q[2 * k]), y = std::nearbyint(q[2 * k + 1]);
+        x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1;
+        y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
+    }
+    box[0] = y0; box[1] = x0; box[2] = y1 - y0 + 1; box[3] = x1 - x0 + 1;
+    return true;
 }
 // for the entry points that cannot run in place
 #define VKX_REQUIRE_DISJOINT(...) \
@@ -313,8 +342,9 @@ __device__ __forceinline__ int reflect101(int p, int len)
     } while ((unsigned)p >= (unsigned)len);
     return p;
 }
-// The last of n >= 1 entries whose prefix is <= t: prefix(i) ascending, prefix(0) <= t.  (Which tile, edge or char owns item t of
-// a launch laid out by a prefix sum; fused.hip and nprand.hip keep their own copies.)
+// The last of n >= 1 entries whose prefix is <= t: prefix(i) ascending, prefix(0) <= t.  (Which edge, quad or glyph owns item t of
+// a launch laid out by a prefix sum; box_tile_pixel below is its use for the tiles of boxes; fused.hip and nprand.hip keep their
+// own copies.)
 template <class Prefix>
 __device__ __forceinline__ int last_at_most(int n, int t, Prefix prefix)
 {
@@ -324,6 +354,28 @@ __device__ __forceinline__ int last_at_most(int n, int t, Prefix prefix)
         if (prefix(mid) <= t) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+// The pixel of a lane where workgroup blockIdx.x is one TW x TH tile of an h x w plane, tiles_x tiles a row (the bins of
+// vkx_tile_bins.h; a workgroup of fewer than TW * TH lanes has the first rows of its tile).  False: outside the plane.
+template <int TW, int TH>
+__device__ __forceinline__ bool tile_pixel(int tiles_x, int h, int w, int &x, int &y)
+{
+    const int t = blockIdx.x, ty = t / tiles_x, tx = t - ty * tiles_x;
+    y = ty * TH + (int)threadIdx.x / TW;
+    x = tx * TW + (int)threadIdx.x % TW;
+    return y < h && x < w;
+}
+// ... where workgroup blockIdx.x is one TW x TH tile of one of n boxes (vkb::box_tile_starts: box g owns tiles tile_start[g] ..
+// tile_start[g + 1]; width_of(g) is its width): the box, and the pixel (rx, ry) inside it -- the caller tests it against the sides.
+template <int TW, int TH, class WidthOf>
+__device__ __forceinline__ int box_tile_pixel(int n, const int *__restrict__ tile_start, WidthOf width_of, int &rx, int &ry)
+{
+    const int t = blockIdx.x;
+    const int g = last_at_most(n, t, [&](int i) { return tile_start[i]; });
+    const int tiles_x = (width_of(g) + TW - 1) / TW, lt = t - tile_start[g];
+    ry = (lt / tiles_x) * TH + (int)threadIdx.x / TW;
+    rx = (lt % tiles_x) * TW + (int)threadIdx.x % TW;
+    return g;
 }
 __device__ __forceinline__ int sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 __device__ __forceinline__ int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
