@@ -400,6 +400,38 @@ def test_abi_refusals():
     del keep
 
 
+def test_seals_at_the_borders_of_the_64_x_4_tiles():
+    """one raw call with a seal of 65 x 5 pixels (two tiles a row, two rows of tiles) and one of 64 x 4 (exactly one tile), an
+    unrotated char in the last rows and columns of each, its glyph resized CUBIC: the restatement's bits"""
+    from vkit_amd import _native as N
+    from vkit_amd.engine.seal_impression.text_line_slot_filler import build_seal_fill_tables
+    ctx = N.default_ctx()
+    rng = np.random.default_rng(65)
+    cases = []
+    for (h, w), (up_y, up_x) in (((5, 65), (2, 62)), ((4, 64), (1, 61))):
+        score = (R.blocky(rng, (3, 8), 1, 1, 5, np.float32) / np.float32(4)).astype(np.float32)       # 8 wide -> 6: aspect 0.75
+        char = dict(box=[0, 2, 0, 7], score=score, image=(score * 255).astype(np.uint8), ref_h=3, ref_w=3)
+        slot = dict(height=3, aspect=0.75, chars=[[270, float(up_y), float(up_x), float(up_y + 3), float(up_x)]])
+        cases.append(dict(seal=dict(h=h, w=w, alpha=0.6, slots=[slot], internal_box=None), indices=[0],
+                          lines=[dict(height=3, width=8, interp=R.INTERPOLATIONS['CUBIC'], chars=[char])], internal=None))
+    chars, seals, planes_host, keep, _, floats = build_seal_fill_tables([amd_items(case, device=True) for case in cases])
+    assert [(int(s['w']), int(s['h'])) for s in seals] == [(65, 5), (64, 4)] and floats == 65 * 5 + 64 * 4
+    assert len(chars) == 2 and chars['identity'].all() and list(chars['seal']) == [0, 1]
+    assert all((int(c['src_h']), int(c['src_w']), int(c['glyph_h']), int(c['plane_w'])) == (3, 8, 3, 6) for c in chars)
+    # each char ends in its seal's last row and column: pixel (4, 64) lies in the fourth tile of the first seal
+    assert [(int(c['dst_up']) + int(c['rot_h']), int(c['dst_left']) + int(c['rot_w'])) for c in chars] == [(5, 65), (4, 64)]
+    dst = ctx.to_device(np.full(floats, 7.0, np.float32))
+    assert raw_call(ctx, chars, seals, planes_host, dst) == 0
+    got = np.array(dst.host())
+    at = 0
+    for case in cases:
+        want = R.fill(case)[0]
+        assert want[-1, -1] > 0 and want[0, 0] == 0
+        assert R.same_bits(got[at:at + want.size].reshape(want.shape), want), want.shape
+        at += want.size
+    del keep
+
+
 def _count(monkeypatch, ctx, call):
     from vkit_amd import _native as N
     syncs = []

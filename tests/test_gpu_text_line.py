@@ -238,6 +238,51 @@ def raw_call(ctx, chars, lines, blob, dst, n_chars=None, n_lines=None, dst_bytes
         dst.nbytes if dst_bytes is None else dst_bytes)
 
 
+def test_lines_at_the_borders_of_the_64_x_4_tiles():
+    """one raw call with an unresized line of 65 x 5 pixels (two tiles a row, two rows of tiles) and a line resized CUBIC from a
+    32 x 2 pasted plane to 64 x 4 (exactly one tile), glyphs in the last rows and columns of both: the restatement's bits"""
+    from vkit_amd import _native as N
+    ctx = N.default_ctx()
+    rng = np.random.default_rng(65)
+    color = (10, 200, 30)
+    # (pasted shape, output shape, the glyph boxes [up, down, left, right] in the pasted plane)
+    layout = (((5, 65), (5, 65), ([0, 4, 0, 29], [1, 4, 55, 64])), ((2, 32), (4, 64), ([0, 1, 0, 14], [1, 1, 16, 31])))
+    chars, lines, parts, wants = [], np.zeros(2, N.TEXT_LINE_DTYPE), [], []
+    blob_bytes = dst_bytes = 0
+    for k, (pasted, out, boxes) in enumerate(layout):
+        glyphs = []
+        for up, down, left, right in boxes:
+            score = (R.blocky(rng, (down - up + 1, right - left + 1), 1, 1, 5) / np.float32(4)).astype(np.float32)
+            glyphs.append(dict(image=(score * 255).astype(np.uint8), score=score))
+            record = np.zeros((), N.TEXT_CHAR_DTYPE)
+            record['glyph_h'], record['glyph_w'], record['line'], record['up'], record['left'] = score.shape[0], score.shape[1], k, up, left
+            record['image_off'], record['score_off'], record['paste_off'] = blob_bytes + score.size * 4, blob_bytes, -1
+            parts += [score.view(np.uint8).reshape(-1), glyphs[-1]['image'].reshape(-1), np.zeros(-score.size % 4, np.uint8)]
+            blob_bytes += sum(p.size for p in parts[-3:])
+            chars.append(record)
+        area = out[0] * out[1]
+        line = lines[k]
+        line['channels'], line['color'], line['has_score'], line['interpolation'] = 1, color, 1, R.INTERPOLATIONS['CUBIC']
+        line['paste_h'], line['paste_w'], line['resized_h'], line['resized_w'], line['out_h'], line['out_w'] = pasted + out + out
+        line['score_off'], line['image_off'], line['mask_off'] = dst_bytes, dst_bytes + 4 * area, dst_bytes + 7 * area
+        dst_bytes += 8 * area
+        case = dict(style=dict(glyph_color=color), hori=True, height=out[0], width=out[1], enlarge=R.INTERPOLATIONS['CUBIC'],
+                    shrink=R.INTERPOLATIONS['AREA'])
+        wants.append(R.render_pixels(glyphs, boxes, pasted, case))
+        assert wants[-1]['mask'].shape == out and wants[-1]['interp'] == R.INTERPOLATIONS['CUBIC']
+        assert wants[-1]['mask'][-1, -1] == 1 and wants[-1]['score'][-1, -1] > 0                    # ink in the last row and column
+    assert (int(lines[1]['resized_h']), int(lines[1]['resized_w'])) != (int(lines[1]['paste_h']), int(lines[1]['paste_w']))
+    dst = ctx.to_device(np.full(dst_bytes, 123, np.uint8))
+    assert raw_call(ctx, np.array(chars, N.TEXT_CHAR_DTYPE), lines, np.concatenate(parts), dst) == 0
+    got = np.array(dst.host())
+    for line, want in zip(lines, wants):
+        h, w = want['mask'].shape
+        image = got[int(line['image_off']):int(line['image_off']) + 3 * h * w].reshape(h, w, 3)
+        mask = got[int(line['mask_off']):int(line['mask_off']) + h * w].reshape(h, w)
+        score = got[int(line['score_off']):int(line['score_off']) + 4 * h * w].view(np.float32).reshape(h, w)
+        assert same_planes((image, mask, score), (want['image'], want['mask'], want['score'])), (h, w)
+
+
 def test_abi_refusals():
     """every refusal of include/vkx.h: VKX_ERR_INVALID and nothing written; the unchanged tables still run and match"""
     from vkit_amd import _native as N

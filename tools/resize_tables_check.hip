@@ -1,8 +1,10 @@
 // Host-side check of the resize plan and table blocks (vkit_amd/csrc/vkx_resize_axes.h): a seeded sweep of geometries, sides
 // 1 .. 300, both dtypes, every interpolation code and some unknown ones, the exact-half and integer-factor cases among them,
 // goes through vkd::plan_resize and the packers as resize.hip, seal_fill.hip and region_flatten.hip use them; every block is
-// written between guard bytes and read back through its view.  Plain host code: it needs no device.  Build with the
-// sanitizers and run:
+// written between guard bytes and read back through its view.  Every geometry also goes, with the five codes of the batched
+// sites on both dtypes and one job of equal shapes, through ONE vkd::ResizePlanner as seal_fill.hip and text_line.hip drive it
+// (plan, layout, pack): between guard bytes each block must be, byte for byte, what the direct packer writes.  Plain host code: it
+// needs no device.  Build with the sanitizers and run (and once more plain, at -O2):
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //       tools/resize_tables_check.hip -o /tmp/resize_tables_check && /tmp/resize_tables_check
 #include "../vkit_amd/csrc/vkx_resize_axes.h"
@@ -11,12 +13,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 
+static char last_error[256];                    // what the library keeps for vkx_last_error
 void vkx_set_error(const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
-    vfprintf(stderr, fmt, ap);
+    vsnprintf(last_error, sizeof(last_error), fmt, ap);
     va_end(ap);
 }
 
@@ -29,6 +33,7 @@ void vkx_set_error(const char *fmt, ...)
     } while (0)
 
 static long long n_plans, n_refused, n_nan_rows, n_blocks[3], n_modes[vkd::M_REFUSED_UNKNOWN + 1];
+static long long n_planner_jobs, n_planner_blocks, n_planner_refused;
 
 // a block of exactly `bytes` between two guards: pack(nullptr) announced the size, pack(address) must fill it and no more
 struct Guarded {
@@ -188,6 +193,82 @@ static void run(bool f32, int code, int sh, int sw, int dh, int dw)
     }
 }
 
+// One planner over every (dtype, code) of the batched sites at this geometry, and one job of equal shapes: what the two entry
+// points do with the resizes of a call.  The blocks lie between guard bytes at the offsets layout() was given.
+static void check_planner(int sh, int sw, int dh, int dw)
+{
+    constexpr size_t kGuard = 64;
+    const int codes[5] = {VKX_INTER_CUBIC, VKX_INTER_AREA, VKX_INTER_LANCZOS4, VKX_INTER_LINEAR_EXACT, VKX_INTER_NEAREST_EXACT};
+    struct Job { vkd::PlannedResize r; bool f32; int code; bool planned; };
+    std::vector<Job> jobs;                      // (sized before the first plan(): the planner keeps the jobs' addresses)
+    for (int code : codes)
+        for (int f32 = 0; f32 < 2; f32++) jobs.push_back(Job{{}, f32 != 0, code, false});
+    jobs.push_back(Job{{}, false, VKX_INTER_AREA, false});                       // equal shapes, below
+    vkd::ResizePlanner planner("check_planner");
+    for (int code = -1; code <= 8; code++) {
+        bool known = false;
+        for (int c : codes) known = known || c == code;
+        CHECK(vkd::ResizePlanner::known_interpolation(code) == known);
+    }
+    for (size_t k = 0; k < jobs.size(); k++) {
+        Job &j = jobs[k];
+        const bool equal = k + 1 == jobs.size();
+        const int th = equal ? sh : dh, tw = equal ? sw : dw;
+        last_error[0] = 0;
+        const int rc = planner.plan(j.r, j.f32, j.code, sh, sw, th, tw);
+        CHECK(j.r.sh == sh && j.r.sw == sw && j.r.dh == th && j.r.dw == tw && j.r.tab_off == 0);
+        if (sh == th && sw == tw) {             // nothing is resized: nothing is planned, whatever the code
+            CHECK(rc == VKX_OK && j.r.plan.mode == vkd::M_COPY);
+            continue;
+        }
+        const vkd::ResizePlan direct = vkd::plan_resize(j.f32, j.code, sh, sw, th, tw);
+        CHECK(direct.mode != vkd::M_REFUSED_UNKNOWN);
+        if (direct.refused()) {                 // an enlarging AREA
+            CHECK(j.code == VKX_INTER_AREA && (tw > sw || th > sh));
+            CHECK(rc == VKX_ERR_INVALID && std::string(last_error) == "check_planner: requirement failed: INTER_AREA is for shrinking only");
+            n_planner_refused++;
+            continue;
+        }
+        CHECK(rc == VKX_OK && last_error[0] == 0 && j.r.plan.mode == direct.mode && j.r.plan.ks == direct.ks);
+        j.planned = true;
+        n_planner_jobs++;
+    }
+    // the layout: every block behind a guard of its own
+    size_t end = kGuard, asked = 0;
+    planner.layout([&](size_t bytes) { CHECK(bytes > 0); const size_t off = end; end = off + bytes + kGuard; asked++; return off; });
+    std::vector<unsigned char> got(end, 0xa5), want(end, 0xa5);
+    planner.pack(got.data());
+    // what the direct packers write, at the same offsets
+    size_t blocks = 0;
+    for (Job &j : jobs) {
+        if (!j.planned) { CHECK(j.r.tab_off == 0); continue; }
+        const vkd::ResizePlan direct = vkd::plan_resize(j.f32, j.code, sh, sw, dh, dw);
+        unsigned char *at = want.data() + j.r.tab_off;
+        int range[4] = {0, 0, 0, 0};
+        size_t bytes = 0;
+        switch (direct.mode) {
+        case vkd::M_TAPS: bytes = vkd::pack_taps(direct.ks, j.f32, sh, sw, dh, dw, nullptr); break;
+        case vkd::M_LINEAR_EXACT_U8: bytes = vkd::pack_linear_exact(sh, sw, dh, dw, nullptr, range); break;
+        case vkd::M_AREA: bytes = vkd::AreaTabs(sh, sw, dh, dw, direct.scale_x, direct.scale_y).pack(nullptr); break;
+        default: break;
+        }
+        if (!bytes) { CHECK(j.r.tab_off == 0); continue; }
+        CHECK(j.r.tab_off >= (long long)kGuard && (size_t)j.r.tab_off + bytes + kGuard <= end);
+        switch (direct.mode) {
+        case vkd::M_TAPS: vkd::pack_taps(direct.ks, j.f32, sh, sw, dh, dw, at); break;
+        case vkd::M_LINEAR_EXACT_U8: vkd::pack_linear_exact(sh, sw, dh, dw, at, range); break;
+        default: vkd::AreaTabs(sh, sw, dh, dw, direct.scale_x, direct.scale_y).pack(at); break;
+        }
+        blocks++;
+        // the plan as the record carries it to the device: a LINEAR_EXACT job holds its ranges once it is packed
+        for (int i = 0; i < 4; i++) CHECK(j.r.plan.p[i] == (direct.mode == vkd::M_LINEAR_EXACT_U8 ? range[i] : direct.p[i]));
+        CHECK(j.r.plan.scale_x == direct.scale_x && j.r.plan.scale_y == direct.scale_y);
+    }
+    CHECK(blocks == asked);
+    CHECK(got == want);                         // every block and every guard byte
+    n_planner_blocks += (long long)blocks;
+}
+
 int main()
 {
     std::mt19937 rng(20240607u);
@@ -207,6 +288,7 @@ int main()
         }
         for (int code : codes)
             for (int f32 = 0; f32 < 2; f32++) run(f32 != 0, code, sh, sw, dh, dw);
+        check_planner(sh, sw, dh, dw);
     }
     // the geometries of the NaN LANCZOS4 coefficient column (one tap saturates to -32768, the others are 0)
     const int nan_geometries[3][4] = {{146, 4, 64, 196}, {127, 1, 202, 197}, {4, 146, 196, 64}};
@@ -218,6 +300,9 @@ int main()
         }
     for (int m = vkd::M_NEAREST; m <= vkd::M_REFUSED_UNKNOWN; m++) CHECK(n_modes[m] > 0);
     CHECK(n_blocks[0] > 0 && n_blocks[1] > 0 && n_blocks[2] > 0);
+    CHECK(n_planner_jobs > 0 && n_planner_blocks > 0 && n_planner_refused > 0);
+    printf("resize planner host check ok: %lld jobs planned, %lld refused, %lld blocks equal to the direct packers'\n", n_planner_jobs,
+           n_planner_refused, n_planner_blocks);
     printf("resize tables host check ok: %lld plans (%lld refused), %lld tap, %lld linear-exact and %lld area blocks\n", n_plans, n_refused,
            n_blocks[0], n_blocks[1], n_blocks[2]);
     return 0;

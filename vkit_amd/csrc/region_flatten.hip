@@ -193,15 +193,6 @@ __global__ void __launch_bounds__(256) k_region_stack(const StackRec *__restrict
     }
 }
 
-// the byte ranges [first, second) of a call's destinations: true when two of them overlap
-bool ranges_overlap(std::vector<std::pair<long long, long long>> &ranges)
-{
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); i++)
-        if (ranges[i].first < ranges[i - 1].second) return true;
-    return false;
-}
-
 // the source planes of a pair and where it writes, against the contract of vkx.h; need_mask: the mask is read even if unwritten
 int check_pair(const uint8_t *src_image, const uint8_t *src_mask, long long image_step, long long mask_step, int sh, int sw,
                int dh, int dw, long long image_off, long long mask_off, bool need_mask, const uint8_t *dst, size_t dst_bytes,
@@ -253,7 +244,7 @@ VKX_EXPORT int vkx_region_warp_dev(vkx_ctx *ctx, const vkx_region_warp_pair *pai
                     "window outside a warped plane of at most 32767 px");
         groups = pair_groups(p.dst_h, p.dst_w, groups);
     }
-    VKX_REQUIRE(!ranges_overlap(ranges), "destinations overlap one another");
+    VKX_REQUIRE(!vkx_ranges_overlap(ranges), "destinations overlap one another");
     vkx_tables tab(ctx);
     int rc;
     if ((rc = tab.take(sizeof(WarpRec) * (size_t)n_pairs))) return rc;
@@ -325,7 +316,7 @@ VKX_EXPORT int vkx_region_resize_dev(vkx_ctx *ctx, const vkx_region_resize_pair 
         tab_off[i] = bytes;
         bytes += (vkd::pack_taps(4, false, p.src_h, p.src_w, p.dst_h, p.dst_w, nullptr) + 15) & ~(size_t)15;
     }
-    VKX_REQUIRE(!ranges_overlap(ranges), "destinations overlap one another");
+    VKX_REQUIRE(!vkx_ranges_overlap(ranges), "destinations overlap one another");
     vkx_tables tab(ctx);
     int rc;
     if ((rc = tab.take(bytes))) return rc;

@@ -119,9 +119,7 @@ VKX_EXPORT int vkx_region_extend_masks_dev(vkx_ctx *ctx, const vkx_region_masks_
         words += (area + 3) >> 2;
         groups = std::max(groups, std::min(kRegionGroups, ((w + 63) / 64) * ((h + 3) / 4)));
     }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); i++)
-        VKX_REQUIRE(ranges[i].first >= ranges[i - 1].second, "destinations overlap one another");
+    VKX_REQUIRE(!vkx_ranges_overlap(ranges), "destinations overlap one another");
     // every polygon in BB-relative coordinates
     vkp::Raster<vkp::kPaintCross> raster;
     VKX_REQUIRE(raster.reserve(total_pts), "too many vertices");

@@ -22,7 +22,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <utility>
 #include <vector>
 
@@ -36,16 +35,15 @@ constexpr unsigned kNanKey = 0xffffffffu;
 struct CharRec {
     const unsigned char *src;
     long long src_step;                         // bytes
-    int src_kind;                               // VKX_SEAL_SRC_F32 / _U8C1 / _U8C3
-    int sh, sw, gh;                             // the glyph is resized to gh x pw
-    vkd::ResizePlan plan;                       // (M_COPY: the source has the glyph's shape)
-    long long tab_off;                          // the char's table block, bytes from the start of the staged block
+    vkd::PlannedResize resize;                  // the glyph -> glyph_h x plane_w (M_COPY: the source has that shape); dw is the plane's width
     long long plane_off;                        // its plane in the plane scratch, floats
-    int ph, pw, glyph_up;
+    int ph, glyph_up;                           // the plane is ph x resize.dw, the glyph in its rows from glyph_up
     int identity;                               // the rotation is a nop: the plane itself is filled
+    int src_kind;                               // VKX_SEAL_SRC_F32 / _U8C1 / _U8C3
     double m[6];                                // CoordAffine's inverse matrix
     int rh, rw, seal, up, left;                 // the rotated plane and where it lands in its seal
 };
+static_assert(sizeof(CharRec) == 176, "k_seal_gather walks these records: no padding, the resize in front of what the gather reads");
 
 struct SealRec {
     long long dst_off;                          // floats
@@ -74,65 +72,8 @@ struct Src {
     }
 };
 
-// CUBIC / LANCZOS4 of a glyph: the tap pixel on the char's tap block
-template <int KS>
-__device__ __forceinline__ void glyph_taps(const Src &s, bool f32, const unsigned char *tab, int sh, int sw, int dh, int dw, int dy, int dx,
-                                           float *vf, uint8_t *vu)
-{
-    if (f32) {
-        const vkd::TapView<float> t(tab, KS, dh, dw);
-        *vf = vkd::taps_pixel_f32<KS>([&](int y, int x) { return s.f(y, x); }, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + KS * dx, t.ycoef + KS * dy);
-    } else {
-        const vkd::TapView<short> t(tab, KS, dh, dw);
-        vkd::taps_pixel_u8<1, KS>([&](int y, int x) { return s.u(y, x); }, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + KS * dx, t.ycoef + KS * dy, vu);
-    }
-}
-
-// One pixel of the resized glyph as the char plane holds it: the pixel of vkx_resize_pixel.h the char's plan names, read through Src.
-__device__ float glyph_pixel(const CharRec &r, const unsigned char *tabs, int dy, int dx)
-{
-    const Src s{r.src, r.src_step, r.src_kind};
-    const bool f32 = r.src_kind == VKX_SEAL_SRC_F32;
-    const int sh = r.sh, sw = r.sw, dh = r.gh, dw = r.pw;
-    const int *p = r.plan.p;
-    const unsigned char *tab = tabs + r.tab_off;
-    float vf = 0.f;
-    uint8_t vu = 0;
-    switch (r.plan.mode) {
-    case vkd::M_COPY:
-        if (f32) return s.f(dy, dx);            // (a matching score map is filled as it is: no clip)
-        vu = (uint8_t)s.u(dy, dx);
-        break;
-    case vkd::M_NEAREST_EXACT: {
-        const int sx = vkd::nearest_exact_index(dx, p[0], p[1], sw), sy = vkd::nearest_exact_index(dy, p[2], p[3], sh);
-        if (f32) vf = s.f(sy, sx); else vu = (uint8_t)s.u(sy, sx);
-        break;
-    }
-    case vkd::M_LINEAR_F32:
-        vf = vkd::linear_pixel_f32([&](int y, int x) { return s.f(y, x); }, sh, sw, dy, dx, r.plan.scale_x, r.plan.scale_y);
-        break;
-    case vkd::M_LINEAR_EXACT_U8:
-        vkd::linear_exact_pixel_u8<1>([&](int y, int below, int x, int) { return s.u(y + below, x); }, vkd::LinearExactView::of(tab, dh, dw), p, dh, dw, dy, dx, &vu);
-        break;
-    case vkd::M_HALF_U8: vkd::half_pixel_u8<1>([&](int y, int x, int) { return s.u(2 * dy + y, 2 * dx + x); }, &vu); break;
-    case vkd::M_TAPS:
-        if (r.plan.ks == 4) glyph_taps<4>(s, f32, tab, sh, sw, dh, dw, dy, dx, &vf, &vu);
-        else glyph_taps<8>(s, f32, tab, sh, sw, dh, dw, dy, dx, &vf, &vu);
-        break;
-    case vkd::M_AREA_FAST:
-        if (f32) vf = vkd::area_fast_f32([&](int y, int x) { return s.f(dy * p[1] + y, dx * p[0] + x); }, p[0], p[1]);
-        else vu = vkd::area_fast_u8([&](int y, int x) { return s.u(dy * p[1] + y, dx * p[0] + x); }, p[0], p[1]);
-        break;
-    default:                                    // M_AREA
-        if (f32) vkd::area_pixel<1, true>([&](int y, int x, int) { return s.f(y, x); }, vkd::AreaView(tab, dh, dw), dy, dx, &vf);
-        else vkd::area_pixel<1, false>([&](int y, int x, int) { return (float)s.u(y, x); }, vkd::AreaView(tab, dh, dw), dy, dx, &vu);
-        break;
-    }
-    if (!f32) return vu > 0 ? 1.f : 0.f;        // Mask.to_resized_mask's `> 0`, then mat.astype(np.float32)
-    return vf < 0.f ? 0.f : (vf > 1.f ? 1.f : vf);   // np.clip(mat, 0, 1) of to_resized_score_map; a NaN stays
-}
-
-// grid: (max(chars, 1), groups); the workgroups of a char stride over the pixels of its plane
+// grid: (max(chars, 1), groups); the workgroups of a char stride over the pixels of its plane.  A pixel of the resized glyph is the
+// char's planned pixel of vkx_resize_pixel.h, read through Src; the source kind is the char's, so it is decided outside the loop.
 __global__ void __launch_bounds__(256) k_seal_planes(const CharRec *__restrict__ recs, int n_chars, const unsigned char *__restrict__ tabs,
                                                      float *__restrict__ planes, unsigned *__restrict__ seal_max, int n_seals)
 {
@@ -140,12 +81,23 @@ __global__ void __launch_bounds__(256) k_seal_planes(const CharRec *__restrict__
         for (int i = threadIdx.x; i < n_seals; i += 256) seal_max[i] = 0u;
     if ((int)blockIdx.x >= n_chars) return;
     const CharRec r = recs[blockIdx.x];
-    const int n = r.ph * r.pw;                  // sides <= 32767: below 2^30
+    const Src s{r.src, r.src_step, r.src_kind};
+    const int n = r.ph * r.resize.dw;           // sides <= 32767: below 2^30
     float *plane = planes + r.plane_off;
-    for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
-        const int y = i / r.pw, x = i - y * r.pw, gy = y - r.glyph_up;
-        plane[i] = (unsigned)gy < (unsigned)r.gh ? glyph_pixel(r, tabs, gy, x) : 0.f;
-    }
+    const auto fill = [&](auto glyph_pixel) {
+        for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) {
+            const int y = i / r.resize.dw, x = i - y * r.resize.dw, gy = y - r.glyph_up;
+            plane[i] = (unsigned)gy < (unsigned)r.resize.dh ? glyph_pixel(gy, x) : 0.f;
+        }
+    };
+    if (r.src_kind == VKX_SEAL_SRC_F32)         // a score map: np.clip(mat, 0, 1) of to_resized_score_map, unless it has the glyph's shape already
+        fill([&](int dy, int dx) { return vkd::planned_pixel_f32(r.resize, tabs, dy, dx, [&](int y, int x) { return s.f(y, x); }); });
+    else
+        fill([&](int dy, int dx) {
+            uint8_t vu;
+            vkd::planned_pixel_u8<1>(r.resize, tabs, dy, dx, [&](int y, int x) { return s.u(y, x); }, &vu);
+            return vu > 0 ? 1.f : 0.f;          // Mask.to_resized_mask's `> 0`, then mat.astype(np.float32)
+        });
 }
 
 // float32 -> a key whose unsigned order is the order of the values; every NaN is the largest key (np.max returns NaN then)
@@ -162,9 +114,9 @@ __device__ __forceinline__ float key_value(unsigned k)
 }
 
 // the seal of a workgroup of the gather and scale grids, and the workgroup's 64 x 4 tile of it
-__device__ __forceinline__ int seal_of_block(const SealRec *seals, int n_seals, int block)
+__device__ __forceinline__ int seal_tile_pixel(const SealRec *seals, int n_seals, int &x, int &y)
 {
-    return vkd::last_at_most(n_seals, block, [&](int i) { return seals[i].first_block; });
+    return vkd::box_tile_pixel<64, 4>(n_seals, [&](int i) { return seals[i].first_block; }, [&](int i) { return seals[i].w; }, x, y);
 }
 
 __global__ void __launch_bounds__(256) k_seal_gather(const CharRec *__restrict__ recs, const SealRec *__restrict__ seals, int n_seals,
@@ -172,10 +124,9 @@ __global__ void __launch_bounds__(256) k_seal_gather(const CharRec *__restrict__
                                                      unsigned *__restrict__ seal_max)
 {
     __shared__ unsigned part[4];
-    const int si = seal_of_block(seals, n_seals, blockIdx.x);
+    int x, y;
+    const int si = seal_tile_pixel(seals, n_seals, x, y);
     const SealRec s = seals[si];
-    const int tiles_x = (s.w + 63) >> 6, t = blockIdx.x - s.first_block;
-    const int x = (t % tiles_x) * 64 + (threadIdx.x & 63), y = (t / tiles_x) * 4 + (threadIdx.x >> 6);
     unsigned key = 0u;                          // below every value's key
     if (x < s.w && y < s.h) {
         float v = 0.f;                          // ScoreMap.from_shape
@@ -185,14 +136,14 @@ __global__ void __launch_bounds__(256) k_seal_gather(const CharRec *__restrict__
             if ((unsigned)ry >= (unsigned)r.rh || (unsigned)rx >= (unsigned)r.rw) continue;
             const float *plane = planes + r.plane_off;
             float q;
-            if (r.identity) q = plane[(ptrdiff_t)ry * r.pw + rx];
+            if (r.identity) q = plane[(ptrdiff_t)ry * r.resize.dw + rx];
             else {
                 vkd::CoordAffine coord;
 #pragma unroll
                 for (int i = 0; i < 6; i++) coord.m[i] = r.m[i];
                 int X, Y;
                 coord(rx, ry, X, Y);
-                q = vkd::sample_f32(plane, r.ph, r.pw, (ptrdiff_t)r.pw, X, Y);
+                q = vkd::sample_f32(plane, r.ph, r.resize.dw, (ptrdiff_t)r.resize.dw, X, Y);
             }
             if (v < q) v = q;                   // fill_np_array(keep_max_value=True): np.putmask(mat, mat < value, value)
         }
@@ -214,10 +165,9 @@ __global__ void __launch_bounds__(256) k_seal_gather(const CharRec *__restrict__
 __global__ void __launch_bounds__(256) k_seal_scale(const SealRec *__restrict__ seals, int n_seals, float *__restrict__ dst,
                                                     const unsigned *__restrict__ seal_max)
 {
-    const int si = seal_of_block(seals, n_seals, blockIdx.x);
+    int x, y;
+    const int si = seal_tile_pixel(seals, n_seals, x, y);
     const SealRec s = seals[si];
-    const int tiles_x = (s.w + 63) >> 6, t = blockIdx.x - s.first_block;
-    const int x = (t % tiles_x) * 64 + (threadIdx.x & 63), y = (t / tiles_x) * 4 + (threadIdx.x >> 6);
     if (x >= s.w || y >= s.h) return;
     const float top = key_value(seal_max[si]);
     float *p = dst + s.dst_off + (ptrdiff_t)y * s.w + x;
@@ -227,22 +177,6 @@ __global__ void __launch_bounds__(256) k_seal_scale(const SealRec *__restrict__ 
 
 bool is_u8(int kind) { return kind == VKX_SEAL_SRC_U8C1 || kind == VKX_SEAL_SRC_U8C3; }
 size_t elem_row_bytes(int kind, int w) { return kind == VKX_SEAL_SRC_F32 ? (size_t)w * 4 : (kind == VKX_SEAL_SRC_U8C3 ? (size_t)w * 3 : (size_t)w); }
-
-bool known_interpolation(int c)
-{
-    return c == VKX_INTER_CUBIC || c == VKX_INTER_AREA || c == VKX_INTER_LANCZOS4 || c == VKX_INTER_LINEAR_EXACT || c == VKX_INTER_NEAREST_EXACT;
-}
-
-// the bytes of a char's table block (none: 0); given an address, the block is written there (and a LINEAR_EXACT plan gets its ranges)
-size_t pack_tables(CharRec &r, bool f32, const vkd::AreaTabs *area, unsigned char *out)
-{
-    switch (r.plan.mode) {
-    case vkd::M_TAPS: return vkd::pack_taps(r.plan.ks, f32, r.sh, r.sw, r.gh, r.pw, out);
-    case vkd::M_LINEAR_EXACT_U8: return vkd::pack_linear_exact(r.sh, r.sw, r.gh, r.pw, out, r.plan.p);
-    case vkd::M_AREA: return area->pack(out);
-    default: return 0;
-    }
-}
 
 }  // namespace
 
@@ -301,12 +235,11 @@ VKX_EXPORT int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, 
         VKX_REQUIRE(blocks + tiles < (1ll << 30), "too many pixels for one call");
         blocks += (int)tiles;
     }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); i++) VKX_REQUIRE(ranges[i].first >= ranges[i - 1].second, "seal destinations overlap one another");
+    VKX_REQUIRE(!vkx_ranges_overlap(ranges), "seal destinations overlap one another");
 
     // chars: checked, planned, and laid out behind the records in one staged block
     std::vector<CharRec> chars(n_chars);
-    std::vector<std::unique_ptr<vkd::AreaTabs>> area(n_chars);   // of the chars whose plan is M_AREA
+    vkd::ResizePlanner planner(__func__);
     vkx_tables tab(ctx);
     const size_t chars_off = tab.add(sizeof(CharRec) * (size_t)std::max(n_chars, 1));
     const size_t seals_off = tab.add(sizeof(SealRec) * (size_t)n_seals);
@@ -325,19 +258,11 @@ VKX_EXPORT int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, 
         VKX_REQUIRE(p.dst_up >= 0 && p.dst_left >= 0 && p.dst_up <= sp.h - p.rot_h && p.dst_left <= sp.w - p.rot_w,
                     "a char destination box outside its seal");
         VKX_REQUIRE(!p.identity || (p.rot_h == p.plane_h && p.rot_w == p.plane_w), "an identity rotation keeps the plane's size");
-        VKX_REQUIRE(known_interpolation(p.interpolation), "unknown interpolation code");
+        VKX_REQUIRE(vkd::ResizePlanner::known_interpolation(p.interpolation), "unknown interpolation code");
         const bool f32 = (p.src_kind & ~VKX_SEAL_SRC_HOST) == VKX_SEAL_SRC_F32;
         r.src = (const unsigned char *)p.src; r.src_step = p.src_step; r.src_kind = p.src_kind;
-        r.sh = p.src_h; r.sw = p.src_w; r.gh = p.glyph_h;
-        r.ph = p.plane_h; r.pw = p.plane_w; r.glyph_up = p.glyph_up;
-        r.tab_off = 0;
-        r.plan = vkd::ResizePlan();
-        if (p.src_h != p.glyph_h || p.src_w != p.plane_w) {
-            r.plan = vkd::plan_resize(f32, p.interpolation, p.src_h, p.src_w, p.glyph_h, p.plane_w);
-            VKX_REQUIRE(!r.plan.refused(), "INTER_AREA is for shrinking only");
-            if (r.plan.mode == vkd::M_AREA) area[i].reset(new vkd::AreaTabs(p.src_h, p.src_w, p.glyph_h, p.plane_w, r.plan.scale_x, r.plan.scale_y));
-            if (const size_t bytes = pack_tables(r, f32, area[i].get(), nullptr)) r.tab_off = (long long)tab.add(bytes);
-        }
+        r.ph = p.plane_h; r.glyph_up = p.glyph_up;
+        if (int rc = planner.plan(r.resize, f32, p.interpolation, p.src_h, p.src_w, p.glyph_h, p.plane_w)) return rc;
         r.identity = p.identity ? 1 : 0;
         double forward[6];
         for (int k = 0; k < 6; k++) forward[k] = (double)p.m[k];
@@ -350,14 +275,12 @@ VKX_EXPORT int vkx_seal_fill_dev(vkx_ctx *ctx, const vkx_seal_char *chars_host, 
         SealRec &s = seals[p.seal];
         if (s.n_chars++ == 0) s.first_char = i;
     }
+    planner.layout([&](size_t bytes) { return tab.add(bytes); });
     const size_t host_off = planes_host_bytes ? tab.add(planes_host_bytes) : 0;
 
     int rc;
     if ((rc = tab.take())) return rc;
-    for (int i = 0; i < n_chars; i++) {
-        CharRec &r = chars[i];
-        if (r.tab_off) pack_tables(r, (r.src_kind & ~VKX_SEAL_SRC_HOST) == VKX_SEAL_SRC_F32, area[i].get(), tab.at<unsigned char>((size_t)r.tab_off));
-    }
+    planner.pack(tab.at<unsigned char>(0));          // (before the records are copied: packing completes the plans)
     if (planes_host_bytes) memcpy(tab.at<unsigned char>(host_off), planes_host, planes_host_bytes);
     // the staged block lands in seal_tables: host sources are addressed there
     if ((rc = vkx_scratch_reserve(ctx, &ctx->seal_tables, std::max(tab.bytes, (size_t)64 << 10)))) return rc;

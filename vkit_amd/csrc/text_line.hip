@@ -23,7 +23,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <utility>
 #include <vector>
 
@@ -32,13 +31,6 @@ namespace {
 constexpr int kMaxChars = 65536, kMaxLines = 4096;
 constexpr int kMaxSide = 32767;
 constexpr int kLdsChars = 64;                   // char records a workgroup holds at a time
-
-// one cv.resize: the plan of vkx_resize_axes.h, its table block (bytes from the start of the staged block) and the two shapes
-struct ResizeJob {
-    vkd::ResizePlan plan;                       // (M_COPY: equal shapes)
-    long long tab_off;
-    int sh, sw, dh, dw;
-};
 
 struct CharRec {
     const uint8_t *image;                       // [gh][gw][cn of its line]
@@ -56,87 +48,13 @@ struct LineRec {
     float *scr;
     uint8_t *s_img, *s_msk;                     // the pasted planes of a resized line (scratch)
     float *s_scr;
-    ResizeJob r_u8, r_f32;                      // the line's resize on uint8 (image, mask) and float32 (score map)
+    vkd::PlannedResize r_u8, r_f32;             // the line's resize on uint8 (image, mask) and float32 (score map)
     int cleanup, t_char, k_char;                // the first trimmed and the last kept char (indices of the char table)
     int tb[4], kb[4];                           // their boxes in the padded plane: up, left, height, width
-    ResizeJob r_t, r_k;                         // the trimmed glyph's mask -> its box (uint8); the kept glyph's score map -> its box
+    vkd::PlannedResize r_t, r_k;                // the trimmed glyph's mask -> its box (uint8); the kept glyph's score map -> its box
 };
 
 struct TileJob { int line, first_block; };      // the 64 x 4 tiles of a line's domain start at first_block
-
-// One resized uint8 pixel of CN channels: the pixel of vkx_resize_pixel.h the plan names.  px(y, b): byte b = x * CN + c of row y.
-template <int CN, class Px>
-__device__ void resize_u8(const ResizeJob &j, const unsigned char *tabs, int dy, int dx, Px px, uint8_t *out)
-{
-    const int sh = j.sh, sw = j.sw, dh = j.dh, dw = j.dw;
-    const int *p = j.plan.p;
-    const unsigned char *tab = tabs + j.tab_off;
-    switch (j.plan.mode) {
-    case vkd::M_COPY:
-#pragma unroll
-        for (int c = 0; c < CN; c++) out[c] = (uint8_t)px(dy, dx * CN + c);
-        break;
-    case vkd::M_NEAREST_EXACT: {
-        const int sx = vkd::nearest_exact_index(dx, p[0], p[1], sw), sy = vkd::nearest_exact_index(dy, p[2], p[3], sh);
-#pragma unroll
-        for (int c = 0; c < CN; c++) out[c] = (uint8_t)px(sy, sx * CN + c);
-        break;
-    }
-    case vkd::M_LINEAR_EXACT_U8:
-        vkd::linear_exact_pixel_u8<CN>([&](int y, int below, int x, int c) { return (unsigned)px(y + below, x * CN + c); },
-                                       vkd::LinearExactView::of(tab, dh, dw), p, dh, dw, dy, dx, out);
-        break;
-    case vkd::M_HALF_U8: vkd::half_pixel_u8<CN>([&](int y, int x, int c) { return px(2 * dy + y, (2 * dx + x) * CN + c); }, out); break;
-    case vkd::M_TAPS:
-        if (j.plan.ks == 4) {
-            const vkd::TapView<short> t(tab, 4, dh, dw);
-            vkd::taps_pixel_u8<CN, 4>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 4 * dx, t.ycoef + 4 * dy, out);
-        } else {
-            const vkd::TapView<short> t(tab, 8, dh, dw);
-            vkd::taps_pixel_u8<CN, 8>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 8 * dx, t.ycoef + 8 * dy, out);
-        }
-        break;
-    case vkd::M_AREA_FAST:
-#pragma unroll
-        for (int c = 0; c < CN; c++)
-            out[c] = vkd::area_fast_u8([&](int y, int x) { return px(dy * p[1] + y, (dx * p[0] + x) * CN + c); }, p[0], p[1]);
-        break;
-    default:                                    // M_AREA
-        vkd::area_pixel<CN, false>([&](int y, int x, int c) { return (float)px(y, x * CN + c); }, vkd::AreaView(tab, dh, dw), dy, dx, out);
-        break;
-    }
-}
-
-// ... and one float32 pixel, as ScoreMap.to_resized_score_map leaves it: clipped to [0, 1] unless nothing was resized.  px(y, x).
-template <class Px>
-__device__ float resize_f32(const ResizeJob &j, const unsigned char *tabs, int dy, int dx, Px px)
-{
-    const int sh = j.sh, sw = j.sw, dh = j.dh, dw = j.dw;
-    const int *p = j.plan.p;
-    const unsigned char *tab = tabs + j.tab_off;
-    float v = 0.f;
-    switch (j.plan.mode) {
-    case vkd::M_COPY: return px(dy, dx);
-    case vkd::M_NEAREST_EXACT:
-        v = px(vkd::nearest_exact_index(dy, p[2], p[3], sh), vkd::nearest_exact_index(dx, p[0], p[1], sw));
-        break;
-    case vkd::M_LINEAR_F32: v = vkd::linear_pixel_f32(px, sh, sw, dy, dx, j.plan.scale_x, j.plan.scale_y); break;
-    case vkd::M_TAPS:
-        if (j.plan.ks == 4) {
-            const vkd::TapView<float> t(tab, 4, dh, dw);
-            v = vkd::taps_pixel_f32<4>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 4 * dx, t.ycoef + 4 * dy);
-        } else {
-            const vkd::TapView<float> t(tab, 8, dh, dw);
-            v = vkd::taps_pixel_f32<8>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 8 * dx, t.ycoef + 8 * dy);
-        }
-        break;
-    case vkd::M_AREA_FAST: v = vkd::area_fast_f32([&](int y, int x) { return px(dy * p[1] + y, dx * p[0] + x); }, p[0], p[1]); break;
-    default:                                    // M_AREA
-        vkd::area_pixel<1, true>([&](int y, int x, int) { return px(y, x); }, vkd::AreaView(tab, dh, dw), dy, dx, &v);
-        break;
-    }
-    return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);      // np.clip(mat, 0, 1); a NaN stays
-}
 
 // What an LCD glyph pastes at gamma 1 (reference :362-366): ((1 - v / 255.0) * 255).astype(uint8) in float64, as numpy computes it.
 // That is NOT 255 - v: 1 - v / 255.0 rounds, and for 50 of the 256 values the product falls just below the integer (v = 43 gives
@@ -167,7 +85,7 @@ __device__ void cleanup_pixel(const LineRec &L, const CharRec *__restrict__ char
         const CharRec t = chars[L.t_char];
         uint8_t ink;
         const int cn = L.cn;
-        resize_u8<1>(L.r_t, tabs, ty, tx, [&](int yy, int xx) { return glyph_ink(t, cn, yy, xx); }, &ink);
+        vkd::planned_pixel_u8<1>(L.r_t, tabs, ty, tx, [&](int yy, int xx) { return glyph_ink(t, cn, yy, xx); }, &ink);
         if (ink > 0) { img[0] = img[1] = img[2] = 255; m = 0; }
         if (L.has_score) s = 0.f;
     }
@@ -175,7 +93,7 @@ __device__ void cleanup_pixel(const LineRec &L, const CharRec *__restrict__ char
     const int ky = y - L.kb[0], kx = x - L.kb[1];
     if ((unsigned)ky < (unsigned)L.kb[2] && (unsigned)kx < (unsigned)L.kb[3]) {
         const CharRec k = chars[L.k_char];
-        const float q = resize_f32(L.r_k, tabs, ky, kx, [&](int yy, int xx) { return k.score[(ptrdiff_t)yy * k.gw + xx]; });
+        const float q = vkd::planned_pixel_f32(L.r_k, tabs, ky, kx, [&](int yy, int xx) { return k.score[(ptrdiff_t)yy * k.gw + xx]; });
         if (s < q) s = q;                       // keep_max_value: np.putmask(mat, mat < value, value)
     }
 }
@@ -189,9 +107,12 @@ __device__ __forceinline__ void store_pixel(const LineRec &L, int y, int x, cons
     if (L.has_score) L.scr[at] = s;
 }
 
-__device__ __forceinline__ int job_of_block(const TileJob *jobs, int n_jobs, int block)
+// the line of a workgroup of either grid: its tile job, and the workgroup's 64 x 4 tile of the domain width_of(L) wide
+template <class WidthOf>
+__device__ __forceinline__ const LineRec &line_tile_pixel(const LineRec *lines, const TileJob *jobs, int n_jobs, WidthOf width_of, int &x, int &y)
 {
-    return vkd::last_at_most(n_jobs, block, [&](int i) { return jobs[i].first_block; });
+    const int j = vkd::box_tile_pixel<64, 4>(n_jobs, [&](int i) { return jobs[i].first_block; }, [&](int i) { return width_of(lines[jobs[i].line]); }, x, y);
+    return lines[jobs[j].line];
 }
 
 // grid: the 64 x 4 tiles of every line's domain -- the pasted plane of a resized line, the output of any other
@@ -201,11 +122,9 @@ __global__ void __launch_bounds__(256) k_text_paste(const LineRec *__restrict__ 
 {
     __shared__ CharRec held[kLdsChars];
     if (n_jobs == 0) return;
-    const TileJob job = jobs[job_of_block(jobs, n_jobs, blockIdx.x)];
-    const LineRec &L = lines[job.line];
+    int x, y;
+    const LineRec &L = line_tile_pixel(lines, jobs, n_jobs, [](const LineRec &l) { return l.resized ? l.pw : l.ow; }, x, y);
     const int dom_h = L.resized ? L.ph : L.oh, dom_w = L.resized ? L.pw : L.ow;
-    const int tiles_x = (dom_w + 63) >> 6, t = blockIdx.x - job.first_block;
-    const int x = (t % tiles_x) * 64 + (threadIdx.x & 63), y = (t / tiles_x) * 4 + (threadIdx.x >> 6);
     const bool live = x < dom_w && y < dom_h;
     // the pixel of the pasted plane this lane forms
     const int py = L.resized ? y : y - L.pad_up, px = L.resized ? x : x - L.pad_left;
@@ -256,10 +175,8 @@ __global__ void __launch_bounds__(256) k_text_resize(const LineRec *__restrict__
                                                      const TileJob *__restrict__ jobs, int n_jobs, const unsigned char *__restrict__ tabs)
 {
     if (n_jobs == 0) return;
-    const TileJob job = jobs[job_of_block(jobs, n_jobs, blockIdx.x)];
-    const LineRec &L = lines[job.line];
-    const int tiles_x = (L.ow + 63) >> 6, t = blockIdx.x - job.first_block;
-    const int x = (t % tiles_x) * 64 + (threadIdx.x & 63), y = (t / tiles_x) * 4 + (threadIdx.x >> 6);
+    int x, y;
+    const LineRec &L = line_tile_pixel(lines, jobs, n_jobs, [](const LineRec &l) { return l.ow; }, x, y);
     if (x >= L.ow || y >= L.oh) return;
     uint8_t img[3] = {255, 255, 255}, m = 0;
     float s = 0.f;
@@ -268,36 +185,14 @@ __global__ void __launch_bounds__(256) k_text_resize(const LineRec *__restrict__
         const uint8_t *s_img = L.s_img, *s_msk = L.s_msk;
         const float *s_scr = L.s_scr;
         const int pw = L.pw;
-        resize_u8<3>(L.r_u8, tabs, ry, rx, [&](int yy, int b) { return (int)s_img[(ptrdiff_t)yy * 3 * pw + b]; }, img);
+        vkd::planned_pixel_u8<3>(L.r_u8, tabs, ry, rx, [&](int yy, int b) { return (int)s_img[(ptrdiff_t)yy * 3 * pw + b]; }, img);
         uint8_t ink;                            // Mask.to_resized_mask: (mask * 255) resized, > 0
-        resize_u8<1>(L.r_u8, tabs, ry, rx, [&](int yy, int xx) { return s_msk[(ptrdiff_t)yy * pw + xx] ? 255 : 0; }, &ink);
+        vkd::planned_pixel_u8<1>(L.r_u8, tabs, ry, rx, [&](int yy, int xx) { return s_msk[(ptrdiff_t)yy * pw + xx] ? 255 : 0; }, &ink);
         m = ink > 0 ? 1 : 0;
-        if (L.has_score) s = resize_f32(L.r_f32, tabs, ry, rx, [&](int yy, int xx) { return s_scr[(ptrdiff_t)yy * pw + xx]; });
+        if (L.has_score) s = vkd::planned_pixel_f32(L.r_f32, tabs, ry, rx, [&](int yy, int xx) { return s_scr[(ptrdiff_t)yy * pw + xx]; });
     }
     if (L.cleanup) cleanup_pixel(L, chars, tabs, y, x, img, m, s);
     store_pixel(L, y, x, img, m, s);
-}
-
-bool known_interpolation(int c)
-{
-    return c == VKX_INTER_CUBIC || c == VKX_INTER_AREA || c == VKX_INTER_LANCZOS4 || c == VKX_INTER_LINEAR_EXACT || c == VKX_INTER_NEAREST_EXACT;
-}
-
-// A resize to be planned: its job, whether it runs on float32, and the AREA tables when its plan needs them
-struct Planned {
-    ResizeJob *job;
-    bool f32;
-    std::unique_ptr<vkd::AreaTabs> area;
-};
-
-size_t pack_tables(ResizeJob &j, bool f32, const vkd::AreaTabs *area, unsigned char *out)
-{
-    switch (j.plan.mode) {
-    case vkd::M_TAPS: return vkd::pack_taps(j.plan.ks, f32, j.sh, j.sw, j.dh, j.dw, out);
-    case vkd::M_LINEAR_EXACT_U8: return vkd::pack_linear_exact(j.sh, j.sw, j.dh, j.dw, out, j.plan.p);
-    case vkd::M_AREA: return area->pack(out);
-    default: return 0;
-    }
 }
 
 }  // namespace
@@ -316,10 +211,9 @@ VKX_EXPORT int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host,
     std::vector<LineRec> lines(n_lines);
     std::vector<CharRec> chars(n_chars);
     std::vector<TileJob> paste_jobs(n_lines), resize_jobs;
-    std::vector<Planned> planned;
+    vkd::ResizePlanner planner(__func__);
     std::vector<std::pair<long long, long long>> ranges;
     long long paste_blocks = 0, resize_blocks = 0, scratch_bytes = 0;
-    planned.reserve(4 * (size_t)n_lines);
 
     // the first and the number of chars of every line: the chars of a line are consecutive (ascending `line`)
     std::vector<int> first_char(n_lines, 0), count(n_lines, 0);
@@ -329,17 +223,6 @@ VKX_EXPORT int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host,
         VKX_REQUIRE(i == 0 || line >= chars_host[i - 1].line, "chars not grouped by ascending line");
         if (count[line]++ == 0) first_char[line] = i;
     }
-
-    auto plan = [&](ResizeJob &j, bool f32, int interpolation, int sh, int sw, int dh, int dw) -> int {
-        j.plan = vkd::ResizePlan();
-        j.tab_off = 0; j.sh = sh; j.sw = sw; j.dh = dh; j.dw = dw;
-        if (sh == dh && sw == dw) return VKX_OK;
-        j.plan = vkd::plan_resize(f32, interpolation, sh, sw, dh, dw);
-        VKX_REQUIRE(!j.plan.refused(), "INTER_AREA is for shrinking only");
-        planned.push_back(Planned{&j, f32, nullptr});
-        if (j.plan.mode == vkd::M_AREA) planned.back().area.reset(new vkd::AreaTabs(sh, sw, dh, dw, j.plan.scale_x, j.plan.scale_y));
-        return VKX_OK;
-    };
 
     for (int i = 0; i < n_lines; i++) {
         const vkx_text_line &p = lines_host[i];
@@ -351,7 +234,7 @@ VKX_EXPORT int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host,
         VKX_REQUIRE(p.resized_h >= 1 && p.resized_w >= 1 && p.resized_h <= kMaxSide && p.resized_w <= kMaxSide, "resized plane side outside 1 .. 32767");
         VKX_REQUIRE(p.out_h >= 1 && p.out_w >= 1 && p.out_h <= kMaxSide && p.out_w <= kMaxSide, "output side outside 1 .. 32767");
         VKX_REQUIRE(p.pad_up >= 0 && p.pad_left >= 0 && p.pad_up <= kMaxSide && p.pad_left <= kMaxSide, "pad outside 0 .. 32767");
-        VKX_REQUIRE(known_interpolation(p.interpolation), "unknown interpolation code");
+        VKX_REQUIRE(vkd::ResizePlanner::known_interpolation(p.interpolation), "unknown interpolation code");
         VKX_REQUIRE((p.has_score != 0) == (p.channels == 1), "a 1-channel line has a score map, an LCD line has none");
         L.cn = p.channels;
         for (int c = 0; c < 3; c++) L.color[c] = p.color[c];
@@ -375,14 +258,14 @@ VKX_EXPORT int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host,
         }
 
         int rc;
-        if ((rc = plan(L.r_u8, false, p.interpolation, p.paste_h, p.paste_w, p.resized_h, p.resized_w))) return rc;
-        if ((rc = plan(L.r_f32, true, p.interpolation, p.paste_h, p.paste_w, p.resized_h, p.resized_w))) return rc;
+        if ((rc = planner.plan(L.r_u8, false, p.interpolation, p.paste_h, p.paste_w, p.resized_h, p.resized_w))) return rc;
+        if ((rc = planner.plan(L.r_f32, true, p.interpolation, p.paste_h, p.paste_w, p.resized_h, p.resized_w))) return rc;
 
         // the clean-up of a trimmed char
         L.cleanup = p.cleanup ? 1 : 0;
         L.t_char = L.k_char = L.first_char;
         for (int k = 0; k < 4; k++) L.tb[k] = L.kb[k] = 0;
-        L.r_t = L.r_k = ResizeJob{vkd::ResizePlan(), 0, 1, 1, 1, 1};
+        L.r_t = L.r_k = vkd::PlannedResize{vkd::ResizePlan(), 0, 1, 1, 1, 1};
         if (L.cleanup) {
             VKX_REQUIRE(p.trimmed_char >= 0 && p.trimmed_char < count[i] && p.kept_char >= 0 && p.kept_char < count[i],
                         "clean-up char outside its line");
@@ -394,8 +277,8 @@ VKX_EXPORT int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host,
             VKX_REQUIRE(p.kept_box[0] + p.kept_box[2] <= p.out_h && p.kept_box[1] + p.kept_box[3] <= p.out_w, "kept char box outside its line");
             L.t_char = L.first_char + p.trimmed_char; L.k_char = L.first_char + p.kept_char;
             const vkx_text_char &t = chars_host[L.t_char], &k = chars_host[L.k_char];
-            if ((rc = plan(L.r_t, false, p.interpolation, t.glyph_h, t.glyph_w, p.trimmed_box[2], p.trimmed_box[3]))) return rc;
-            if (L.has_score && (rc = plan(L.r_k, true, p.interpolation, k.glyph_h, k.glyph_w, p.kept_box[2], p.kept_box[3]))) return rc;
+            if ((rc = planner.plan(L.r_t, false, p.interpolation, t.glyph_h, t.glyph_w, p.trimmed_box[2], p.trimmed_box[3]))) return rc;
+            if (L.has_score && (rc = planner.plan(L.r_k, true, p.interpolation, k.glyph_h, k.glyph_w, p.kept_box[2], p.kept_box[3]))) return rc;
         }
 
         // the tiles of the two grids; the scratch planes of a resized line (offsets for now)
@@ -414,8 +297,7 @@ VKX_EXPORT int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host,
         }
         VKX_REQUIRE(paste_blocks < (1ll << 30) && resize_blocks < (1ll << 30) && scratch_bytes < (1ll << 40), "too many pixels for one call");
     }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); i++) VKX_REQUIRE(ranges[i].first >= ranges[i - 1].second, "line destinations overlap one another");
+    VKX_REQUIRE(!vkx_ranges_overlap(ranges), "line destinations overlap one another");
 
     for (int i = 0; i < n_chars; i++) {
         const vkx_text_char &p = chars_host[i];
@@ -435,15 +317,13 @@ VKX_EXPORT int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host,
     const size_t chars_off = tab.add(sizeof(CharRec) * (size_t)n_chars);
     const size_t pjobs_off = tab.add(sizeof(TileJob) * (size_t)n_lines);
     const size_t rjobs_off = tab.add(sizeof(TileJob) * std::max(resize_jobs.size(), (size_t)1));
-    for (auto &q : planned)
-        if (const size_t bytes = pack_tables(*q.job, q.f32, q.area.get(), nullptr)) q.job->tab_off = (long long)tab.add(bytes);
+    planner.layout([&](size_t bytes) { return tab.add(bytes); });
     const size_t lcd_off = tab.add(256);
     const size_t blob_off = tab.add(blob_bytes);
 
     int rc;
     if ((rc = tab.take())) return rc;
-    for (auto &q : planned)
-        if (q.job->tab_off) pack_tables(*q.job, q.f32, q.area.get(), tab.at<unsigned char>((size_t)q.job->tab_off));
+    planner.pack(tab.at<unsigned char>(0));          // (before the records are copied: packing completes the plans)
     fill_lcd_values(tab.at<uint8_t>(lcd_off));
     memcpy(tab.at<unsigned char>(blob_off), blob_host, blob_bytes);
     if ((rc = vkx_scratch_reserve(ctx, &ctx->text_tables, std::max(tab.bytes, (size_t)256 << 10)))) return rc;

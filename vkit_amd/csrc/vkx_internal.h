@@ -5,8 +5,10 @@
 #include <stddef.h>
 #include <limits.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <cmath>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/vkx.h"
@@ -25,10 +27,12 @@ void vkx_set_error(const char *fmt, ...);
         }                                                                                  \
     } while (0)
 
+// (the text of a refused requirement; vkd::ResizePlanner reports one in the name of its entry point)
+#define VKX_REQUIRE_FORMAT "%s: requirement failed: %s"
 #define VKX_REQUIRE(cond, msg)                                     \
     do {                                                           \
         if (!(cond)) {                                             \
-            vkx_set_error("%s: requirement failed: %s", __func__, msg); \
+            vkx_set_error(VKX_REQUIRE_FORMAT, __func__, msg);      \
             return VKX_ERR_INVALID;                                \
         }                                                          \
     } while (0)
@@ -76,6 +80,14 @@ static inline bool vkx_quad_box(const double q[8], double box[4])
     }
     box[0] = y0; box[1] = x0; box[2] = y1 - y0 + 1; box[3] = x1 - x0 + 1;
     return true;
+}
+// The destinations [first, second) of a batched call, in the unit of its offsets: true when two of them overlap (sorts the list).
+static inline bool vkx_ranges_overlap(std::vector<std::pair<long long, long long>> &ranges)
+{
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); i++)
+        if (ranges[i].first < ranges[i - 1].second) return true;
+    return false;
 }
 // for the entry points that cannot run in place
 #define VKX_REQUIRE_DISJOINT(...) \
@@ -365,17 +377,24 @@ __device__ __forceinline__ bool tile_pixel(int tiles_x, int h, int w, int &x, in
     x = tx * TW + (int)threadIdx.x % TW;
     return y < h && x < w;
 }
-// ... where workgroup blockIdx.x is one TW x TH tile of one of n boxes (vkb::box_tile_starts: box g owns tiles tile_start[g] ..
-// tile_start[g + 1]; width_of(g) is its width): the box, and the pixel (rx, ry) inside it -- the caller tests it against the sides.
-template <int TW, int TH, class WidthOf>
-__device__ __forceinline__ int box_tile_pixel(int n, const int *__restrict__ tile_start, WidthOf width_of, int &rx, int &ry)
+// ... where workgroup blockIdx.x is one TW x TH tile of one of n boxes: box g owns the tiles from first_tile(g) up to first_tile(g + 1)
+// (a prefix the caller holds in its records) and width_of(g) is its width.  Returns the box, and the pixel (rx, ry) inside it -- the
+// caller tests it against the sides.
+template <int TW, int TH, class FirstTile, class WidthOf>
+__device__ __forceinline__ int box_tile_pixel(int n, FirstTile first_tile, WidthOf width_of, int &rx, int &ry)
 {
     const int t = blockIdx.x;
-    const int g = last_at_most(n, t, [&](int i) { return tile_start[i]; });
-    const int tiles_x = (width_of(g) + TW - 1) / TW, lt = t - tile_start[g];
+    const int g = last_at_most(n, t, first_tile);
+    const int tiles_x = (width_of(g) + TW - 1) / TW, lt = t - first_tile(g);
     ry = (lt / tiles_x) * TH + (int)threadIdx.x / TW;
     rx = (lt % tiles_x) * TW + (int)threadIdx.x % TW;
     return g;
+}
+// ... the prefix an array (vkb::box_tile_starts)
+template <int TW, int TH, class WidthOf>
+__device__ __forceinline__ int box_tile_pixel(int n, const int *__restrict__ tile_start, WidthOf width_of, int &rx, int &ry)
+{
+    return box_tile_pixel<TW, TH>(n, [&](int i) { return tile_start[i]; }, width_of, rx, ry);
 }
 __device__ __forceinline__ int sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 __device__ __forceinline__ int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }

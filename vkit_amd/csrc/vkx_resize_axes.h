@@ -1,7 +1,9 @@
 // The host half of cv.resize, stated once for every site that resizes (resize.hip, the batched glyph resize of seal_fill.hip, the
 // batched region resize of region_flatten.hip): the axis tables (bit for bit oracle/vkx_oracle.c's), the rule that routes a
 // request to a kernel (plan_resize), and the blocks the tables travel to the device in -- a packer that writes a block and the
-// view a kernel, or the host that launches it, reads the block through.  The device half is vkx_resize_pixel.h.
+// view a kernel, or the host that launches it, reads the block through.  The batched record kernels (seal_fill.hip, text_line.hip)
+// carry a resize as a PlannedResize and plan, lay out and pack all of a call's with one ResizePlanner.  The device half is
+// vkx_resize_pixel.h.
 #pragma once
 #include "vkx_internal.h"
 
@@ -10,6 +12,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 namespace vkd {
@@ -259,6 +262,78 @@ struct AreaTabs {
         out = put_array(put_array(out, x.si.data(), x.si.size()), y.si.data(), y.si.size());
         put_array(put_array(out, x.alpha.data(), x.alpha.size()), y.alpha.data(), y.alpha.size());
         return bytes;
+    }
+};
+
+// ---- one cv.resize of a batched call as its record carries it: the plan, where its table block lies and the two shapes.  The
+// device reads it through planned_pixel_u8 / planned_pixel_f32 of vkx_resize_pixel.h.
+struct PlannedResize {
+    ResizePlan plan;                     // (M_COPY: equal shapes, nothing is resized)
+    long long tab_off;                   // its table block, bytes from the start of the staged block (no block: 0)
+    int sh, sw, dh, dw;
+};
+
+// All the resizes of one batched call.  plan() every job while the records are checked; layout() once, where the table blocks
+// belong in the staged block; pack() once the block is taken.  The planner keeps the ADDRESS of every job, so the records stay
+// where they are between plan() and pack() -- and they are copied to the staged block only AFTER pack(): packing a LINEAR_EXACT
+// block is what writes the range ends into plan.p.
+class ResizePlanner {
+    struct Item {
+        PlannedResize *job;
+        bool f32;
+        size_t bytes;                    // of its block, set by layout()
+        std::unique_ptr<AreaTabs> area;  // M_AREA only
+    };
+    std::vector<Item> items;
+    const char *entry;                   // the entry point a refusal is reported for
+
+    // the bytes of a job's table block (none: 0); given an address, the block is written there
+    static size_t pack_block(const Item &it, unsigned char *out)
+    {
+        PlannedResize &j = *it.job;
+        switch (j.plan.mode) {
+        case M_TAPS: return pack_taps(j.plan.ks, it.f32, j.sh, j.sw, j.dh, j.dw, out);
+        case M_LINEAR_EXACT_U8: return pack_linear_exact(j.sh, j.sw, j.dh, j.dw, out, j.plan.p);
+        case M_AREA: return it.area->pack(out);
+        default: return 0;
+        }
+    }
+
+public:
+    explicit ResizePlanner(const char *entry_point) : entry(entry_point) {}
+
+    // the interpolation codes the batched sites take
+    static bool known_interpolation(int c)
+    {
+        return c == VKX_INTER_CUBIC || c == VKX_INTER_AREA || c == VKX_INTER_LANCZOS4 || c == VKX_INTER_LINEAR_EXACT || c == VKX_INTER_NEAREST_EXACT;
+    }
+
+    // cv.resize((sh, sw) -> (dh, dw)) on float32 or uint8 into `j`.  Equal shapes leave M_COPY and plan nothing.
+    int plan(PlannedResize &j, bool f32, int interpolation, int sh, int sw, int dh, int dw)
+    {
+        j = PlannedResize{ResizePlan(), 0, sh, sw, dh, dw};
+        if (sh == dh && sw == dw) return VKX_OK;
+        j.plan = plan_resize(f32, interpolation, sh, sw, dh, dw);
+        if (j.plan.refused()) {
+            vkx_set_error(VKX_REQUIRE_FORMAT, entry, "INTER_AREA is for shrinking only");
+            return VKX_ERR_INVALID;
+        }
+        items.push_back(Item{&j, f32, 0, nullptr});
+        if (j.plan.mode == M_AREA) items.back().area.reset(new AreaTabs(sh, sw, dh, dw, j.plan.scale_x, j.plan.scale_y));
+        return VKX_OK;
+    }
+    // add(bytes) -> the offset of a block of that size in the staged block (vkx_tables::add), asked once per job that has tables
+    template <class Add>
+    void layout(Add add)
+    {
+        for (Item &it : items)
+            if ((it.bytes = pack_block(it, nullptr))) it.job->tab_off = (long long)add(it.bytes);
+    }
+    // ... and the blocks written at their offsets from `base`, the taken block
+    void pack(unsigned char *base) const
+    {
+        for (const Item &it : items)
+            if (it.bytes) pack_block(it, base + it.job->tab_off);
     }
 };
 

@@ -1,6 +1,7 @@
 // The device half of cv.resize: ONE destination pixel of every interpolation, each stated once for every site that resizes --
-// the direct kernels of resize.hip, the glyph planes of seal_fill.hip (k_seal_planes), the batched region resize of
-// region_flatten.hip (k_region_resize) and the label shrink of crop.hip.  A site hands its source over as an accessor, which
+// the direct kernels of resize.hip, the glyph planes of seal_fill.hip (k_seal_planes), the text lines of text_line.hip, the batched
+// region resize of region_flatten.hip (k_region_resize) and the label shrink of crop.hip.  The batched record kernels, whose mode
+// differs from record to record, reach their pixel through planned_pixel_u8 / planned_pixel_f32 at the end.  A site hands its source over as an accessor, which
 // carries everything the site does to a sample on the way in: the pitch, the (m > 0) * 255 of a mask, the any-channel test of a
 // 3-channel glyph.  The accessor is asked for clipped coordinates only.  The order of every float32 sum and the int32 wrap of the
 // fixed-point sums are the oracle's (oracle/vkx_oracle.c); the library is built with -ffp-contract=off.  The host half (axis
@@ -233,6 +234,82 @@ __device__ __forceinline__ void area_pixel(Load load, const AreaView &t, int dy,
         if constexpr (F32) out[c] = sum[c];
         else out[c] = (uint8_t)clamp_u8(cv_round(sum[c]));
     }
+}
+
+// ---- a PlannedResize (vkx_resize_axes.h) to its pixel: the function above its plan names, on the view of its table block.  `tabs`:
+// the staged block the job's tab_off counts from.  The modes are the ones the codes of ResizePlanner::known_interpolation reach.
+// One uint8 pixel of CN channels.  px(y, b): byte b = x * CN + c of source row y.
+template <int CN, class Px>
+__device__ void planned_pixel_u8(const PlannedResize &j, const unsigned char *tabs, int dy, int dx, Px px, uint8_t *out)
+{
+    const int sh = j.sh, sw = j.sw, dh = j.dh, dw = j.dw;
+    const int *p = j.plan.p;
+    const unsigned char *tab = tabs + j.tab_off;
+    switch (j.plan.mode) {
+    case M_COPY:
+#pragma unroll
+        for (int c = 0; c < CN; c++) out[c] = (uint8_t)px(dy, dx * CN + c);
+        break;
+    case M_NEAREST_EXACT: {
+        const int sx = nearest_exact_index(dx, p[0], p[1], sw), sy = nearest_exact_index(dy, p[2], p[3], sh);
+#pragma unroll
+        for (int c = 0; c < CN; c++) out[c] = (uint8_t)px(sy, sx * CN + c);
+        break;
+    }
+    case M_LINEAR_EXACT_U8:
+        linear_exact_pixel_u8<CN>([&](int y, int below, int x, int c) { return (unsigned)px(y + below, x * CN + c); },
+                                  LinearExactView::of(tab, dh, dw), p, dh, dw, dy, dx, out);
+        break;
+    case M_HALF_U8: half_pixel_u8<CN>([&](int y, int x, int c) { return px(2 * dy + y, (2 * dx + x) * CN + c); }, out); break;
+    case M_TAPS:
+        if (j.plan.ks == 4) {
+            const TapView<short> t(tab, 4, dh, dw);
+            taps_pixel_u8<CN, 4>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 4 * dx, t.ycoef + 4 * dy, out);
+        } else {
+            const TapView<short> t(tab, 8, dh, dw);
+            taps_pixel_u8<CN, 8>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 8 * dx, t.ycoef + 8 * dy, out);
+        }
+        break;
+    case M_AREA_FAST:
+#pragma unroll
+        for (int c = 0; c < CN; c++)
+            out[c] = area_fast_u8([&](int y, int x) { return px(dy * p[1] + y, (dx * p[0] + x) * CN + c); }, p[0], p[1]);
+        break;
+    default:                                    // M_AREA
+        area_pixel<CN, false>([&](int y, int x, int c) { return (float)px(y, x * CN + c); }, AreaView(tab, dh, dw), dy, dx, out);
+        break;
+    }
+}
+
+// ... and one float32 pixel, as ScoreMap.to_resized_score_map leaves it: clipped to [0, 1] unless nothing was resized.  px(y, x).
+template <class Px>
+__device__ float planned_pixel_f32(const PlannedResize &j, const unsigned char *tabs, int dy, int dx, Px px)
+{
+    const int sh = j.sh, sw = j.sw, dh = j.dh, dw = j.dw;
+    const int *p = j.plan.p;
+    const unsigned char *tab = tabs + j.tab_off;
+    float v = 0.f;
+    switch (j.plan.mode) {
+    case M_COPY: return px(dy, dx);
+    case M_NEAREST_EXACT:
+        v = px(nearest_exact_index(dy, p[2], p[3], sh), nearest_exact_index(dx, p[0], p[1], sw));
+        break;
+    case M_LINEAR_F32: v = linear_pixel_f32(px, sh, sw, dy, dx, j.plan.scale_x, j.plan.scale_y); break;
+    case M_TAPS:
+        if (j.plan.ks == 4) {
+            const TapView<float> t(tab, 4, dh, dw);
+            v = taps_pixel_f32<4>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 4 * dx, t.ycoef + 4 * dy);
+        } else {
+            const TapView<float> t(tab, 8, dh, dw);
+            v = taps_pixel_f32<8>(px, sh, sw, t.xofs[dx], t.yofs[dy], t.xcoef + 8 * dx, t.ycoef + 8 * dy);
+        }
+        break;
+    case M_AREA_FAST: v = area_fast_f32([&](int y, int x) { return px(dy * p[1] + y, dx * p[0] + x); }, p[0], p[1]); break;
+    default:                                    // M_AREA
+        area_pixel<1, true>([&](int y, int x, int) { return px(y, x); }, AreaView(tab, dh, dw), dy, dx, &v);
+        break;
+    }
+    return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);      // np.clip(mat, 0, 1); a NaN stays
 }
 
 } // namespace vkd
