@@ -1217,6 +1217,49 @@ typedef struct vkx_text_line {
 int vkx_text_lines_dev(vkx_ctx *ctx, const vkx_text_char *chars_host, int n_chars, const vkx_text_line *lines_host, int n_lines,
                        const void *blob_host, size_t blob_bytes, uint8_t *dst, size_t dst_bytes);
 
+/* ---- the page's symbol, barcode and frame layers (pipeline/text_detection/page_non_text_symbol.py:107-169 after
+ * engine/image/selector.py:98-101; engine/barcode/qr.py:81-93 and code39.py:137-148; page_text_line_bounding_box.py:94-147) -------
+ * vkx_page_layers_dev builds EVERY such layer of a page: at most two launches whatever the number of layers (one without symbol
+ * records), no synchronisation.  The records are a HOST table; every draw and every box in them is the caller's, every pixel
+ * is the call's, each operation rounded once in float32:
+ *   VKX_LAYER_SYMBOL_RGBA  source uint8 [src_h][src_w][4]; r = cv.resize(source, (out_w, out_h), INTER_CUBIC) (equal shapes: the
+ *     source itself); the image uint8 [out_h][out_w][3] = r[..., :3] at image_off; with a = r[..., 3] and m = max(a) over the
+ *     record the plane float32 [out_h][out_w] = ((float32(a) / 255) * float32(alpha)) / (float32(m) / 255) at alpha_off; m == 0
+ *     divides 0 by 0 and the plane is NaN throughout, as in the reference;
+ *   VKX_LAYER_SYMBOL_GRAY  source uint8 [src_h][src_w]; g resized likewise; the plane is g > 0 ? float32(alpha) : 0, the image
+ *     the constant `color`;
+ *   VKX_LAYER_SCORE  source a uint8 module mask [src_h][src_w]; s = mask ? float32(alpha) : 0; where the shapes differ the plane
+ *     is cv.resize(s, INTER_CUBIC) on float32 clipped to [0, 1] (ScoreMap.to_resized_score_map), else s; no image;
+ *   VKX_LAYER_FRAME  no source; of a plane src_h x src_w that holds float32(alpha) on a ring of `thickness` pixels and 0 inside,
+ *     the window of rows trim[0] .. src_h - 1 - trim[1] and columns trim[2] .. src_w - 1 - trim[3], which has out_h x out_w.
+ * A source is dense: at byte offset src_off of the HOST block `blob_host`, which travels with the table as one staged upload, or
+ * (src_off == -1) the DEVICE array src_dev.  dst: DEVICE, `dst_bytes` long, aligned to 4 bytes; the planes are dense, at the
+ * byte offsets of the records (alpha_off a multiple of 4); every element of them is written, dst needs no memset.
+ * Refused (VKX_ERR_INVALID, nothing launched): a NULL pointer, n_layers outside 1 .. 4096, an unknown kind, a side outside
+ * 1 .. 32767, a colour outside 0 .. 255, an alpha that is NaN or outside [0, 1], a frame whose thickness is below 1 or leaves
+ * an interior of fewer than two rows or columns (the reference's asserts), whose trims leave no window or whose output is not
+ * that window, a blob offset out of range, a device source that overlaps dst, a destination outside dst, misaligned, or
+ * overlapping another. */
+#define VKX_LAYER_SYMBOL_RGBA 0
+#define VKX_LAYER_SYMBOL_GRAY 1
+#define VKX_LAYER_SCORE 2
+#define VKX_LAYER_FRAME 3
+typedef struct vkx_page_layer {
+    int32_t kind;                       /* VKX_LAYER_* */
+    int32_t src_h, src_w;               /* the source; VKX_LAYER_FRAME: the untrimmed plane */
+    int32_t out_h, out_w;
+    int32_t color[3];                   /* VKX_LAYER_SYMBOL_GRAY */
+    int32_t thickness;                  /* VKX_LAYER_FRAME */
+    int32_t trim[4];                    /* VKX_LAYER_FRAME: up, down, left, right */
+    int32_t reserved;
+    double alpha;
+    int64_t src_off;                    /* blob, bytes; -1: src_dev */
+    const void *src_dev;
+    int64_t image_off, alpha_off;       /* dst, bytes; image_off is read for the symbol kinds only */
+} vkx_page_layer;
+int vkx_page_layers_dev(vkx_ctx *ctx, const vkx_page_layer *layers_host, int n_layers, const void *blob_host, size_t blob_bytes,
+                        uint8_t *dst, size_t dst_bytes);
+
 /* ---- text-line labels: quad interpolation and the box masks (element/score_map.py:139-283, :562-588;
  * pipeline/text_detection/page_text_line_label.py:156-306) ---------------------------------------------------------------------
  * One HOST record a quad, its vertices point0 .. point3 as ScoreMap.from_quad_interpolation holds them: x / y the rounded

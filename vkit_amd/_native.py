@@ -399,6 +399,7 @@ _SIGNATURES['vkx_region_extend_masks_dev'] = [c_void_p, c_void_p, c_int, c_void_
 _SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 _SIGNATURES['vkx_seal_fill_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_text_lines_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
+_SIGNATURES['vkx_page_layers_dev'] = [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_set_mask_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ssize, c_void_p,
                                    ctypes.c_size_t]
 _SIGNATURES['vkx_set_mask'] = _SIGNATURES['vkx_set_mask_dev']
@@ -2679,6 +2680,30 @@ def text_lines(chars, lines, blob, dst):
     check(lib().vkx_text_lines_dev(dst.ctx.handle, chars.ctypes.data if len(chars) else None, len(chars),
                                    lines.ctypes.data if len(lines) else None, len(lines), blob.ctypes.data if blob.size else None,
                                    blob.size, c_void_p(dst.ptr), dst.nbytes))
+    dst.invalidate_host()
+
+
+# --------------------------------------------------------------------------------------------------------------
+# the symbol, barcode and frame layers of a page (csrc/page_layers.hip): vkx_page_layer of include/vkx.h
+# --------------------------------------------------------------------------------------------------------------
+LAYER_SYMBOL_RGBA, LAYER_SYMBOL_GRAY, LAYER_SCORE, LAYER_FRAME = 0, 1, 2, 3
+PAGE_LAYER_DTYPE = np.dtype([('kind', np.int32), ('src_h', np.int32), ('src_w', np.int32), ('out_h', np.int32), ('out_w', np.int32),
+                             ('color', np.int32, (3,)), ('thickness', np.int32), ('trim', np.int32, (4,)), ('reserved', np.int32),
+                             ('alpha', np.float64), ('src_off', np.int64), ('src_dev', np.uint64), ('image_off', np.int64),
+                             ('alpha_off', np.int64)], align=True)
+assert PAGE_LAYER_DTYPE.itemsize == 96
+
+
+def page_layers(layers, blob, dst):
+    """vkx_page_layers_dev: ``layers`` PAGE_LAYER_DTYPE records, ``blob`` the uint8 host block the records with a ``src_off``
+    address (None: every source is a device array), ``dst`` the uint8 DevArray the planes are written into at the byte offsets of
+    the records.  At most TWO launches whatever the number of layers (ONE without symbol records), asynchronous."""
+    layers = _records(layers, PAGE_LAYER_DTYPE)
+    if dst.dtype != np.uint8:
+        raise TypeError('dst must be a uint8 DevArray')
+    blob = np.zeros(0, np.uint8) if blob is None else np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    check(lib().vkx_page_layers_dev(dst.ctx.handle, layers.ctypes.data if len(layers) else None, len(layers),
+                                    blob.ctypes.data if blob.size else None, blob.size, c_void_p(dst.ptr), dst.nbytes))
     dst.invalidate_host()
 
 

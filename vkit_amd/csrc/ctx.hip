@@ -123,6 +123,7 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->seal_planes);
     scratch_release(&ctx->text_tables);
     scratch_release(&ctx->text_planes);
+    scratch_release(&ctx->layer_tables);
     scratch_release(&ctx->quad_tables);
     scratch_release(&ctx->glass_win);
     scratch_release(&ctx->jpeg_planes);

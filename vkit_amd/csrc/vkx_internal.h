@@ -172,6 +172,7 @@ struct vkx_ctx {
     vkx_scratch set_tables, set_planes;       // element set masks (element_sets.hip): the overflow flag + staged tables; the two index planes (int [2][h * w]) of the last call
     vkx_scratch seal_tables, seal_planes;     // seal impressions (seal_fill.hip): the staged records, tap tables and host planes of the last call; the char planes + per-seal maxima
     vkx_scratch text_tables, text_planes;     // text lines (text_line.hip): the staged records, resize tables and glyph blob of the last call; the pasted planes of its resized lines
+    vkx_scratch layer_tables;                 // page layers (page_layers.hip): the staged records, resize tables, per-record maxima and host sources of the last call
     vkx_scratch quad_tables;                  // text-line labels (quad_interp.hip): the staged records, tile bins and vote counts of the last call
     vkx_scratch glass_win;                   // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows

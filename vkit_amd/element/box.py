@@ -23,6 +23,7 @@ from .opt import (
 )
 from .type import ElementSetOperationMode, Shapable
 
+_PLANES = (np.ndarray, _native.DevArray)        # what a recorded layer's plane may be held as
 
 @attrs.define(frozen=True)
 class Box(Shapable):
@@ -234,8 +235,9 @@ class Box(Shapable):
                     and 0 <= self.left <= self.right < target.shape[1]):
                 shape = self.shape
                 plane = value._mat if isinstance(value, Image) else value
-                ok = isinstance(plane, tuple) or (isinstance(plane, np.ndarray) and plane.dtype == np.uint8
-                                                 and plane.shape == shape + (target.shape[2],))
+                # (a plane is a host array or, born on the device, a DevArray: make_layer takes either where it is)
+                ok = isinstance(plane, tuple) or (isinstance(plane, _PLANES) and plane.dtype == np.uint8
+                                                 and tuple(plane.shape) == shape + (target.shape[2],))
                 mask_plane = None
                 if image_mask is not None:
                     mask_plane = image_mask._mat if isinstance(image_mask, Mask) else image_mask
@@ -246,8 +248,8 @@ class Box(Shapable):
                 if isinstance(alpha, ScoreMap):
                     ok = ok and alpha.is_prob
                     weight = alpha._mat
-                if isinstance(weight, np.ndarray):
-                    ok = ok and weight.shape == shape and weight.dtype == np.float32
+                if isinstance(weight, _PLANES):
+                    ok = ok and tuple(weight.shape) == shape and weight.dtype == np.float32
                 else:
                     ok = ok and type(weight) is float and 0.0 <= weight <= 1.0
                 if ok:

@@ -286,7 +286,7 @@ class ScoreMap(LazyMat, Shapable):
         # composite on a uint8 image.  Same layer as the generic path below records (box geometry, the map as alpha plane,
         # no selection plane), without its five calls per layer.
         box, target, alpha = self.box, image._mat, self._mat
-        if (box is not None and image.box is None and type(value) is tuple and self.is_prob and isinstance(alpha, np.ndarray)
+        if (box is not None and image.box is None and type(value) is tuple and self.is_prob and isinstance(alpha, (np.ndarray, _native.DevArray))
                 and target.dtype == np.uint8 and target.ndim == 3 and len(value) == target.shape[2]):
             stack = _deferred_stack()
             if (stack and stack[-1].base is target and 0 <= box.up <= box.down < target.shape[0]

@@ -57,6 +57,8 @@ class ImageSelectorEngine:
         self._caches = {}
 
     def texture(self, ctx, image_file):
+        """The decoded file as a DevArray of ``ctx`` (None: the thread's default context), from the context's cache."""
+        ctx = ctx or _native.default_ctx()
         cache = self._caches.get(id(ctx))
         if cache is None or cache[0]() is not ctx:
             import weakref

@@ -67,3 +67,31 @@ from .page_text_region_cropping import (  # noqa: F401
     PageTextRegionCroppingStepOutput,
     page_text_region_cropping_step_factory,
 )
+from .page_image import (  # noqa: F401
+    PageImageStep,
+    PageImageStepConfig,
+    PageImageStepInput,
+    page_image_step_factory,
+)
+from .page_barcode import (  # noqa: F401
+    PageBarcodePlan,
+    PageBarcodeStep,
+    PageBarcodeStepConfig,
+    PageBarcodeStepInput,
+    page_barcode_step_factory,
+)
+from .page_text_line_bounding_box import (  # noqa: F401
+    PageTextLineBoundingBoxStep,
+    PageTextLineBoundingBoxStepConfig,
+    PageTextLineBoundingBoxStepInput,
+    TextLineBoundingBoxPlan,
+    page_text_line_bounding_box_step_factory,
+)
+from .page_non_text_symbol import (  # noqa: F401
+    NonTextSymbolColorMode,
+    NonTextSymbolPlan,
+    PageNonTextSymbolStep,
+    PageNonTextSymbolStepConfig,
+    PageNonTextSymbolStepInput,
+    page_non_text_symbol_step_factory,
+)

@@ -42,11 +42,37 @@ class NonTextRegion:
 
 
 @attrs.define
+class LayoutImage:
+    box: Box
+
+
+@attrs.define
+class LayoutBarcodeQr:
+    box: Box
+
+
+@attrs.define
+class LayoutBarcodeCode39:
+    box: Box
+
+
+@attrs.define
+class LayoutNonTextSymbol:
+    box: Box
+    alpha: float
+
+
+@attrs.define
 class PageLayout:
     height: int
     width: int
     disconnected_text_regions: Sequence[DisconnectedTextRegion] = ()
     non_text_regions: Sequence[NonTextRegion] = ()
+    # what PageImageStep, PageBarcodeStep and PageNonTextSymbolStep read (reference page_layout.py: PageLayout)
+    layout_images: Sequence[LayoutImage] = ()
+    layout_barcode_qrs: Sequence[LayoutBarcodeQr] = ()
+    layout_barcode_code39s: Sequence[LayoutBarcodeCode39] = ()
+    layout_non_text_symbols: Sequence[LayoutNonTextSymbol] = ()
 
 
 @attrs.define
@@ -154,7 +180,8 @@ class PageTextLineStepOutput:
 class PageNonTextSymbolStepOutput:
     images: Sequence[Image] = ()
     boxes: Sequence[Box] = ()
-    alphas: Sequence[Union[np.ndarray, float]] = ()
+    # (a plane born on the device -- PageNonTextSymbolStep in resident mode -- is a box-less ScoreMap holding it)
+    alphas: Sequence[Union[np.ndarray, ScoreMap, float]] = ()
 
 
 @attrs.define
