@@ -604,6 +604,10 @@ int vkx_np_draw_batch_dev(vkx_ctx *ctx, const vkx_np_job *jobs_host, int n_jobs,
  * table[t].first <= i < table[t + 1].first, is slot t's element table[t].skip + i - table[t].first; samples i + 1 .. i + 3 follow
  * it in the same slot (a slot ends with the first three samples of its successor).  Any output pointer may be NULL. */
 int vkx_np_tiles_layout(int64_t n, int64_t *n_tiles, int64_t *slot_elems, int64_t *table_offset, int64_t *slots_offset, int64_t *bytes);
+/* Debug: 1 when the draw pass parks the samples of an int16 job with this scale (and location; the jobs above have 0) as bytes,
+ * i.e. when 3.6541528853610088 |scale| + |loc| <= 127, the largest integer a ziggurat fast accept can become; 0 otherwise.  The
+ * samples are the same either way; a launch parks bytes when all its jobs qualify.  No device needed. */
+int vkx_np_parks_as_bytes(double scale, double loc);
 /* dst int16 [n] (device, 8-byte aligned) = the plane a finished tile buffer stands for; asynchronous on the ctx stream */
 int vkx_np_tiles_expand_dev(vkx_ctx *ctx, const void *tiles, int64_t n, int16_t *dst);
 /* Debug: est[i] (device, float64) = the float32-logarithm estimate of -log(1 - u), u = (draws[i] >> 11) * 2^-53, from which the integer

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Static ISA census of k_np_draw_compact<EmitI16> (the int16 draw pass of the numpy streams), priced in SIMD cycles.
+"""Static ISA census of k_np_draw_compact (the int16 draw pass of the numpy streams), priced in SIMD cycles: the byte-parked
+instantiation <EmitI16B8> the bench runs, or with --emit EmitI16 the int16-parked one.
 
 Compiles vkit_amd/csrc/nprand.hip for gfx950 with the Makefile's flags, splits the kernel into basic blocks and prices every VALU
 instruction with the issue rates measured by tools/ubench (cycles per wavefront instruction per SIMD: profiles/r2_instruction_rates.md,
 overridden by profiles/np_instruction_rates.md where both have a form).  LDS and SALU instructions are counted, not priced: they issue
 to other units.  The phase-1 loop (the depth-2 loop with the most v_mad_u64_u32; one ds_read_b128 per round) and the compaction block (the
-most v_readlane) are summed per round; the event-push blocks of phase 1 (the ones holding ds_write_b128) run in the ~62 % of rounds
+most v_readlane) are summed per round, so are the blocks that widen parked bytes on the way to the slot (v_pk_ashrrev_i16); the event-push blocks of phase 1 (the ones holding ds_write_b128) run in the ~62 % of rounds
 that have a draw that is not a fast accept and are listed apart.
-Usage: tools/np_draw_census.py [--src nprand.hip] [-D NAME=VALUE ...] [--asm out.s] > profiles/np_draw_census.md"""
+Usage: tools/np_draw_census.py [--emit EmitI16B8|EmitI16] [--src nprand.hip] [-D NAME=VALUE ...] [--asm out.s] > profiles/np_draw_census.md"""
 import argparse
 import collections
 import os
@@ -19,7 +20,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fvisibility=hidden', '-Wno-unused-function',
          '-S', '--cuda-device-only']
-KERNEL = '_ZN12_GLOBAL__N_117k_np_draw_compactINS_7EmitI16EEE'
+KERNEL_OF = {'EmitI16': '_ZN12_GLOBAL__N_117k_np_draw_compactINS_7EmitI16EEE', 'EmitI16B8': '_ZN12_GLOBAL__N_117k_np_draw_compactINS_9EmitI16B8EEE'}
+KERNEL = KERNEL_OF['EmitI16B8']
 RATE_FILES = ['profiles/r2_instruction_rates.md', 'profiles/np_instruction_rates.md']
 # forms whose ubench row measures something else than the form the kernel uses
 ALIAS = {
@@ -137,11 +139,14 @@ def summarize(block, rates):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--emit', default='EmitI16B8', choices=sorted(KERNEL_OF))
     ap.add_argument('--src', default=os.path.join(ROOT, 'vkit_amd', 'csrc', 'nprand.hip'))
     ap.add_argument('-D', dest='defines', action='append', default=[])
     ap.add_argument('--asm', help='also write the assembly here')
     ap.add_argument('--min-ops', type=int, default=8, help='list blocks with at least this many instructions')
     args = ap.parse_args()
+    global KERNEL
+    KERNEL = KERNEL_OF[args.emit]
     rates = load_rates()
     asm = compile_asm(args.src, args.defines)
     if args.asm:
@@ -155,7 +160,7 @@ def main():
     p1 = mads.most_common(1)[0][0] if mads else None
     comp = max(blocks, key=lambda b: b['ops'].count('v_readlane_b32'))
     all_unpriced = set()
-    print(f'# k_np_draw_compact<EmitI16>: VALU cycles per basic block ({os.path.relpath(args.src, ROOT)}'
+    print(f'# k_np_draw_compact<{args.emit}>: VALU cycles per basic block ({os.path.relpath(args.src, ROOT)}'
           f'{", " + " ".join("-D" + d for d in args.defines) if args.defines else ""})\n')
     print('Cycles = sum over the block\'s VALU instructions of the issue cycles per wavefront instruction per SIMD (tools/ubench; '
           f'forms without a row: {DEFAULT_RATE}).  LDS / SALU / VMEM: instruction counts.\n')
@@ -186,8 +191,14 @@ def main():
         k = comp['ops'].count('v_readlane_b32') // 2
         if k:
             print(f'| compaction ({comp["name"]}, {k} rounds) | {cc["valu"] / k:.1f} | {cc["cycles"] / k:.1f} | {cc["lds"] / k:.1f} |')
-        print(f'| **sum (event push at 0.62)** | **{(bv + 0.62 * pv) / k1 + (cc["valu"] / k if k else 0):.1f}** | '
-              f'**{(bc + 0.62 * pc) / k1 + (cc["cycles"] / k if k else 0):.1f}** | |')
+        # the slot write of the byte-parked pass: per 16-byte group a perm and a packed shift per dword, kTile / 512 groups per lane
+        widen = [r for r in rows if 'v_pk_ashrrev_i16' in r[0]['ops']]
+        wv, wc = sum(r[1]['valu'] for r in widen), sum(r[1]['cycles'] for r in widen)
+        if widen and k:
+            print(f'| slot write with widening ({len(widen)} blocks, {k} rounds) | {wv / k:.1f} | {wc / k:.1f} | {sum(r[1]["lds"] for r in widen) / k:.1f} |')
+        kk = k or 1
+        print(f'| **sum (event push at 0.62)** | **{(bv + 0.62 * pv) / k1 + (cc["valu"] + wv) / kk:.1f}** | '
+              f'**{(bc + 0.62 * pc) / k1 + (cc["cycles"] + wc) / kk:.1f}** | |')
     if all_unpriced:
         print(f'\nForms without a measured rate (priced at {DEFAULT_RATE}): ' + ', '.join(sorted(all_unpriced)))
 

@@ -291,6 +291,7 @@ _SIGNATURES = {
     'vkx_noise_normal_i16_batch_dev': [c_void_p, ctypes.POINTER(VkxNoisePlane), c_int, c_double],
     'vkx_np_draw_batch_dev': [c_void_p, ctypes.POINTER(VkxNpJob), c_int, ctypes.POINTER(VkxNpResult)],
     'vkx_np_tiles_layout': [ctypes.c_int64] + [ctypes.POINTER(ctypes.c_int64)] * 5,
+    'vkx_np_parks_as_bytes': [c_double, c_double],
     'vkx_np_tiles_expand_dev': [c_void_p, c_void_p, ctypes.c_int64, c_void_p],
     'vkx_np_tail_log_est_dev': [c_void_p, c_void_p, ctypes.c_int64, c_void_p, ctypes.POINTER(c_double)],
     'vkx_np_draw': [c_void_p, ctypes.POINTER(VkxNpJob), ctypes.POINTER(VkxNpResult)],

@@ -86,10 +86,13 @@ struct NpJob {
 };
 
 struct TileInfo {            // pass 1, assuming carry-in 0
-    uint32_t count0, out0;   // out0: bit 31 = the tile holds a tail sample
+    uint32_t count0, out0;   // out0: bit 31 = the tile holds a tail sample, bit 30 = kParkOver
     uint64_t start0, emit0;  // round 0: positions that start an attempt / that emit a sample
 };
-constexpr uint32_t kIrregular = 0x80000000u;   // TilePlan::c_in: the carry-in is not a start of the recorded chain
+constexpr uint32_t kIrregular = 0x80000000u;   // TilePlan::c_in: the carry-in is not a start of the recorded chain, or the slot is not the tile's (kParkOver)
+constexpr uint32_t kParkOver = 0x40000000u;    // TileInfo::out0: a tail sample of the tile did not fit the byte it was parked in (EmitI16B8)
+constexpr uint32_t kOutCarry = 0x3fffffffu;    // TileInfo::out0: the carry-out itself
+constexpr uint32_t kFlagParkOver = 0x40000000u;   // inside walk_tile's `flags` only: never reaches a job's result
 struct TilePlan {
     unsigned long long prefix;   // index of the tile's first sample
     uint32_t c_in, count;
@@ -222,6 +225,7 @@ struct EmitNone {
     static constexpr bool kFastTail = true;     // (the walk that only counts: the decisions)
     typedef int Val;
     typedef int16_t Store;
+    typedef int16_t Park;
     __device__ static bool tail_proven(const NpJob &, double) { return true; }
     __device__ static Val make(const NpJob &, double, bool, uint32_t &) { return 0; }
     __device__ static void store(const NpJob &, void *, long long, Val, bool, uint32_t &) {}
@@ -232,8 +236,21 @@ struct EmitI16 {   // np.round(0 + std * z).astype(int16)
     __device__ static bool tail_proven(const NpJob &job, double ze) { return rounded_step_proven(job, ze); }
     typedef int Val;
     typedef int16_t Store;
+    typedef int16_t Park;
     __device__ static Val make(const NpJob &job, double z, bool inexact, uint32_t &flags) { return rounded_step(job, z, inexact, flags); }
     __device__ static void store(const NpJob &, void *dst, long long pos, Val k, bool, uint32_t &) { ((int16_t VKX_GLOBAL *)dst)[pos] = (int16_t)k; }
+};
+// A fast accept is bounded, |x| <= kNorR, so its integer is bounded by kNorR |scale| + |loc|: where that fits a signed byte the draw
+// pass parks a tile's samples as bytes (EmitI16B8) and widens them on the way to the slot.  The one statement of the rule: the host
+// picks the kernel of a launch with it, every int16 job of the launch has to qualify.
+__host__ __device__ inline bool np_parks_as_bytes(double scale, double loc)
+{
+    return 3.6541528853610088 * fabs(scale) + fabs(loc) <= 127.0;
+}
+// EmitI16 for the launches that qualify: the same samples, parked in LDS as bytes.  Only a tail sample (phase 2) can leave the byte;
+// it marks its tile (kParkOver), which k_np_place_walk then rewrites from the generator state like a tile with an irregular carry-in.
+struct EmitI16B8 : EmitI16 {
+    typedef int8_t Park;
 };
 struct EmitAddU8 {   // clip(int16(px) + noise, 0, 255): the whole gaussion_noise operator
     static constexpr bool kCheckAtStore = false;
@@ -241,6 +258,7 @@ struct EmitAddU8 {   // clip(int16(px) + noise, 0, 255): the whole gaussion_nois
     __device__ static bool tail_proven(const NpJob &job, double ze) { return rounded_step_proven(job, ze); }
     typedef int Val;
     typedef int16_t Store;
+    typedef int16_t Park;
     __device__ static Val make(const NpJob &job, double z, bool inexact, uint32_t &flags) { return rounded_step(job, z, inexact, flags); }
     __device__ static void store(const NpJob &job, void *dst, long long pos, Val k, bool, uint32_t &)
     {
@@ -253,6 +271,7 @@ struct EmitSpeckle {   // uint8(clip(px + px * (0 + std * z), 0, 255)) in float6
     static constexpr bool kFastTail = false;    // the float64 draw itself is stored
     typedef double Val;
     typedef double Store;
+    typedef double Park;
     __device__ static Val make(const NpJob &, double z, bool, uint32_t &) { return z; }
     __device__ static void store(const NpJob &job, void *dst, long long pos, Val z, bool inexact, uint32_t &flags)
     {
@@ -277,11 +296,17 @@ struct WaveWork {
     uint16_t ev_info[kEvCap];    // draws consumed | emits << 8 | tail << 9
     uint64_t slow[kRounds];      // per round: the lanes whose attempt is not a fast accept
     uint64_t semit[kRounds];     // per round: the events that emit a sample, as a lane mask
-    uint64_t cov[kRounds];       // per round: the draws consumed by an attempt that started earlier
+    // per round: the draws consumed by an attempt that started earlier.  Byte parking has no words of its own for them: phase 3
+    // builds them over ev_s, which nothing reads after phase 2 but kEmit (5 760 B per wavefront: five workgroups of four to a CU)
+    static constexpr bool kCovInEv = WITH_VAL && sizeof(Val) == 1;
+    uint64_t cov_own[kCovInEv ? 0 : kRounds];
+    __device__ __forceinline__ uint64_t *cov() { return kCovInEv ? &ev_s[0][0] : cov_own; }
     // kEmit / kCompact: what every draw would emit as a fast accept (int16 steps, or the float64 draw); kCompact parks two rounds
-    // per dword (park_index), squeezes the tile's samples together in place and sends them to the tile's slot as 16-byte groups
+    // per dword (park_index) -- as bytes, four rounds per dword (park_index_b8) --, squeezes the tile's samples together in place and
+    // sends them to the tile's slot as 16-byte groups
     __attribute__((aligned(16))) Val val[WITH_VAL ? kRounds : 1][64];
 };
+static_assert(kEvCap * 16 >= kRounds * 8, "the cover words fit the event states");
 
 __device__ __forceinline__ uint64_t rfl64(uint64_t v)
 {
@@ -368,15 +393,77 @@ __device__ __forceinline__ uint32_t compact_tile_lds(int16_t *flat, uint64_t m)
     return run;
 }
 
+// The same with bytes: element r of lane l at park_index_b8(64 r + l), rounds 4 q .. 4 q + 3 of a lane in one dword.  Phase 1 writes
+// a half-word per trip (two rounds), the squeeze reads a dword per four rounds and writes bytes under exec: byte 0 as it stands, byte 2
+// through ds_write_b8_d16_hi, bytes 1 and 3 after one shift.  A sample's rank stays below 64 (r + 1) <= the end of its dword row, rows
+// are handled in order and eight rounds (two rows) are read before the first of their writes.
+__device__ __forceinline__ uint32_t park_index_b8(uint32_t pos) { return (pos & ~255u) | ((pos & 63u) << 2) | ((pos >> 6) & 3u); }
+
+__device__ __forceinline__ uint32_t compact_tile_lds_b8(int8_t *flat, uint64_t m)
+{
+    const uint32_t lane = (uint32_t)__lane_id();
+    const uint32_t base = lds_offset(flat);
+    const uint32_t *quads = (const uint32_t *)flat;
+    uint32_t run = 0;
+    constexpr int kBatch = 8;
+    static_assert(kRounds % kBatch == 0, "rounds per compaction batch");
+#pragma unroll
+    for (int r0 = 0; r0 < kRounds; r0 += kBatch) {
+        uint32_t v[kBatch / 4];
+#pragma unroll
+        for (int j = 0; j < kBatch; j += 4) v[j / 4] = quads[16 * (r0 + j) + lane];
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) {
+            const int r = r0 + j;
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)m, r), hi = (uint32_t)__builtin_amdgcn_readlane((int)(m >> 32), r);
+            const uint32_t addr = base + (uint32_t)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, run));
+            const uint64_t mask = ((uint64_t)hi << 32) | lo;
+            const uint32_t b = (j & 1) ? v[j / 4] >> 8 : v[j / 4];      // bytes 1 and 3 at bits 0 and 16
+            uint64_t saved;
+            if (j & 2)
+                asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\tds_write_b8_d16_hi %[a], %[v]\n\ts_mov_b64 exec, %[sv]"
+                             : [sv] "=&s"(saved) : [m] "s"(mask), [a] "v"(addr), [v] "v"(b) : "memory");
+            else
+                asm volatile("s_mov_b64 %[sv], exec\n\ts_mov_b64 exec, %[m]\n\tds_write_b8 %[a], %[v]\n\ts_mov_b64 exec, %[sv]"
+                             : [sv] "=&s"(saved) : [m] "s"(mask), [a] "v"(addr), [v] "v"(b) : "memory");
+            run += (uint32_t)__builtin_popcountll(mask);
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    return run;
+}
+
+// Eight parked bytes as eight int16: per dword one v_perm_b32 that puts each byte into the high half of its 16 bits and one packed
+// arithmetic shift.
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t widen_b8_pair(uint32_t w, uint32_t sel)
+{
+    const uint32_t up = __builtin_amdgcn_perm(w, w, sel);
+    s16x2 h;
+    memcpy(&h, &up, 4);
+    h = h >> (s16x2)8;
+    uint32_t out;
+    memcpy(&out, &h, 4);
+    return out;
+}
+
+// libm's float64 exp() as a call.  Inlined, its five polynomial constants are hoisted out of the loop over a wavefront's tiles and live
+// through phase 1; under the byte pass's budget of 96 registers the compiler spilled them (44 B of scratch per lane, five stores per
+// wavefront that go to memory: + 21 % of the pass's HBM writes).  The call keeps them inside the rare branch of phase 2 that needs them:
+// 89 VGPRs, no scratch.  The same code, so the same bits.
+__device__ __attribute__((noinline)) double exp_f64_call(double y) { return exp(y); }
+
 template <class Emit, int MODE>
 __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 *__restrict__ zig /* LDS: ki | wi */, const FiC *__restrict__ fic /* LDS: fi | -2^52 wi */,
-                          WaveWork<typename Emit::Store, MODE == kEmit || MODE == kCompact> &ws, u128 &s, u128 &s2, uint32_t c_in, long long prefix,
+                          WaveWork<typename Emit::Park, MODE == kEmit || MODE == kCompact> &ws, u128 &s, u128 &s2, uint32_t c_in, long long prefix,
                           long long draw_base, typename Emit::Store VKX_GLOBAL *rec_val, uint64_t VKX_GLOBAL *rec_mask, void *emit_dst,
                           uint32_t &count_out, uint32_t &carry_out, uint64_t &start0, uint64_t &emit0, bool &has_tail, uint32_t &flags,
                           unsigned long long *draws_used)
 {
     const int lane = __lane_id();
     const u128 inc = mk128(job.inc);
+    constexpr bool kParkBytes = sizeof(typename Emit::Park) == 1;
+    static_assert(!kParkBytes || MODE == kCompact, "bytes are parked by the compacting draw pass only");
     // wave-uniform by construction; said explicitly so that the start walk below stays on the scalar unit
     c_in = (uint32_t)__builtin_amdgcn_readfirstlane((int)c_in);
     prefix = (long long)rfl64((uint64_t)prefix);
@@ -464,7 +551,11 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
         const typename Emit::Val vb = finish(r + 1, sb, db);
         // kCompact parks rounds r and r + 1 of a lane side by side (park_index): one v_perm_b32 and one 4-byte LDS write per two
         // rounds (two 2-byte writes without the perm measured 1 % slower: a 2-byte write costs the LDS pipe what a 4-byte one does)
-        if constexpr (MODE == kCompact)
+        // (as bytes: the low bytes of the two steps in one half-word, park_index_b8: the same perm, a 2-byte write)
+        if constexpr (MODE == kCompact && kParkBytes)
+            ((uint16_t *)&ws.val[0][0])[128 * (r >> 2) + ((r >> 1) & 1) + 2 * lane] =
+                (uint16_t)__builtin_amdgcn_perm((uint32_t)vb, (uint32_t)va, 0x0c0c0400u);
+        else if constexpr (MODE == kCompact)
             ((uint32_t *)&ws.val[0][0])[32 * r + lane] = __builtin_amdgcn_perm((uint32_t)vb, (uint32_t)va, 0x05040100u);
     }
     s = sl;
@@ -503,7 +594,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                 const float l32 = (float)lhs;
                 bool accept = l32 < r32;
                 if (fabsf(l32 - r32) <= r32 * 0x1p-14f || job.margin >= 1.0) {
-                    const double rhs = exp(y);
+                    const double rhs = kParkBytes ? exp_f64_call(y) : exp(y);
                     if (fabs(rhs - lhs) <= lhs * job.margin) flags |= VKX_NP_AMBIGUOUS;
                     accept = lhs < rhs;
                 }
@@ -552,6 +643,11 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                 const double z = neg ? -(kNorR + xx) : kNorR + xx;
                 if (MODE == kRecord) {
                     rec_val[pos] = (typename Emit::Store)Emit::make(job, z, inexact, flags);
+                } else if constexpr (MODE == kCompact && kParkBytes) {
+                    // the one sample that can leave the byte: its tile is marked and walked again (kParkOver)
+                    const int k = (int)Emit::make(job, z, inexact, flags);
+                    (&ws.val[0][0])[park_index_b8(pos)] = (int8_t)k;
+                    if (k != (int)(int8_t)k) flags |= kFlagParkOver;
                 } else if (MODE == kCompact) {
                     (&ws.val[0][0])[park_index(pos)] = (typename Emit::Store)Emit::make(job, z, inexact, flags);
                 } else if (MODE == kEmit) {
@@ -612,7 +708,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
             if (last_end > (uint32_t)kTile && last_end - kTile > carry) carry = last_end - kTile;
         }
         // the draws each valid event consumes after its own: positions P + 1 .. end - 1
-        if (lane < kRounds) ws.cov[lane] = 0;
+        if (lane < kRounds) ws.cov()[lane] = 0;
         __builtin_amdgcn_wave_barrier();
         if ((valid >> lane) & 1) {
             uint32_t p0 = P + 1, p1 = end < (uint32_t)kTile ? end : (uint32_t)kTile;     // [p0, p1)
@@ -620,7 +716,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
                 const uint32_t r = p0 >> 6, stop = (r + 1) << 6 < p1 ? (r + 1) << 6 : p1;
                 const uint32_t lo = p0 & 63, n = stop - p0;
                 const uint64_t bits = (n == 64 ? ~0ull : ((1ull << n) - 1)) << lo;
-                atomicOr((unsigned long long *)&ws.cov[r], bits);
+                atomicOr((unsigned long long *)&ws.cov()[r], bits);
                 p0 = stop;
             }
         }
@@ -628,7 +724,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
     } else {
         // more than 64 events in one tile (12 sigma): the plain serial walk
         valid = 0;
-        if (lane < kRounds) ws.cov[lane] = 0;
+        if (lane < kRounds) ws.cov()[lane] = 0;
         __builtin_amdgcn_wave_barrier();
         uint32_t cover_end = c_in;
         for (uint32_t e = 0; e < nev; e++) {
@@ -636,7 +732,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
             if (pe < cover_end) continue;
             cover_end = ee;
             if (lane == 0)
-                for (uint32_t q = pe + 1; q < ee && q < (uint32_t)kTile; q++) ws.cov[q >> 6] |= 1ull << (q & 63);
+                for (uint32_t q = pe + 1; q < ee && q < (uint32_t)kTile; q++) ws.cov()[q >> 6] |= 1ull << (q & 63);
         }
         if (cover_end > (uint32_t)kTile && cover_end - kTile > carry) carry = cover_end - kTile;
         __builtin_amdgcn_wave_barrier();
@@ -644,7 +740,7 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
     // lane r: the masks of round r
     uint64_t my_mask = 0, my_starts = 0;
     if (lane < kRounds) {
-        uint64_t cov = ws.cov[lane];
+        uint64_t cov = ws.cov()[lane];
         const uint32_t lo = 64u * lane;
         if (c_in > lo) cov |= c_in - lo >= 64 ? ~0ull : ((1ull << (c_in - lo)) - 1);
         const uint64_t slow = ws.slow[lane];
@@ -698,7 +794,28 @@ __device__ void walk_tile(const NpJob &job, const JumpTabs &g_jump, const uint4 
         }
     }
     if (MODE == kRecord && lane < kRounds) rec_mask[lane] = my_mask;
-    if constexpr (MODE == kCompact) {
+    if constexpr (MODE == kCompact && kParkBytes) {
+        static_assert(sizeof(typename Emit::Store) == 2, "compact records are int16");
+        int8_t *flat = (int8_t *)&ws.val[0][0];
+        const uint32_t total = compact_tile_lds_b8(flat, my_mask);     // == count
+        const uint32_t groups = (total + 7) >> 3;                      // the last group's surplus elements are never read
+        const uint2 *f8 = (const uint2 *)flat;
+        u32x4 VKX_GLOBAL *s16 = (u32x4 VKX_GLOBAL *)rec_val;
+#pragma unroll
+        for (int i = 0; i < kTile / 512; i++) {
+            const uint32_t idx = (uint32_t)lane + 64u * i;
+            if (idx < groups) {
+                const uint2 b = f8[idx];
+                u32x4 g;
+                g[0] = widen_b8_pair(b.x, 0x010c000cu);
+                g[1] = widen_b8_pair(b.x, 0x030c020cu);
+                g[2] = widen_b8_pair(b.y, 0x010c000cu);
+                g[3] = widen_b8_pair(b.y, 0x030c020cu);
+                s16[idx] = g;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    } else if constexpr (MODE == kCompact) {
         static_assert(sizeof(typename Emit::Store) == 2, "compact records are int16");
         int16_t *flat = (int16_t *)&ws.val[0][0];
         const uint32_t total = compact_tile_lds(flat, my_mask);        // == count
@@ -838,30 +955,40 @@ constexpr int kLent = 3;                 // a reader's 4-sample fetch that begin
 #define VKX_NP_DRAW_WAVES 8
 #endif
 constexpr int kDrawWaves = VKX_NP_DRAW_WAVES;
+// The byte-parked pass (EmitI16B8): 4 x 5 760 B + 8 KB = 31 232 B per workgroup, under the 32 000 B (25 LDS granules of 1 280 B) at
+// which five workgroups share a CU, and a register budget of 96: 20 wavefronts per CU, five per SIMD.  A workgroup's wavefronts go
+// round the four SIMDs, so only a multiple of four fills them evenly (two workgroups of ten never became resident together).
+#ifndef VKX_NP_DRAW_WAVES_B8
+#define VKX_NP_DRAW_WAVES_B8 4
+#endif
+template <class Emit> struct DrawShape { static constexpr int kWaves = kDrawWaves, kPerSimd = 0; };
+template <> struct DrawShape<EmitI16B8> { static constexpr int kWaves = VKX_NP_DRAW_WAVES_B8, kPerSimd = 5; };
 
 template <class Emit>
-__global__ void __launch_bounds__(64 * kDrawWaves) k_np_draw_compact(const NpJob *__restrict__ jobs, int n_jobs, long long total_tiles,
-                                                                    long long run, const uint64_t *__restrict__ states, TileInfo *__restrict__ info,
-                                                                    vkx_np_result *__restrict__ results, const NpTabs *__restrict__ tabs)
+__global__ void __launch_bounds__(64 * DrawShape<Emit>::kWaves, DrawShape<Emit>::kPerSimd)
+k_np_draw_compact(const NpJob *__restrict__ jobs, int n_jobs, long long total_tiles, long long run, const uint64_t *__restrict__ states,
+                  TileInfo *__restrict__ info, vkx_np_result *__restrict__ results, const NpTabs *__restrict__ tabs)
 {
     // one LDS block with the table first: a table entry's address is 16 idx, one shift of the draw (at the table's own LDS offset,
     // above the 64 KB a ds_read offset field reaches, it took one more instruction per round)
+    constexpr int kWaves = DrawShape<Emit>::kWaves;
+    typedef WaveWork<typename Emit::Park, true> Work;
     struct Lds {
         uint4 zig[256];
         FiC fic[256];
-        WaveWork<int16_t, true> work[kDrawWaves];
+        Work work[kWaves];
     };
     __shared__ Lds lds;
     uint4 *zig = lds.zig;
     FiC *fic = lds.fic;
-    WaveWork<int16_t, true> *work = lds.work;
+    Work *work = lds.work;
     load_tables(zig, fic, tabs);
     const JumpTabs &g_jump = tabs->jump;
     // a wavefront walks a run of consecutive tiles: the walk leaves the lane's states at the next tile's first two rounds, so the
     // job search and the start states (two full 128-bit products and a stride step per lane) are paid once per run and job, not
     // once per tile.  `run` = tiles per wavefront, ceil(total_tiles / wavefronts of the grid), from the host (the 64-bit division
     // on the device costs each wavefront about a hundred VALU instructions)
-    const long long wave = (long long)blockIdx.x * kDrawWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long wave = (long long)blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long run_end = min(total_tiles, (wave + 1) * run);
     int j = 0;
     long long job_end = 0;
@@ -879,9 +1006,11 @@ __global__ void __launch_bounds__(64 * kDrawWaves) k_np_draw_compact(const NpJob
         walk_tile<Emit, kCompact>(job, g_jump, zig, fic, work[threadIdx.x >> 6], s, s2, 0u, 0, 0,
                                   (int16_t VKX_GLOBAL *)(job.rec + (tile - job.tile_base) * kSlot), nullptr, nullptr,
                                   count, carry, start0, emit0, has_tail, flags, nullptr);
+        const bool over = __ballot((flags & kFlagParkOver) != 0) != 0;
+        flags &= ~kFlagParkOver;
         if (__lane_id() == 0) {
             TileInfo t;
-            t.count0 = count; t.out0 = carry | (has_tail ? 0x80000000u : 0u); t.start0 = start0; t.emit0 = emit0;
+            t.count0 = count; t.out0 = carry | (has_tail ? 0x80000000u : 0u) | (over ? kParkOver : 0u); t.start0 = start0; t.emit0 = emit0;
             info[tile] = t;
         }
         if (flags) atomicOr(&results[j].flags, flags);
@@ -913,9 +1042,10 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
         const int j = w * 64 + (threadIdx.x & 63);
         bool bad = false;
         if (j < T) {
-            const uint32_t c = j ? (info[j - 1].out0 & 0x7fffffffu) : 0u;
+            const uint32_t c = j ? (info[j - 1].out0 & kOutCarry) : 0u;
             const TileInfo t = info[j];
-            const bool ok = c < 64 && ((t.start0 >> c) & 1);
+            // (a tile marked kParkOver counts and carries like any other, but its slot is not to be read: phase B passes the mark on)
+            const bool ok = c < 64 && ((t.start0 >> c) & 1) && !(t.out0 & kParkOver);
             TilePlan p;
             p.prefix = 0;
             p.c_in = c;
@@ -942,7 +1072,7 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
                 const int j = w * 64 + b;
                 const TileInfo t = info[j];
                 const uint32_t c = ((volatile TilePlan *)plan)[j].c_in & ~kIrregular;
-                const uint32_t out0 = t.out0 & 0x7fffffffu;
+                const uint32_t out0 = t.out0 & kOutCarry;
                 uint32_t count, out;
                 bool simulated = false;
                 if (c < 64 && ((t.start0 >> c) & 1)) {
@@ -959,11 +1089,11 @@ __global__ void __launch_bounds__(1024) k_np_resolve(const NpJob *__restrict__ j
                 }
                 if (threadIdx.x == 0) {
                     plan[j].count = count;
-                    plan[j].c_in = c | (simulated ? kIrregular : 0u);
+                    plan[j].c_in = c | (simulated || (t.out0 & kParkOver) ? kIrregular : 0u);
                     irregular[w] = m & ~(1ull << b);
                     if (j + 1 < T && out != out0) {
                         const TileInfo tn = info[j + 1];
-                        const bool ok = out < 64 && ((tn.start0 >> out) & 1);
+                        const bool ok = out < 64 && ((tn.start0 >> out) & 1) && !(tn.out0 & kParkOver);
                         plan[j + 1].c_in = out;
                         plan[j + 1].count = ok ? tn.count0 - (uint32_t)__builtin_popcountll(tn.emit0 & ((1ull << out) - 1)) : 0u;
                         const int wn = (j + 1) >> 6;
@@ -1341,6 +1471,8 @@ VKX_EXPORT int vkx_np_tiles_layout(int64_t n, int64_t *n_tiles, int64_t *slot_el
     return VKX_OK;
 }
 
+VKX_EXPORT int vkx_np_parks_as_bytes(double scale, double loc) { return np_parks_as_bytes(scale, loc) ? 1 : 0; }
+
 // The three int16 kinds leave the draw pass as compacted tile slots; speckle records raw draws for the placement pass.
 static bool np_compact_records(int kind)
 {
@@ -1476,9 +1608,16 @@ static int np_chunk_front(vkx_ctx *ctx, NpChunk &c)
     if (np_compact_records(kind)) {
         // (the emitter only decides how a draw becomes an int16 step: the same for the three int16 kinds)
         VKX_TIMED_MAJOR(ctx, "k_np_draw");
-        const unsigned wgc = (unsigned)((total_tiles + (long long)kDrawWaves * tiles_per_wave - 1) / ((long long)kDrawWaves * tiles_per_wave));
-        const long long run = (total_tiles + (long long)wgc * kDrawWaves - 1) / ((long long)wgc * kDrawWaves);
-        k_np_draw_compact<EmitI16><<<wgc, 64 * kDrawWaves, 0, ctx->stream>>>(dj, n_jobs, total_tiles, run, states, info, res, tabs);
+        // bytes are parked per launch: when every job of it qualifies (np_parks_as_bytes); the device forms carry loc = 0
+        bool bytes = true;
+        for (int i = 0; i < n_jobs; i++) bytes = bytes && np_parks_as_bytes(c.jobs[i].scale, 0.0);
+        const long long waves = bytes ? DrawShape<EmitI16B8>::kWaves : DrawShape<EmitI16>::kWaves;
+        const unsigned wgc = (unsigned)((total_tiles + waves * tiles_per_wave - 1) / (waves * tiles_per_wave));
+        const long long run = (total_tiles + (long long)wgc * waves - 1) / ((long long)wgc * waves);
+        if (bytes)
+            k_np_draw_compact<EmitI16B8><<<wgc, 64 * (unsigned)waves, 0, ctx->stream>>>(dj, n_jobs, total_tiles, run, states, info, res, tabs);
+        else
+            k_np_draw_compact<EmitI16><<<wgc, 64 * (unsigned)waves, 0, ctx->stream>>>(dj, n_jobs, total_tiles, run, states, info, res, tabs);
         VKX_LAUNCH_CHECK();
         return VKX_OK;
     }
