@@ -85,6 +85,17 @@ int vkx_download_async(vkx_ctx *ctx, void *hptr, const void *dptr, size_t bytes)
 /* one copy on the named stream of the ctx: to_device 0 = device -> host, 1 = host -> device, 2 = device -> device */
 int vkx_memcpy_async(vkx_ctx *ctx, int stream, void *dst, const void *src, size_t bytes, int to_device);
 int vkx_ctx_order(vkx_ctx *ctx, int later_stream, int earlier_stream);
+/* Ordering against a stream the context does not own (the consumer's: torch.cuda.current_stream().cuda_stream), for memory the
+ * two share without a copy (vkit_amd/torch_bridge.py).  vkx_ctx_wait_external: the context's compute stream continues after
+ * everything queued on `hip_stream` at the time of the call; vkx_ctx_signal_external: `hip_stream` continues after everything
+ * queued on the context's compute stream at the time of the call.  Each is one event record and one hipStreamWaitEvent (the
+ * event comes from the context's pool and returns to it on every exit); the host never waits.  hip_stream == NULL names the
+ * LEGACY DEFAULT STREAM (handle 0, torch's default stream) -- unlike vkx_ctx_set_stream, where NULL means "restore".  Nothing
+ * is queued when `hip_stream` is the compute stream itself.  Refused before anything is queued: a NULL ctx and a stream of
+ * another device than the context's (VKX_ERR_INVALID); either stream in capture (VKX_ERR_UNSUPPORTED: a captured graph
+ * cannot carry an ordering against work outside it). */
+int vkx_ctx_wait_external(vkx_ctx *ctx, void *hip_stream);
+int vkx_ctx_signal_external(vkx_ctx *ctx, void *hip_stream);
 int vkx_ctx_sync_stream(vkx_ctx *ctx, int stream);
 int vkx_event_record(vkx_ctx *ctx, int stream, void **event);
 int vkx_event_wait(vkx_ctx *ctx, void *event);   /* waits on the host and releases the event */
@@ -1306,6 +1317,49 @@ int vkx_quad_interp_uv_dev(vkx_ctx *ctx, const vkx_quad *quad_host, float *uv, s
  * masks that overlap. */
 int vkx_box_label_masks_dev(vkx_ctx *ctx, const int32_t *boxes_host, int n_text, int n_dilated, int h, int w, uint8_t *text_mask,
                             uint8_t *boundary_mask, uint8_t *both_mask);
+
+/* ---- batch collate (vkit_amd/torch_bridge.py) ----------------------------------------------------------------------------
+ * The samples of a batch -- crops of several pages, each plane a dense block at its own device address -- into the dense batch
+ * tensors a training loop consumes, in at most TWO launches whatever the batch size, no synchronisation.  The reference has no
+ * such step (its samples leave as numpy arrays and the consumer stacks them); the arithmetic is fixed here so that it can be
+ * checked bit for bit (tests/collate_restate.py).
+ * Image launch (n_images > 0): images_host[i].src is a dense uint8 [height][width][3] block at ANY byte address (a view into a
+ * packed buffer need not be dword aligned: an aligned source is read as dwords, another byte by byte).  norm->dst is the batch:
+ * [n_images][3][height][width] (channels_first) or [n_images][height][width][3], dense, of norm->dtype, aligned to its
+ * element.  VKX_COLLATE_U8 is the plain transpose / copy; the float types are
+ *     out = (float32(x) - mean[c]) * scale[c]
+ * with ONE float32 subtraction and ONE float32 multiplication (never fused), and for F16 / BF16 one more rounding to nearest
+ * even.  (torch_bridge passes mean[c] = float32(255 mean_c), scale[c] = float32(1 / (255 std_c)), each worked out in float64
+ * and rounded once.)  mean and scale are finite.
+ * Plane launch (n_planes > 0): planes_host[i] copies `bytes` bytes from src to dst (label planes: uint8 masks and float32
+ * score maps into their place in a batch tensor), 16 bytes a lane where src and dst are both 16-byte aligned, single bytes
+ * otherwise.
+ * The tables are HOST tables; every src and dst is a DEVICE pointer.  Refused (VKX_ERR_INVALID, nothing launched, nothing
+ * written): a NULL ctx, a NULL table with a non-zero count, norm NULL with images, a NULL src or dst, a count below 0,
+ * n_images above 65535, n_planes above 2^20, height or width outside 1 .. 32768, a plane of 0 bytes or of 2^31 and more, an unknown
+ * dtype, channels_first other than 0 / 1, a dst not aligned to its element, a mean or scale that is not finite, two
+ * destinations that overlap, a destination that overlaps a source. */
+#define VKX_COLLATE_U8 0
+#define VKX_COLLATE_F32 1
+#define VKX_COLLATE_F16 2
+#define VKX_COLLATE_BF16 3
+typedef struct vkx_collate_image {
+    const uint8_t *src;   /* device, uint8 [height][width][3], dense */
+} vkx_collate_image;
+typedef struct vkx_collate_plane {
+    const void *src;      /* device */
+    void *dst;            /* device */
+    size_t bytes;
+} vkx_collate_plane;
+typedef struct vkx_collate_norm {
+    void *dst;                /* device, the image batch */
+    int32_t height, width;    /* of every source */
+    int32_t dtype;            /* VKX_COLLATE_* */
+    int32_t channels_first;   /* 1: [n][3][h][w]; 0: [n][h][w][3] */
+    float mean[3], scale[3];
+} vkx_collate_norm;
+int vkx_collate_dev(vkx_ctx *ctx, const vkx_collate_image *images_host, int n_images, const vkx_collate_plane *planes_host,
+                    int n_planes, const vkx_collate_norm *norm);
 
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx

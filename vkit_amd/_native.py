@@ -249,6 +249,19 @@ class VkxCropPlane(ctypes.Structure):
         (name, ctypes.c_int32) for name in ('cn', 'is_f32', 'core_only', 'is_mask', 'clip', 'fill', 'window')]
 
 
+class VkxCollateImage(ctypes.Structure):
+    _fields_ = [('src', c_void_p)]
+
+
+class VkxCollatePlane(ctypes.Structure):
+    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('bytes', ctypes.c_size_t)]
+
+
+class VkxCollateNorm(ctypes.Structure):
+    _fields_ = [('dst', c_void_p), ('height', ctypes.c_int32), ('width', ctypes.c_int32), ('dtype', ctypes.c_int32),
+                ('channels_first', ctypes.c_int32), ('mean', ctypes.c_float * 3), ('scale', ctypes.c_float * 3)]
+
+
 class VkxCombineTile(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in ('up', 'down', 'left', 'right', 'source')]
 
@@ -407,6 +420,10 @@ _SIGNATURES['vkx_set_mask'] = _SIGNATURES['vkx_set_mask_dev']
 _SIGNATURES['vkx_quad_interp_fill_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
 _SIGNATURES['vkx_quad_interp_uv_dev'] = [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_box_label_masks_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+_SIGNATURES['vkx_ctx_wait_external'] = [c_void_p, c_void_p]
+_SIGNATURES['vkx_ctx_signal_external'] = [c_void_p, c_void_p]
+_SIGNATURES['vkx_collate_dev'] = [c_void_p, ctypes.POINTER(VkxCollateImage), c_int, ctypes.POINTER(VkxCollatePlane), c_int,
+                                  ctypes.POINTER(VkxCollateNorm)]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
 _lib = None
@@ -573,6 +590,15 @@ class Context:
     def order(self, later_stream, earlier_stream):
         check(lib().vkx_ctx_order(self.handle, int(later_stream), int(earlier_stream)))
 
+    def wait_external(self, stream_ptr):
+        """The compute stream continues after everything queued so far on the foreign stream ``stream_ptr`` (a hipStream_t as an
+        int; 0 is the legacy default stream, torch's default).  No host wait."""
+        check(lib().vkx_ctx_wait_external(self.handle, c_void_p(stream_ptr) if stream_ptr else None))
+
+    def signal_external(self, stream_ptr):
+        """The foreign stream ``stream_ptr`` continues after everything queued so far on the compute stream.  No host wait."""
+        check(lib().vkx_ctx_signal_external(self.handle, c_void_p(stream_ptr) if stream_ptr else None))
+
     def sync_stream(self, stream):
         check(lib().vkx_ctx_sync_stream(self.handle, int(stream)))
 
@@ -628,13 +654,30 @@ class DevArray:
     """A C-contiguous array in device memory: ``shape`` / ``dtype`` / ``ndim`` / ``nbytes`` like numpy, ``ptr`` the device
     address, ``host()`` the (cached, page-locked) numpy copy.  Every kernel of a context runs on its one stream, so arrays
     chain from call to call without synchronisation; the block returns to the context's pool when the object dies --
-    whatever is still queued on the stream has been queued before any later user of the block."""
+    whatever is still queued on the stream has been queued before any later user of the block.  An array that was handed to
+    torch without a copy (``vkit_amd.torch_bridge.as_tensor``) has users on other streams: ``_viewed`` holds the handles of the
+    streams it was viewed from, and the context's stream is ordered behind them before the array is read through ``_Call`` or
+    ``host()`` and before its block returns to the pool."""
 
-    __slots__ = ('ctx', 'ptr', 'shape', 'dtype', '_host', '_size', '__weakref__')
+    __slots__ = ('ctx', 'ptr', 'shape', 'dtype', '_host', '_size', '_viewed', '__weakref__')
 
     def __init__(self, ctx, ptr, shape, dtype, size):
         self.ctx, self.ptr, self.shape, self.dtype, self._size = ctx, ptr, tuple(int(v) for v in shape), np.dtype(dtype), size
         self._host = None
+        self._viewed = None
+
+    @property
+    def __cuda_array_interface__(self):
+        """Version 2 of the array interface torch-ROCm reads (``torch.as_tensor``): the block as it is, no stream entry -- the
+        ordering is ``torch_bridge.as_tensor``'s, which is the way to a tensor."""
+        return {'shape': self.shape, 'typestr': self.dtype.str, 'data': (int(self.ptr), False), 'version': 2, 'strides': None}
+
+    def after_views(self, ctx=None):
+        """The stream of ``ctx`` (default: the array's own context) continues after everything queued so far on the streams the
+        array was viewed from."""
+        if self._viewed:
+            for stream in sorted(self._viewed):
+                (ctx or self.ctx).wait_external(stream)
 
     @property
     def ndim(self):
@@ -653,6 +696,7 @@ class DevArray:
         if self._host is None:
             out = self.ctx.pinned_empty(self.shape, self.dtype)
             if self.nbytes:
+                self.after_views()
                 self.ctx.download(self.ptr, out)
             self._host = out
         return self._host
@@ -678,6 +722,13 @@ class DevicePool:
         self._idle = 0
         self.cap_bytes = cap_bytes
         self._lock = threading.Lock()
+        self._viewed = {}               # block -> the streams it was viewed from (torch_bridge.as_tensor), while its array lives
+
+    def note_view(self, arr, stream):
+        """``arr`` (an array of this pool) is about to be used on the foreign stream ``stream``."""
+        if arr._viewed is None:
+            arr._viewed = self._viewed.setdefault(arr.ptr, set())
+        arr._viewed.add(stream)
 
     def empty(self, shape, dtype=np.uint8):
         ctx = self._ctx()
@@ -699,6 +750,19 @@ class DevicePool:
         ctx = self._ctx()
         if ctx is None or not ctx._h:
             return                      # the context is gone and took its allocations with the process
+        viewed = self._viewed.pop(ptr, None) if self._viewed else None
+        if viewed:
+            # the pool's invariant -- whatever is still queued has been queued before any later user of the block -- holds for
+            # the context's own stream only: the next user waits for the streams the block was viewed from
+            try:
+                for stream in sorted(viewed):
+                    ctx.wait_external(stream)
+            except Exception:
+                try:
+                    ctx.free(ptr)       # no ordering to be had: the block does not go round again (hipFree waits for the device)
+                except Exception:
+                    pass
+                return
         with self._lock:
             if self._idle + size <= self.cap_bytes:
                 self._free.setdefault(size, []).append(ptr)
@@ -1023,6 +1087,8 @@ class _Call:
             if not isinstance(a, DevArray):
                 a = np.ascontiguousarray(a, dtype=dtype) if dtype is not None else np.ascontiguousarray(a)
                 a = self.ctx.to_device(a)
+            elif a._viewed:
+                a.after_views(self.ctx)
             self.keep.append(a)
             return c_void_p(a.ptr)
         a = host_array(a)
@@ -2545,6 +2611,7 @@ class DevView(DevArray):
     def __init__(self, base, offset, shape, dtype=np.uint8):
         super().__init__(base.ctx, base.ptr + int(offset), shape, dtype, 0)
         self.base = base
+        self._viewed = base._viewed
         assert 0 <= offset and offset + self.nbytes <= base.nbytes
 
 

@@ -125,6 +125,7 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->text_planes);
     scratch_release(&ctx->layer_tables);
     scratch_release(&ctx->quad_tables);
+    scratch_release(&ctx->collate_tables);
     scratch_release(&ctx->glass_win);
     scratch_release(&ctx->jpeg_planes);
     scratch_release(&ctx->pz_tabs);
@@ -480,6 +481,68 @@ VKX_EXPORT int vkx_ctx_order(vkx_ctx *ctx, int later_stream, int earlier_stream)
     ctx->order_events.push_back(e);      // a recorded event may be re-recorded once the wait has been queued
     return VKX_OK;
 }
+
+// VKX_OK where `s` is not capturing; VKX_ERR_UNSUPPORTED where it is, or where a capture under way elsewhere forbids asking
+// (the legacy stream during a global-mode capture).
+static int require_not_capturing(hipStream_t s, const char *who)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(s, &status);
+    if (e == hipSuccess && status == hipStreamCaptureStatusNone) return VKX_OK;
+    (void)hipGetLastError();
+    if (e == hipSuccess || e == hipErrorStreamCaptureImplicit || e == hipErrorStreamCaptureUnsupported) {
+        vkx_set_error("%s: a stream is being captured; ordering against a stream outside the graph is not supported", who);
+        return VKX_ERR_UNSUPPORTED;
+    }
+    vkx_set_error("%s: hipStreamIsCapturing failed: %s", who, hipGetErrorString(e));
+    return VKX_ERR_HIP;
+}
+
+// vkx_ctx_wait_external (external_first) / vkx_ctx_signal_external: checks first, then one record and one wait; the event is back
+// in the pool on every exit.
+static int order_external(vkx_ctx *ctx, void *hip_stream, bool external_first, const char *who)
+{
+    if (!ctx) {
+        vkx_set_error("%s: ctx is NULL", who);
+        return VKX_ERR_INVALID;
+    }
+    vkx_device_guard guard(ctx);
+    hipStream_t ext = (hipStream_t)hip_stream;            // NULL: the legacy default stream of the context's device
+    if (ext) {
+        hipDevice_t dev = -1;
+        if (hipStreamGetDevice(ext, &dev) != hipSuccess) {
+            (void)hipGetLastError();
+            vkx_set_error("%s: not a stream of this process", who);
+            return VKX_ERR_INVALID;
+        }
+        if ((int)dev != ctx->device) {
+            vkx_set_error("%s: the stream belongs to device %d, the ctx to device %d", who, (int)dev, ctx->device);
+            return VKX_ERR_INVALID;
+        }
+    }
+    int rc;
+    if ((rc = require_not_capturing(ctx->stream, who)) || (rc = require_not_capturing(ext, who))) return rc;
+    if (ext == ctx->stream) return VKX_OK;
+    hipStream_t earlier = external_first ? ext : ctx->stream, later = external_first ? ctx->stream : ext;
+    hipEvent_t e = take_order_event(ctx);
+    if (!e) {
+        (void)hipGetLastError();
+        vkx_set_error("%s: hipEventCreate failed", who);
+        return VKX_ERR_HIP;
+    }
+    hipError_t err = hipEventRecord(e, earlier);
+    if (err == hipSuccess) err = hipStreamWaitEvent(later, e, 0);
+    ctx->order_events.push_back(e);      // (a recorded event may be re-recorded once the wait has been queued)
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        vkx_set_error("%s: %s", who, hipGetErrorString(err));
+        return VKX_ERR_HIP;
+    }
+    return VKX_OK;
+}
+
+VKX_EXPORT int vkx_ctx_wait_external(vkx_ctx *ctx, void *hip_stream) { return order_external(ctx, hip_stream, true, __func__); }
+VKX_EXPORT int vkx_ctx_signal_external(vkx_ctx *ctx, void *hip_stream) { return order_external(ctx, hip_stream, false, __func__); }
 
 // `later` continues after everything queued on `earlier` so far (internal form of vkx_ctx_order on raw streams)
 int vkx_stream_order(vkx_ctx *ctx, hipStream_t later, hipStream_t earlier)
