@@ -24,6 +24,7 @@ SOAKS = [
     ('soak8.py', ['160'], 'rng.poisson on the device vs numpy: values and stream position; declined images are counted'),
     ('soak9.py', ['8', '506'], 'fog field and glass_blur shuffle planes vs their host restatements, planes and stream position'),
     ('soak10.py', ['8', '507'], 'k_composite_rgb (batched RGB pages of whole 4-pixel groups, every layer kind, stacked layers) vs the sequential oracle fills'),
+    ('soak11.py', ['6', '508'], 'the batch collate (raw vkx_collate_dev: images around the 1024-pixel group runs, plane records around 4096 bytes, random alignments, edge constants) vs its host restatement'),
 ]
 
 
@@ -50,11 +51,13 @@ def test_bounded_soak(script, argv, what):
     print(f'{script}: {tail}')
     assert proc.returncode == 0, f'{script} {argv} ({what}) failed:\n{proc.stdout[-2000:]}\n{proc.stderr[-4000:]}'
     entry = {'argv': argv, 'covers': what, 'result': tail}
-    if script in ('soak8.py', 'soak9.py', 'soak10.py'):
+    if script in ('soak8.py', 'soak9.py', 'soak10.py', 'soak11.py'):
         report = json.loads(tail)
         entry['result'] = report
         if script == 'soak10.py':
             assert report['soak10'] == 'ok' and report['layers'] > 0, report
+        elif script == 'soak11.py':
+            assert report['soak11'] == 'ok' and report['calls'] > 0, report
         elif script == 'soak8.py':
             # a declined image (near tie of the PTRS comparison, a start outside its 6-sigma window) falls back to numpy: correct,
             # and rare -- one image in ~3 000 in the builder's 4 G-element soak

@@ -44,12 +44,70 @@ def test_restatement_agrees_with_torch_cpu_ops(dtype, channels_first):
     assert R.same_bits(got, want)
 
 
+@pytest.mark.parametrize('name', list(R.EDGE_CONSTANTS))
+def test_restatement_equals_a_float64_evaluation_at_the_edge_constants(name):
+    """Every byte value in every channel.  float64(x) - float64(m) is exact (an integer below 256 against a float32), and the test
+    asserts that it fits float32, so the restatement's float32 subtraction did not round; its product with float64(s) is exact too
+    (24 + 24 bits of 53); ONE rounding to float32 -- to a subnormal, to zero or to infinity where the set goes there -- is the batch."""
+    mean, std = R.EDGE_CONSTANTS[name]
+    image = R.edge_image()
+    m, s = R.constants(mean, std)
+    assert m.dtype == s.dtype == np.float32 and np.isfinite(m).all() and np.isfinite(s).all() and (s != 0).all()
+    diff = image.astype(np.float64) - m.astype(np.float64)
+    assert (diff.astype(np.float32).astype(np.float64) == diff).all()
+    product = diff * s.astype(np.float64)
+    assert np.isfinite(product).all() and ((product != 0) | (diff == 0)).all()                    # float64 has the room
+    mantissa, _ = np.frexp(product)
+    assert (mantissa * 2.0 ** 48 == np.round(mantissa * 2.0 ** 48)).all()                           # 48 bits: nothing was rounded off
+    with np.errstate(over='ignore', under='ignore'):
+        want = product.astype(np.float32)
+    got = R.collate_images([image], 'float32', mean, std, channels_first=False)
+    assert got.dtype == np.float32 and R.same_bits(got, want[None])
+    assert R.same_bits(R.collate_images([image], 'float32', mean, std), np.ascontiguousarray(want.transpose(2, 0, 1))[None])
+    for dtype, reached in R.EDGE_REACHES[name].items():
+        found = R.classes(R.collate_images([image], dtype, mean, std))
+        assert all(found[c] > 0 for c in reached) and found['nan'] == 0, (dtype, found)
+
+
+@pytest.mark.parametrize('channels_first', [True, False])
+@pytest.mark.parametrize('dtype', ['float32', 'float16', 'bfloat16'])
+@pytest.mark.parametrize('name', list(R.EDGE_CONSTANTS))
+def test_restatement_agrees_with_torch_cpu_ops_at_the_edge_constants(name, dtype, channels_first):
+    mean, std = R.EDGE_CONSTANTS[name]
+    rng = np.random.default_rng(6)
+    images = [R.edge_image()] + [rng.integers(0, 256, (16, 16, 3), dtype=np.uint8) for _ in range(2)]
+    got = R.collate_images(images, dtype, mean, std, channels_first=channels_first)
+    m = (255.0 * torch.tensor(mean, dtype=torch.float64)).to(torch.float32)
+    s = (1.0 / (255.0 * torch.tensor(std, dtype=torch.float64))).to(torch.float32)
+    assert R.same_bits(m, R.constants(mean, std)[0]) and R.same_bits(s, R.constants(mean, std)[1])
+    x = torch.stack([torch.from_numpy(i) for i in images]).to(torch.float32).sub(m).mul(s)
+    if channels_first:
+        x = x.permute(0, 3, 1, 2)
+    want = x.contiguous().to(TORCH_DTYPES[dtype])
+    assert R.same_bits(got, want)
+    found = R.classes(got)
+    assert all(found[c] > 0 for c in R.EDGE_REACHES[name].get(dtype, ())) and found['nan'] == 0, found
+
+
 def test_bridge_constants_are_the_restatement_s():
     m, s = TB.norm_constants(R.MEAN, R.STD)
     rm, rs = R.constants()
     assert m.dtype == s.dtype == np.float32 and R.same_bits(m, rm) and R.same_bits(s, rs)
     # rounded once from float64: not the float32 product / quotient
     assert float(m[0]) == float(np.float32(255.0 * 0.485)) and float(s[2]) == float(np.float32(1.0 / (255.0 * 0.225)))
+    for mean, std in R.EDGE_CONSTANTS.values():                            # subnormal scales and scales near the top of float32 included
+        m, s = TB.norm_constants(mean, std)
+        assert R.same_bits(m, R.constants(mean, std)[0]) and R.same_bits(s, R.constants(mean, std)[1])
+
+
+def test_norm_constants_refuse_what_float32_cannot_hold():
+    for kw, message in ((dict(std=(1e-41, 1, 1)), r'std\[0\] = 1e-41'), (dict(std=(1, 1e-320, 1)), r'std\[1\] = 1e-320'),
+                        (dict(std=(1, 1, -1e-41)), r'std\[2\] = -1e-41'), (dict(mean=(2e36, 0, 0)), r'mean\[0\] = 2e\+36'),
+                        (dict(mean=(0, 0, -2e36)), r'mean\[2\] = -2e\+36')):
+        with pytest.raises(ValueError, match=message + '.*not finite'):
+            TB.norm_constants(**{'mean': (0, 0, 0), 'std': (1, 1, 1), **kw})
+    m, s = TB.norm_constants((1.3e36, 0, 0), (1e308, 1.2e-41, 1e36))        # the largest of their kind that float32 still holds
+    assert np.isfinite(m).all() and np.isfinite(s).all() and s[0] == 0 and s[1] > 3e38 and 0 < s[2] < 1e-38
 
 
 # ---- the host plan ---------------------------------------------------------------------------------------------------------
@@ -71,6 +129,41 @@ def test_plan_groups_tail_and_plane_paths(width, offset):
     assert [(p['src'], p['dst'], p['bytes']) for p in plan['planes']] == planes
     assert [p['first_block'] for p in plan['planes']] == [0, 1, 2] and plan['plane_blocks'] == 2 + 3      # 20000 bytes: 3 x 8 KB
     assert plan['plane_bytes'] == 2 * (pixels + 4 * pixels + 20000)
+
+
+# (h, w) -> groups, tail, workgroups a sample: the boundaries of a lane's two groups (256 lanes x 2 groups x 4 pixels a workgroup)
+BOUNDARY_SHAPES = {(1, 1): (0, 1, 1), (1, 2): (0, 2, 1), (1, 3): (0, 3, 1), (32, 32): (256, 0, 1), (13, 79): (256, 3, 1),
+                   (4, 257): (257, 0, 1), (32, 64): (512, 0, 1), (7, 293): (512, 3, 1), (27, 76): (513, 0, 2), (41, 100): (1025, 0, 3),
+                   (3, 1367): (1025, 1, 3)}
+# bytes of a plane -> its workgroups (8192 bytes each)
+PLANE_WORKGROUPS = {1: 1, 15: 1, 16: 1, 17: 1, 4095: 1, 4096: 1, 4097: 1, 4111: 1, 4112: 1, 8191: 1, 8192: 1, 8193: 2, 8208: 2, 12288: 2,
+                    16389: 3, 24576 + 4097: 4}
+
+
+@pytest.mark.parametrize('shape', list(BOUNDARY_SHAPES), ids=lambda s: f'{s[0]}x{s[1]}')
+def test_plan_at_the_group_and_workgroup_boundaries(shape):
+    groups, tail, blocks = BOUNDARY_SHAPES[shape]
+    for dtype in R.DTYPES:
+        for n in (1, 3):
+            plan = TB.collate_plan([4096 + 16384 * i for i in range(n)], shape, dtype, 1 << 20, [])
+            assert (plan['groups'], plan['tail'], plan['image_grid']) == (groups, tail, (blocks, n)), (dtype, n)
+            assert plan['groups'] * 4 + plan['tail'] == shape[0] * shape[1] and plan['planes'] == [] and plan['plane_blocks'] == 0
+
+
+def test_plan_of_plane_records_of_several_workgroups():
+    src, dst = 0x7F0000100000, 0x7F0000900000
+    sizes = list(PLANE_WORKGROUPS) + list(PLANE_WORKGROUPS)[::-1]           # one-workgroup records between multi-workgroup ones, both ways
+    planes = [(src + 65536 * i + (i % 3 == 1), dst + 65536 * i + 4 * (i % 3 == 2), b) for i, b in enumerate(sizes)]
+    plan = TB.collate_plan([], (1, 1), 'uint8', 0, planes)
+    want_first = list(range(11)) + [11, 13, 15, 17, 20] + [24, 28, 31, 33, 35] + list(range(37, 48))
+    assert [p['first_block'] for p in plan['planes']] == want_first
+    assert want_first == [sum(PLANE_WORKGROUPS[b] for b in sizes[:i]) for i in range(len(sizes))]
+    assert plan['plane_blocks'] == 2 * sum(PLANE_WORKGROUPS.values()) == 48
+    assert [p['wide'] for p in plan['planes']] == [i % 3 == 0 for i in range(len(sizes))]
+    assert plan['plane_bytes'] == 2 * 2 * sum(PLANE_WORKGROUPS) and plan['image_grid'] == (1, 0)
+    for nbytes, blocks in PLANE_WORKGROUPS.items():                           # each alone
+        plan = TB.collate_plan([], (1, 1), 'uint8', 0, [(src, dst, nbytes)])
+        assert plan['planes'][0]['first_block'] == 0 and plan['plane_blocks'] == blocks, nbytes
 
 
 def test_plan_grid_grows_with_the_sample_and_refuses_bad_input():
@@ -158,6 +251,13 @@ def test_collate_refusals_before_any_device_call(monkeypatch):
         TB.collate_cropped_pages([sample(ctx)], std=(0.2, 0.0, 0.2))
     with pytest.raises(ValueError, match='finite'):
         TB.collate_cropped_pages([sample(ctx)], mean=(0.2, float('nan'), 0.2))
+    # constants that are finite as given and not as float32: s = 1 / (255 std) overflows, so does m = 255 mean
+    with pytest.raises(ValueError, match=r'std\[0\] = 1e-41.*not finite'):
+        TB.collate_cropped_pages([sample(ctx)], std=(1e-41, 1, 1))
+    with pytest.raises(ValueError, match=r'std\[0\] = 1e-320.*not finite'):
+        TB.collate_cropped_pages([sample(ctx)], std=(1e-320, 1, 1))
+    with pytest.raises(ValueError, match=r'mean\[0\] = 2e\+36.*not finite'):
+        TB.collate_cropped_pages([sample(ctx)], mean=(2e36, 0, 0))
     for bad in ('float64', torch.int8, np.int16):
         with pytest.raises(ValueError, match='image_dtype'):
             TB.collate_cropped_pages([sample(ctx)], image_dtype=bad)

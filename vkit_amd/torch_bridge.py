@@ -142,7 +142,8 @@ def release(arr):
 # ---- the collate ---------------------------------------------------------------------------------------------------------
 def norm_constants(mean, std):
     """(m, s) of ``out = (float32(x) - m_c) * s_c``: m_c = float32(255 mean_c), s_c = float32(1 / (255 std_c)), each worked out in
-    float64 and rounded once."""
+    float64 and rounded once.  Both must be finite AS float32 (a std below about 1.2e-41 or a mean above about 1.3e36 is refused
+    here, before anything is allocated or queued); a scale that rounds to zero is finite."""
     mean, std = [float(v) for v in mean], [float(v) for v in std]
     if len(mean) != 3 or len(std) != 3:
         raise ValueError('mean and std have one entry a channel (3)')
@@ -150,8 +151,16 @@ def norm_constants(mean, std):
         raise ValueError('mean and std are finite')
     if any(v == 0.0 for v in std):
         raise ValueError('std has a zero: the scale 1 / (255 std) does not exist')
-    return (np.array([255.0 * v for v in mean], np.float64).astype(np.float32),
-            np.array([1.0 / (255.0 * v) for v in std], np.float64).astype(np.float32))
+    with np.errstate(over='ignore', divide='ignore'):
+        m = np.array([255.0 * v for v in mean], np.float64).astype(np.float32)
+        # (np.float64: 255 std may be subnormal, or round to zero, and its reciprocal is infinite -- refused just below)
+        s = (1.0 / np.array([255.0 * v for v in std], np.float64)).astype(np.float32)
+    for name, given, constants in (('mean', mean, m), ('std', std, s)):
+        for c in range(3):
+            if not np.isfinite(constants[c]):
+                raise ValueError(f'{name}[{c}] = {given[c]!r}: its float32 constant {"255 mean" if name == "mean" else "1 / (255 std)"} '
+                                 f'is not finite')
+    return m, s
 
 
 def _dtype_name(dtype):
