@@ -1082,6 +1082,39 @@ int vkx_region_extend_masks_dev(vkx_ctx *ctx, const vkx_region_masks_rec *region
                                 const uint8_t *text_mask, ptrdiff_t text_mask_step, int page_h, int page_w, uint8_t *dst,
                                 size_t dst_bytes);
 
+/* ---- Mask.to_disconnected_polygons (element/mask.py:657-733) ---------------------------------------------------------------
+ * vkx_mask_contours_dev: cv.findContours(mask * 255, RETR_TREE, method) of n_masks masks, of which the contours with hierarchy
+ * parent -1 are returned (keep_internal=False): the outer borders of the components that no hole encloses, in the order of their
+ * raster-first pixels.  Pixels > 0 are foreground, 8-connected; background is 4-connected and surrounds the plane.  Each border
+ * is OpenCV's icvFetchContour trace from that first pixel; method VKX_CHAIN_APPROX_NONE keeps every border pixel,
+ * VKX_CHAIN_APPROX_SIMPLE the pixels where the direction changes.  Restated from the published algorithm, not pinned against
+ * a cv2 binary.  A record addresses its mask by device pointer and row step (the pitch contract of this header): a mask may be
+ * a rectangle inside a page plane.  Eight launches whatever the masks hold, no synchronisation; label planes, start bitmaps and
+ * contour lengths (about 9.2 bytes a pixel of the batch) are context scratch, kept until the context is destroyed.
+ * Outputs (DEVICE, dense):
+ *   n_contours int32 [n_masks]; contour_len, contour_off int32 [cap_contours]: the contours of mask 0, then of mask 1, ...;
+ *   contour_off is a contour's first point in `points` int32 [cap_points][2] (x, y);
+ *   totals int64 [n_masks][2]: the contours and the points the mask needs, always complete;
+ *   status int32 [n_masks]: 0, or VKX_CONTOURS_SHORT (the batch needs more than cap_contours contours or cap_points points:
+ *   n_contours is 0 for every mask, and contour_len, contour_off and points are not written at all -- call again with the sums
+ *   of totals) ored with VKX_CONTOURS_GAVE_UP (a trace of this mask reached its cap of 8 * h * w + 8 steps, which a plane that
+ *   stays unchanged during the call never does: the mask's contours are not to be used).
+ * Refused (VKX_ERR_INVALID, nothing launched): a NULL pointer, n_masks outside 1 .. 4096, a side outside 1 .. 32767, a mask of
+ * more than 2^31 - 8 pixels or a batch of more than 2^32, a row step shorter than a row or negative, an unknown method, a
+ * negative capacity, outputs that overlap one another or a mask. */
+#define VKX_CHAIN_APPROX_NONE 1
+#define VKX_CHAIN_APPROX_SIMPLE 2
+#define VKX_CONTOURS_SHORT 1
+#define VKX_CONTOURS_GAVE_UP 2
+typedef struct vkx_contour_mask {
+    const uint8_t *mask;                /* device uint8 [h][w] */
+    int64_t step;
+    int32_t h, w;
+} vkx_contour_mask;
+int vkx_mask_contours_dev(vkx_ctx *ctx, const vkx_contour_mask *masks_host, int n_masks, int method, int cap_contours,
+                          int cap_points, int32_t *n_contours, int32_t *contour_len, int32_t *contour_off, int32_t *points,
+                          int64_t *totals, int32_t *status);
+
 /* ---- the set-operation mask of a list of elements (element/mask.py:126-244) -----------------------------------------------
  * Mask.from_boxes / from_polygons / from_masks / from_score_maps and, through generate_fill_by_*_mask, the DISTINCT / INTERSECT
  * forms of the fill_by_* families (element/image.py:371-665, mask.py:283-410, score_map.py:315-520): count(y, x) is the number

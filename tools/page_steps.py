@@ -18,7 +18,13 @@ ways: the batched path of csrc/region_flatten.hip (build_flattened_text_regions,
 post_rotate_flattened_text_regions, stack_flattened_text_regions) and the same work composed per region from the single-plane
 operators (Mask.extract_image, rotate.distort, the external box in numpy, to_cropped_image, to_resized_image / to_resized_mask,
 Box.fill_image / fill_mask).  The record (default profiles/text_region_flatten_kernels.json) holds, for each, the wall time, the
-time of every kernel and the dispatch counts per page."""
+time of every kernel and the dispatch counts per page.
+
+    tools/page_steps.py contours [size] [out.json]
+
+runs Mask.to_disconnected_polygons (csrc/contours.hip) on a device-resident page mask (default 1024^2) of 64 slanted text-line
+quads, and masks_to_disconnected_polygons on a batch of 128 device-resident pair masks of about 40 x 300.  The record (default
+profiles/contours_kernels.json) holds, for each, the time of every kernel, the dispatch count and the wall time of a call."""
 import cProfile
 import io
 import json
@@ -38,7 +44,7 @@ from vkit_amd.pipeline.text_detection.synthetic_page import synthetic_page_input
 from vkit_amd import _native as N
 from vkit_amd.pipeline import text_detection as T
 
-LEG = len(sys.argv) > 1 and sys.argv[1] in ('text_region_cropping', 'text_region_flatten')
+LEG = len(sys.argv) > 1 and sys.argv[1] in ('text_region_cropping', 'text_region_flatten', 'contours')
 size = int(sys.argv[1]) if len(sys.argv) > 1 and not LEG else 1024
 n_lines = int(sys.argv[2]) if len(sys.argv) > 2 and not LEG else 64
 ctx = N.default_ctx()
@@ -249,6 +255,69 @@ def text_region_flatten_leg(size, path):
     print(json.dumps(record, indent=1))
 
 
+def contours_leg(size, path):
+    from vkit_amd.element import Mask
+    from vkit_amd.element.mask import masks_to_disconnected_polygons
+    rng = default_rng(23)
+    reps = 20
+    yy, xx = np.mgrid[:size, :size]
+    page = np.zeros((size, size), np.uint8)
+    for k in range(64):                                               # 64 text lines, 7 px thick, slanted by 1 .. 2 px in 100
+        slope, centre = rng.uniform(0.01, 0.02), (k + 0.5) * size / 64
+        page |= ((np.abs(yy - (centre + slope * (xx - size / 2))) <= 3) & (xx >= size // 25) & (xx < size - size // 25)).astype(np.uint8)
+    pairs = []
+    for _ in range(128):                                              # a precise polygon cut by a text region: a slanted band
+        h, w = int(rng.integers(30, 51)), int(rng.integers(250, 351))
+        y, x = np.mgrid[:h, :w]
+        slope = rng.uniform(-0.03, 0.03)
+        pairs.append(((np.abs(y - (h / 2 + slope * (x - w / 2))) <= h / 4) & (x >= 3) & (x < w - 3)).astype(np.uint8))
+    page_mask = Mask(mat=ctx.to_device(page))
+    pair_masks = [Mask(mat=ctx.to_device(mat)) for mat in pairs]
+
+    def measure(fn):
+        out = fn()
+        ctx.sync()
+        calls = []
+        real = N.mask_contours_raw
+        N.mask_contours_raw = lambda *a, **k: calls.append(1) or real(*a, **k)
+        ctx.set_timing(True)
+        ctx.reset_timings()
+        each = []
+        try:
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                each.append(time.perf_counter() - t0)
+            timings = ctx.timings()
+        finally:
+            ctx.set_timing(False)
+            N.mask_contours_raw = real
+        each.sort()
+        return {'polygons': sum(len(polygons) for polygons in out), 'points': sum(p.num_points for polygons in out for p in polygons),
+                'contour_calls_per_call': round(len(calls) / reps, 2),
+                'wall_ms': {'median_ms': round(each[reps // 2] * 1e3, 3), 'min_ms': round(each[0] * 1e3, 3), 'max_ms': round(each[-1] * 1e3, 3)},
+                'kernel_ms_per_call': {name: round(ms / reps, 4) for name, (ms, _cnt) in sorted(timings.items())},
+                'kernel_ms_per_call_total': round(sum(ms for ms, _cnt in timings.values()) / reps, 4),
+                'dispatches_per_call': round(sum(cnt for _ms, cnt in timings.values()) / reps, 2)}
+
+    record = {'runs': reps, 'method': 'CHAIN_APPROX_SIMPLE',
+              'page_mask': dict(measure(lambda: [page_mask.to_disconnected_polygons()]), shape=[size, size], text_lines=64),
+              'pair_masks': dict(measure(lambda: masks_to_disconnected_polygons(pair_masks)), masks=len(pair_masks),
+                                 pixels=int(sum(mat.size for mat in pairs))),
+              'note': 'device-resident masks; a call ends with its one copy-out and one Context.sync and wall_ms includes the host '
+                      'work of the element layer (records, the polygons built from the points); kernel times are measured with event '
+                      'pairs, which add a few microseconds a dispatch to the wall time; contour_calls_per_call is 2 where the default '
+                      'capacities were short and the call was repeated with the sizes the first one reported'}
+    with open(path, 'w') as f:
+        json.dump(record, f, indent=1)
+        f.write('\n')
+    print(json.dumps(record, indent=1))
+
+
+if LEG and sys.argv[1] == 'contours':
+    contours_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
+                 sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, 'profiles', 'contours_kernels.json'))
+    sys.exit(0)
 if LEG and sys.argv[1] == 'text_region_flatten':
     text_region_flatten_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 1024,
                             sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, 'profiles', 'text_region_flatten_kernels.json'))

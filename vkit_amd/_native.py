@@ -410,7 +410,8 @@ _SIGNATURES['vkx_region_resize_dev'] = [c_void_p, c_void_p, c_int, c_void_p, cty
 _SIGNATURES['vkx_region_stack_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int]
 _SIGNATURES['vkx_region_extend_masks_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_ssize, c_int, c_int, c_void_p,
                                               ctypes.c_size_t]
-_SIGNATURES['vkx_fill_u8_batch_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
+_SIGNATURES['vkx_mask_contours_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6
+_SIGNATURES['vkx_fill_u8_batch_dev'] =[c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 _SIGNATURES['vkx_seal_fill_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_text_lines_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_page_layers_dev'] = [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
@@ -2692,6 +2693,110 @@ def region_extend_masks(records, points_xy, text_mask, dst, text_mask_step=None)
 
 
 # --------------------------------------------------------------------------------------------------------------
+# Mask.to_disconnected_polygons for a batch of masks (csrc/contours.hip): vkx_contour_mask of include/vkx.h
+# --------------------------------------------------------------------------------------------------------------
+CONTOUR_MASK_DTYPE = np.dtype([('mask', np.uint64), ('step', np.int64), ('h', np.int32), ('w', np.int32)], align=True)
+assert CONTOUR_MASK_DTYPE.itemsize == 24
+CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE = 1, 2
+CONTOURS_SHORT, CONTOURS_GAVE_UP = 1, 2
+# The capacities of a first call.  A page's text-line mask has a few hundred components and a (precise polygon, text region)
+# pair mask one or two, so 2048 contours cover a page and a batch of pairs; CHAIN_APPROX_SIMPLE keeps two points a stair step
+# of a slanted edge, some tens of thousands on a page of 64 slanted lines.  The whole block (16 KB + 512 KB + 24 bytes a
+# mask) is copied out once, about 20 us of PCIe; a batch that needs more is called a second time with exactly what
+# ``totals`` asks for.
+CONTOURS_DEFAULT_CAP_CONTOURS, CONTOURS_DEFAULT_CAP_POINTS = 2048, 65536
+CONTOURS_MAX_MASKS = 4096           # of one vkx_mask_contours_dev call; mask_contours splits a longer list
+
+
+def check_contour_arguments(cv_find_contours_method, keep_internal=False):
+    """What every contour call refuses before it touches the device."""
+    if keep_internal:
+        raise NotImplementedError('keep_internal=True: hole borders and the tree order are outside the accelerated path')
+    if cv_find_contours_method not in (CHAIN_APPROX_NONE, CHAIN_APPROX_SIMPLE):
+        raise ValueError(f'cv_find_contours_method {cv_find_contours_method}: CHAIN_APPROX_NONE (1) and CHAIN_APPROX_SIMPLE (2) '
+                         'are supported')
+
+
+def contour_mask_records(masks):
+    """``masks``: uint8 DevArrays (h, w), or windows ``(DevArray, up, left, h, w)`` inside one -> CONTOUR_MASK_DTYPE records."""
+    records = np.zeros(len(masks), CONTOUR_MASK_DTYPE)
+    for rec, item in zip(records, masks):
+        arr, up, left, h, w = item if isinstance(item, tuple) else (item, 0, 0) + tuple(item.shape)
+        if arr.dtype != np.uint8 or arr.ndim != 2:
+            raise TypeError('a mask is a uint8 plane')
+        if not (0 <= up and 0 <= left and 1 <= h and 1 <= w and up + h <= arr.shape[0] and left + w <= arr.shape[1]):
+            raise ValueError('a window outside its plane')
+        rec['mask'], rec['step'], rec['h'], rec['w'] = arr.ptr + up * arr.shape[1] + left, arr.shape[1], h, w
+    return records
+
+
+class ContoursRaw:
+    """The outputs of one vkx_mask_contours_dev call on the host (views of one page-locked block)."""
+
+    __slots__ = ('totals', 'n_contours', 'status', 'contour_len', 'contour_off', 'points')
+
+
+def mask_contours_raw(records, method=CHAIN_APPROX_SIMPLE, cap_contours=CONTOURS_DEFAULT_CAP_CONTOURS,
+                      cap_points=CONTOURS_DEFAULT_CAP_POINTS, ctx=None):
+    """ONE vkx_mask_contours_dev call on CONTOUR_MASK_DTYPE ``records``: eight launches, ONE copy-out of the block that holds all
+    six outputs, ONE Context.sync -> ContoursRaw."""
+    ctx = ctx or default_ctx()
+    records = _records(records, CONTOUR_MASK_DTYPE)
+    n, cap_contours, cap_points = len(records), int(cap_contours), int(cap_points)
+    sizes = (16 * n, 4 * n, 4 * n, 4 * cap_contours, 4 * cap_contours, 8 * cap_points)      # totals first: int64
+    offs = np.concatenate([[0], np.cumsum([(s + 15) & ~15 for s in sizes])])
+    block = ctx.dev_empty((max(int(offs[-1]), 16),), np.uint8)
+    at = [c_void_p(block.ptr + int(o)) for o in offs[:6]]
+    check(lib().vkx_mask_contours_dev(ctx.handle, records.ctypes.data if n else None, n, int(method), cap_contours, cap_points,
+                                      at[1], at[3], at[4], at[5], at[0], at[2]))
+    host = ctx.pinned_empty(block.shape, np.uint8)
+    ctx.copy_out(block.ptr, host)
+    ctx.sync()
+    raw = ContoursRaw()
+    part = lambda k, dtype: host[int(offs[k]):int(offs[k]) + sizes[k]].view(dtype)  # noqa: E731
+    raw.totals, raw.n_contours, raw.status = part(0, np.int64).reshape(n, 2), part(1, np.int32), part(2, np.int32)
+    raw.contour_len, raw.contour_off, raw.points = part(3, np.int32), part(4, np.int32), part(5, np.int32).reshape(cap_points, 2)
+    return raw
+
+
+def mask_contours(masks, method=CHAIN_APPROX_SIMPLE, cap_contours=None, cap_points=None, ctx=None):
+    """cv.findContours(mask * 255, RETR_TREE, method) filtered to hierarchy parent -1, for every mask of ``masks`` (see
+    ``contour_mask_records``) in one batched call -> per mask the list of its contours, int32 (k, 2) arrays of (x, y) in the
+    mask's own coordinates.  A batch within the default capacities costs one call (one copy-out, one Context.sync); one beyond
+    them is called once more with the sizes the first call reported."""
+    check_contour_arguments(method)
+    masks = list(masks)
+    if not masks:
+        return []
+    if len(masks) > CONTOURS_MAX_MASKS:
+        return [contours for k in range(0, len(masks), CONTOURS_MAX_MASKS)
+                for contours in mask_contours(masks[k:k + CONTOURS_MAX_MASKS], method, cap_contours, cap_points, ctx)]
+    first = masks[0][0] if isinstance(masks[0], tuple) else masks[0]
+    ctx = ctx or first.ctx
+    for item in masks:
+        arr = item[0] if isinstance(item, tuple) else item
+        if arr.ctx is not ctx:
+            raise ValueError('the masks of a batch live on one context')
+        arr.after_views(ctx)
+    records = contour_mask_records(masks)
+    raw = mask_contours_raw(records, method, CONTOURS_DEFAULT_CAP_CONTOURS if cap_contours is None else cap_contours,
+                            CONTOURS_DEFAULT_CAP_POINTS if cap_points is None else cap_points, ctx)
+    if (raw.status & CONTOURS_SHORT).any():
+        if int(raw.totals[:, 1].sum()) > 0x7fffffff:
+            raise VkxError('mask_contours: the batch has more than 2^31 - 1 contour points; split it')
+        raw = mask_contours_raw(records, method, int(raw.totals[:, 0].sum()), int(raw.totals[:, 1].sum()), ctx)
+    if (raw.status & CONTOURS_GAVE_UP).any():
+        raise VkxError('mask_contours: a trace reached its step cap (a mask changed during the call)')
+    if raw.status.any():
+        raise VkxError('mask_contours: the capacities the first call reported were not enough')
+    out, c = [], 0
+    for k in raw.n_contours.tolist():
+        out.append([np.array(raw.points[raw.contour_off[g]:raw.contour_off[g] + raw.contour_len[g]]) for g in range(c, c + k)])
+        c += k
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------
 # fill_text_line_to_seal_impression for every seal of a page (csrc/seal_fill.hip): vkx_seal_char / vkx_seal_rec of include/vkx.h
 # --------------------------------------------------------------------------------------------------------------
 SEAL_SRC_F32, SEAL_SRC_U8C1, SEAL_SRC_U8C3, SEAL_SRC_HOST, SEAL_INTERNAL_NONE = 0, 1, 2, 16, -1
@@ -2793,7 +2898,8 @@ def set_mask(elements, shape, mode, want_windows=False, ctx=None, gated=False):
       a box-like object (``up`` / ``left`` / ``height`` / ``width``): its window is active;
       a signed-integer (N, 2) array of (x, y) vertices in plane coordinates: the cv.fillPoly raster, window = its bounding box;
       a uint8 or float32 plane (numpy or DevArray), active where > 0, over the whole plane or, as ``(plane, box_like)`` or
-      ``(plane, (up, left))``, over that window.
+      ``(plane, (up, left))``, over that window; ``(plane, (up, left), (part_up, part_left, height, width))`` places only that
+      rectangle of the plane.
     At most FOUR launches whatever the number of elements, asynchronous while no polygon has more than 64 vertices.  Host planes
     are uploaded for the call.  Returns a DevArray in resident mode or when an element plane is one, else a host array; with
     ``want_windows`` also the list of every element's own active raster over its window (``gated``: ANDed with the result), as
@@ -2813,9 +2919,9 @@ def set_mask(elements, shape, mode, want_windows=False, ctx=None, gated=False):
     kinds, geos, planes, steps = [SET_POLYGON] * n, [None] * n, [0] * n, [0] * n
     points, poly_at, keep = [], [], []
     for i, el in enumerate(elements):
-        window = None
+        window = part = None
         if type(el) is tuple:
-            el, window = el
+            el, window, *part = el
         if isinstance(el, np.ndarray) and el.ndim == 2 and el.shape[1] == 2 and el.dtype.kind == 'i':
             if not len(el):
                 raise ValueError('a polygon without points')
@@ -2829,16 +2935,22 @@ def set_mask(elements, shape, mode, want_windows=False, ctx=None, gated=False):
             if dev.ctx is not ctx:
                 raise ValueError('the element planes live on one context')
             keep.append(dev)
+            # ``part``: the rectangle (up, left, height, width) of the plane that takes part, the whole plane without one
+            part_up, part_left, part_h, part_w = part[0] if part else (0, 0) + tuple(el.shape)
+            if not (0 <= part_up and 0 <= part_left and 1 <= part_h and 1 <= part_w and part_up + part_h <= el.shape[0] and
+                    part_left + part_w <= el.shape[1]):
+                raise ValueError('the part of a plane that takes part lies inside the plane')
             if window is None:
                 up, left = 0, 0
             elif hasattr(window, 'up'):
-                if (window.height, window.width) != tuple(el.shape):
-                    raise ValueError(f'plane shape {tuple(el.shape)} != its window {(window.height, window.width)}')
+                if (window.height, window.width) != (part_h, part_w):
+                    raise ValueError(f'plane shape {(part_h, part_w)} != its window {(window.height, window.width)}')
                 up, left = window.up, window.left
             else:
                 up, left = window
-            kinds[i], geos[i] = (SET_SCORE_F32 if is_f32 else SET_MASK_U8), (up, left, el.shape[0], el.shape[1])
-            planes[i], steps[i] = dev.ptr, el.shape[1] * (4 if is_f32 else 1)
+            item = 4 if is_f32 else 1
+            kinds[i], geos[i] = (SET_SCORE_F32 if is_f32 else SET_MASK_U8), (up, left, part_h, part_w)
+            planes[i], steps[i] = dev.ptr + (part_up * el.shape[1] + part_left) * item, el.shape[1] * item
         else:
             raise TypeError(f'set_mask: not an element: {type(el).__name__}')
     recs = np.zeros(n, SET_ELEM_DTYPE)

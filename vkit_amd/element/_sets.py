@@ -41,6 +41,15 @@ def set_entries(kind, elements, origin=None):
         elif kind == POLYGONS:
             table = element.to_np_array()
             entries.append(table - np.array([ox, oy], np.int32) if origin else table)
+        elif element.box and origin and not (origin.up <= element.box.up and element.box.down <= origin.down and
+                                             origin.left <= element.box.left and element.box.right <= origin.right):
+            # a plane that reaches beyond the box takes part with what lies inside it
+            up, down = max(element.box.up, origin.up), min(element.box.down, origin.down)
+            left, right = max(element.box.left, origin.left), min(element.box.right, origin.right)
+            if up > down or left > right:
+                raise ValueError('an element that lies outside the box altogether')
+            entries.append((element.arr, (up - oy, left - ox),
+                            (up - element.box.up, left - element.box.left, down - up + 1, right - left + 1)))
         elif element.box:
             entries.append((element.arr, (element.box.up - oy, element.box.left - ox)))
         else:

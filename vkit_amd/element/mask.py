@@ -1,4 +1,5 @@
 """Binary mask element: uint8 HxW, active where > 0 (reference: vkit/element/mask.py)."""
+import logging
 from typing import Iterable, Optional, Tuple, Union
 
 import attrs
@@ -7,6 +8,8 @@ import numpy as np
 from ._writable import LazyMat, WritableContext
 from .opt import generate_resized_shape
 from .type import ElementSetOperationMode, Shapable
+
+logger = logging.getLogger(__name__)
 
 
 _LUT_INVERT = (np.arange(256) == 0).astype(np.uint8).reshape(1, 256)           # (~(mat > 0)).astype(uint8)
@@ -245,6 +248,36 @@ class Mask(LazyMat, Shapable):
         return Box(up=int(np_vert_nonzero[0]), down=int(np_vert_nonzero[-1]), left=int(np_hori_nonzero[0]),
                    right=int(np_hori_nonzero[-1]))
 
+    # ---- contours (reference mask.py:635-749): csrc/contours.hip, see masks_to_disconnected_polygons below
+    def to_external_polygon(self, cv_find_contours_method: int = 2):
+        polygons = self.to_disconnected_polygons(cv_find_contours_method=cv_find_contours_method)
+        if not polygons:
+            raise RuntimeError('Cannot find any contour.')
+        if len(polygons) > 1:
+            logger.warning('More than one polygons is detected, keep the largest one as the external polygon.')
+            area_max = 0
+            best_polygon = None
+            for polygon in polygons:
+                if polygon.area > area_max:
+                    area_max = polygon.area
+                    best_polygon = polygon
+            assert best_polygon
+            return best_polygon
+        return polygons[0]
+
+    def to_disconnected_polygons(self, cv_find_contours_method: int = 2, keep_internal: bool = False):
+        return masks_to_disconnected_polygons([self], cv_find_contours_method=cv_find_contours_method,
+                                              keep_internal=keep_internal)[0]
+
+    def to_disconnected_polygon_mask_pairs(self, cv_find_contours_method: int = 2):
+        pairs = []
+        for polygon in self.to_disconnected_polygons(cv_find_contours_method=cv_find_contours_method):
+            bounding_box = polygon.to_bounding_box()
+            boxed_mask = Mask.from_shapable(bounding_box).to_box_attached(bounding_box)
+            polygon.fill_mask(boxed_mask)
+            pairs.append((polygon, boxed_mask))
+        return pairs
+
     def to_score_map(self):
         return ScoreMap(mat=self.np_mask.astype(np.float32), box=self.box)
 
@@ -289,7 +322,74 @@ def generate_fill_by_masks_mask(shape, masks, mode: ElementSetOperationMode):
     return Mask.from_masks(shape, masks, mode)
 
 
+def _split_by_make_valid(polygon: 'Polygon'):
+    """The reference splits a traced polygon that shapely calls invalid through shapely.validation.make_valid (mask.py:705-728).
+    Where shapely imports, that branch runs; where it does not, the traced polygon is returned unsplit."""
+    try:
+        from shapely.geometry import GeometryCollection, MultiPolygon
+        from shapely.geometry import Polygon as ShapelyPolygon
+        from shapely.validation import make_valid
+    except ImportError:
+        return [polygon]
+
+    def from_shapely(shapely_polygon):
+        xy_pairs = [tuple(xy) for xy in shapely_polygon.exterior.coords]
+        unique = [xy for k, xy in enumerate(xy_pairs) if k == 0 or xy != xy_pairs[k - 1]]
+        if len(unique) > 1 and unique[0] == unique[-1]:
+            unique.pop()
+        assert len(unique) >= 3
+        return Polygon.from_xy_pairs(unique)
+
+    shapely_logger = logging.getLogger('shapely.geos')
+    level = shapely_logger.level
+    shapely_logger.setLevel(logging.WARNING)
+    try:
+        valid = make_valid(ShapelyPolygon(polygon.to_xy_pairs()))
+    finally:
+        shapely_logger.setLevel(level)
+    if isinstance(valid, ShapelyPolygon):
+        return [polygon]
+    out = []
+    if isinstance(valid, (MultiPolygon, GeometryCollection)):
+        for geom in valid.geoms:
+            if isinstance(geom, ShapelyPolygon):
+                out.append(from_shapely(geom))
+            elif isinstance(geom, MultiPolygon):
+                out.extend(from_shapely(sub) for sub in geom.geoms if isinstance(sub, ShapelyPolygon))
+    return out
+
+
+def masks_to_disconnected_polygons(masks, cv_find_contours_method: int = 2, keep_internal: bool = False):
+    """``Mask.to_disconnected_polygons`` of every mask of ``masks`` -> a list of lists of polygons, through ONE
+    ``_native.mask_contours`` call: cv.findContours(np_mask * 255, RETR_TREE, method), of which the contours without a parent are
+    kept, shifted by the mask's box; contours of fewer than 3 points are dropped.  A device-resident mask is read where it is, a
+    host-backed one is uploaded.  ``keep_internal=True`` (hole borders, tree order) is outside the accelerated path."""
+    from vkit_amd import _native
+    _native.check_contour_arguments(cv_find_contours_method, keep_internal)
+    masks = list(masks)
+    if not masks:
+        return []
+    ctx = next((m.arr.ctx for m in masks if m.on_device), None) or _native.default_ctx()
+    contours = _native.mask_contours([ctx.to_device(m.arr) for m in masks], cv_find_contours_method, ctx=ctx)
+    out = []
+    for mask, mask_contours in zip(masks, contours):
+        polygons = []
+        for np_points in mask_contours:
+            if mask.box:
+                np_points[:, 0] += mask.box.left
+                np_points[:, 1] += mask.box.up
+            if np_points.shape[0] < 3:
+                continue
+            if (np_points[0] == np_points[-1]).all():
+                np_points = np_points[:-1]                # Polygon.from_np_array drops a closing duplicate
+            # (the vertices stay one array: the Point objects of a contour are built when something asks for them)
+            polygons.extend(_split_by_make_valid(Polygon.from_smooth_xy(np_points)))
+        out.append(polygons)
+    return out
+
+
 from .box import Box  # noqa: E402
 from .score_map import ScoreMap  # noqa: E402
 from .image import Image  # noqa: E402
+from .polygon import Polygon  # noqa: E402
 from . import _sets  # noqa: E402

@@ -75,6 +75,14 @@ class Polygon:
         return self.bounding_box
 
     @property
+    def area(self):
+        """shapely's Polygon(integer points).area (reference polygon.py:48-53): the absolute shoelace sum of the ring, exact in
+        float64 on integer vertices."""
+        xy = self.to_np_array().astype(np.float64)
+        x, y = xy[:, 0] - xy[0, 0], xy[:, 1] - xy[0, 1]
+        return abs(float(np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y))) / 2
+
+    @property
     def self_relative_polygon(self):
         # reference polygon.py:105-138,59-64: shift by the (integer valued) minima, rebuild through from_np_array
         xy = self.to_smooth_np_array()

@@ -41,6 +41,7 @@ from .page_text_line_label import (  # noqa: F401
 from .page_text_region import (  # noqa: F401
     ColumnPacker,
     FlattenedTextRegion,
+    PageTextRegionStep,
     PageTextRegionStepOutput,
     TextRegionFlattener,
     build_background_image_for_stacking,

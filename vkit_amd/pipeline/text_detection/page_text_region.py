@@ -2,10 +2,13 @@
 output container.
 
 ``PageTextRegionStepOutput`` (:177-186) is the input of PageTextRegionLabelStep and PageTextRegionCroppingStep.  The step as
-a whole needs shapely, rectpack, pyclipper and cv.findContours and stays outside the accelerated path; what is here is
+a whole needs shapely, rectpack and pyclipper and stays outside the accelerated path; what is here is
 everything of it that is pixel work, batched over all text regions of a page (csrc/region_masks.hip,
-csrc/region_flatten.hip):
+csrc/region_flatten.hip, csrc/contours.hip):
 
+* ``PageTextRegionStep.generate_precise_text_region_candidate_polygons`` (:868-897) and its plural form: the AND of a precise
+  mask and a disconnected text-region mask over their common box, then the outer contours (``Mask.to_disconnected_polygons``,
+  cv.findContours on the device) -- eight launches and one synchronisation for all pairs of a list;
 * ``TextRegionFlattener.get_bounding_extended_text_region_masks`` (:477-558): the page's text mask by the fresh mask paint,
   then the three rasters and the mask algebra of every region -- three launches, no synchronisation while no polygon has
   more than 64 vertices;
@@ -16,7 +19,7 @@ csrc/region_flatten.hip):
   launch each, no synchronisation;
 * ``build_background_image_for_stacking`` and ``stack_flattened_text_regions`` (:732-856): one launch, no synchronisation.
 
-The polygon geometry that decides the polygons and the angles (shapely, pyclipper, findContours, the KD-tree) is the caller's
+The polygon geometry that decides the polygons and the angles (shapely, pyclipper, the KD-tree) is the caller's
 (the host's); the masks built from them flow into the flattening on the device.  Results are device resident inside
 ``_native.resident(True)`` or when an input was; otherwise they come back as numpy arrays, by one copy a call.
 """
@@ -432,6 +435,38 @@ def post_rotate_flattened_text_regions(flattened_text_regions: Sequence[Flattene
         for k, region in zip(picked, rotated):
             regions[k] = region
     return regions
+
+
+# ---- candidate polygons ----------------------------------------------------------------------------------------------
+class PageTextRegionStep:
+    """What of the reference's step class is pixel work on masks (:868-897); its host geometry (pyclipper, the STR-tree, the
+    KD-tree, the minimum-area rectangle) stays outside."""
+
+    @classmethod
+    def _intersected_mask(cls, precise_mask: Mask, disconnected_text_region_mask: Mask):
+        assert precise_mask.box and disconnected_text_region_mask.box
+        intersected_box = Box(up=max(precise_mask.box.up, disconnected_text_region_mask.box.up),
+                              down=min(precise_mask.box.down, disconnected_text_region_mask.box.down),
+                              left=max(precise_mask.box.left, disconnected_text_region_mask.box.left),
+                              right=min(precise_mask.box.right, disconnected_text_region_mask.box.right))
+        assert intersected_box.up <= intersected_box.down
+        assert intersected_box.left <= intersected_box.right
+        # the reference's `a.mat & b.mat` of two 0 / 1 planes: active where both are (one vkx_set_mask call, each mask read
+        # through its window over the box)
+        from vkit_amd.element.type import ElementSetOperationMode
+        return Mask.from_masks(intersected_box, [disconnected_text_region_mask, precise_mask], ElementSetOperationMode.INTERSECT)
+
+    @classmethod
+    def generate_precise_text_region_candidate_polygons(cls, precise_mask: Mask, disconnected_text_region_mask: Mask):
+        # 1. Could extract more than one polygons.  2. Some polygons are in border and should be removed later.
+        return cls._intersected_mask(precise_mask, disconnected_text_region_mask).to_disconnected_polygons()
+
+    @classmethod
+    def generate_precise_text_region_candidate_polygons_of_pairs(cls, pairs):
+        """``generate_precise_text_region_candidate_polygons`` of every (precise_mask, disconnected_text_region_mask) pair of
+        ``pairs`` -> a list of lists; the contours of all pairs come from ONE contour call."""
+        from vkit_amd.element.mask import masks_to_disconnected_polygons
+        return masks_to_disconnected_polygons([cls._intersected_mask(precise, region) for precise, region in pairs])
 
 
 # ---- stacking ------------------------------------------------------------------------------------------------------
