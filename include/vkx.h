@@ -1115,6 +1115,51 @@ int vkx_mask_contours_dev(vkx_ctx *ctx, const vkx_contour_mask *masks_host, int 
                           int cap_points, int32_t *n_contours, int32_t *contour_len, int32_t *contour_off, int32_t *points,
                           int64_t *totals, int32_t *status);
 
+/* ---- char binding: the mask-overlap counts of PageTextRegionStep (pipeline/text_detection/page_text_region.py) ---------------
+ * vkx_poly_overlap_counts_dev: the integer areas behind calculate_boxed_masks_intersected_ratio (:189-227) for every
+ * (candidate, anchor) pair that strtree_query_intersected_polygons (:899-925) visits, i.e. for the pairing of precise polygons
+ * with disconnected text regions (:1115-1149) and the binding of a page's chars to its precise text regions (:1160-1216).
+ * polys_host: one HOST record a polygon: its box (up, left, h, w: Polygon.bounding_box) and the range [pts_off, pts_off +
+ * pts_cnt) of its SELF-RELATIVE points (Polygon.self_relative_polygon.to_np_array()) in the HOST int32 table pts_host of (x, y)
+ * pairs.  pairs_host: HOST int32 [n_pairs][2] as (candidate, anchor), indices into polys_host.  The tables are dense.
+ * counts: DEVICE int32 [n_polys + n_pairs]: counts[i] is the raster area of polygon i -- the number of pixels that
+ * cv.fillPoly(zeros((h, w)), [points], 1) sets (the raster of vkx_fill_poly_mask_u8: LINE_8 outline plus even-odd spans; what
+ * falls outside the h x w box is clipped), Polygon.mask.np_mask.sum() --, counts[n_polys + k] the intersected area of pair k:
+ * the pixels that both rasters set inside the intersection of the two boxes, 0 where the boxes do not meet (:200-218).  The
+ * device does no division: intersected_area / base_area is the caller's (two ints, float64).
+ * Every polygon is rasterised once into a bit plane of its own in context scratch (one bit a pixel, rows padded to 32-bit
+ * words; h * ((w + 31) / 32) * 4 bytes a polygon).  Three launches and one memset whatever n_polys and n_pairs; every count is
+ * written by one lane with a plain store, no atomics: a rerun gives identical bytes.  The host tables travel through the
+ * page-locked ring: the call does not synchronise while no polygon has more than 64 points; with a larger one it waits for the
+ * crossing-overflow flag, and more than 64 crossings of one polygon on a scanline are VKX_ERR_UNSUPPORTED (as in
+ * vkx_paint_polys_dev).  n_polys == 0 with n_pairs == 0 returns at once.
+ * Refused (VKX_ERR_INVALID, nothing launched): a negative count; a NULL pointer; a pair index outside [0, n_polys); a polygon
+ * of fewer than 1 point or with a point range that is negative or overflows; a box side outside 1 .. 32767; a box origin
+ * beyond +-2^30; bit planes of more than VKX_POLY_OVERLAP_MAX_SCRATCH bytes in all (the caller splits its candidates into
+ * several calls, the anchors rasterised in each). */
+#define VKX_POLY_OVERLAP_MAX_SCRATCH (1ll << 30)
+typedef struct vkx_poly_overlap_rec {
+    int32_t up, left, h, w;             /* the polygon's box */
+    int32_t pts_off, pts_cnt;           /* its self-relative points in pts_host, in points */
+} vkx_poly_overlap_rec;
+int vkx_poly_overlap_counts_dev(vkx_ctx *ctx, const vkx_poly_overlap_rec *polys_host, int n_polys, const int32_t *pts_host,
+                                const int32_t *pairs_host, int n_pairs, int32_t *counts);
+/* vkx_mask_overlap_counts_dev: the same areas for box-attached masks that are not polygons (:189-227 itself).  One HOST record
+ * a pair: the two DEVICE uint8 planes with their boxes (up, left, h, w) and row steps (bytes from a row to the next, at least
+ * one row, unused with a single row: the pitch contract of this header; a plane may be a rectangle inside a larger one).
+ * counts: DEVICE int64 [n_recs][3]: the sum of the bytes of (anchor & candidate) over the intersection of the two boxes (0
+ * where they do not meet), the number of nonzero bytes of the anchor, the number of nonzero bytes of the candidate.  One launch,
+ * no synchronisation, no atomics; n_recs == 0 returns at once.  Refused (VKX_ERR_INVALID, nothing launched): n_recs outside
+ * 0 .. 65536, a NULL pointer or plane, a box side outside 1 .. 32767, a box origin beyond +-2^30, a row step shorter than a row
+ * or negative, counts overlapping a plane. */
+typedef struct vkx_mask_overlap_rec {
+    const uint8_t *anchor, *candidate;
+    int64_t anchor_step, candidate_step;
+    int32_t anchor_up, anchor_left, anchor_h, anchor_w;
+    int32_t candidate_up, candidate_left, candidate_h, candidate_w;
+} vkx_mask_overlap_rec;
+int vkx_mask_overlap_counts_dev(vkx_ctx *ctx, const vkx_mask_overlap_rec *recs_host, int n_recs, int64_t *counts);
+
 /* ---- the set-operation mask of a list of elements (element/mask.py:126-244) -----------------------------------------------
  * Mask.from_boxes / from_polygons / from_masks / from_score_maps and, through generate_fill_by_*_mask, the DISTINCT / INTERSECT
  * forms of the fill_by_* families (element/image.py:371-665, mask.py:283-410, score_map.py:315-520): count(y, x) is the number

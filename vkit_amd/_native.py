@@ -411,6 +411,8 @@ _SIGNATURES['vkx_region_stack_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_vo
 _SIGNATURES['vkx_region_extend_masks_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_ssize, c_int, c_int, c_void_p,
                                               ctypes.c_size_t]
 _SIGNATURES['vkx_mask_contours_dev'] = [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6
+_SIGNATURES['vkx_poly_overlap_counts_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]
+_SIGNATURES['vkx_mask_overlap_counts_dev'] = [c_void_p, c_void_p, c_int, c_void_p]
 _SIGNATURES['vkx_fill_u8_batch_dev'] =[c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ssize, ctypes.POINTER(VkxLayer), c_void_p]
 _SIGNATURES['vkx_seal_fill_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
 _SIGNATURES['vkx_text_lines_dev'] = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t]
@@ -2793,6 +2795,54 @@ def mask_contours(masks, method=CHAIN_APPROX_SIMPLE, cap_contours=None, cap_poin
     for k in raw.n_contours.tolist():
         out.append([np.array(raw.points[raw.contour_off[g]:raw.contour_off[g] + raw.contour_len[g]]) for g in range(c, c + k)])
         c += k
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------
+# char binding (csrc/polygon_overlap.hip): vkx_poly_overlap_rec / vkx_mask_overlap_rec of include/vkx.h
+# --------------------------------------------------------------------------------------------------------------
+POLY_OVERLAP_REC_DTYPE = np.dtype([('up', np.int32), ('left', np.int32), ('h', np.int32), ('w', np.int32), ('pts_off', np.int32),
+                                   ('pts_cnt', np.int32)], align=True)
+MASK_OVERLAP_REC_DTYPE = np.dtype([('anchor', np.uint64), ('candidate', np.uint64), ('anchor_step', np.int64),
+                                   ('candidate_step', np.int64), ('anchor_up', np.int32), ('anchor_left', np.int32),
+                                   ('anchor_h', np.int32), ('anchor_w', np.int32), ('candidate_up', np.int32),
+                                   ('candidate_left', np.int32), ('candidate_h', np.int32), ('candidate_w', np.int32)], align=True)
+assert (POLY_OVERLAP_REC_DTYPE.itemsize, MASK_OVERLAP_REC_DTYPE.itemsize) == (24, 64)
+POLY_OVERLAP_MAX_SCRATCH = 1 << 30      # VKX_POLY_OVERLAP_MAX_SCRATCH
+
+
+def poly_overlap_plane_bytes(records):
+    """The bytes of bit plane that vkx_poly_overlap_counts_dev needs for every record (int64 array)."""
+    return records['h'].astype(np.int64) * ((records['w'].astype(np.int64) + 31) >> 5) * 4
+
+
+def poly_overlap_counts(records, points_xy, pairs, ctx=None):
+    """vkx_poly_overlap_counts_dev: ``records`` POLY_OVERLAP_REC_DTYPE (a box and the range of the self-relative points of every
+    polygon), ``points_xy`` the int32 (N, 2) table they index, ``pairs`` int32 (k, 2) as (candidate, anchor) -> DevArray int32
+    (n + k,): the raster area of every polygon, then the intersected area of every pair.  THREE launches and one memset
+    whatever the tables hold; asynchronous while no polygon has more than 64 points: the caller copies out and synchronises."""
+    ctx = ctx or default_ctx()
+    records = _records(records, POLY_OVERLAP_REC_DTYPE)
+    points_xy = np.ascontiguousarray(points_xy, dtype=np.int32).reshape(-1, 2)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if len(records) and int((records['pts_off'].astype(np.int64) + records['pts_cnt']).max()) > len(points_xy):
+        raise ValueError('a point range outside the point table')
+    out = ctx.dev_empty((max(len(records) + len(pairs), 1),), np.int32)
+    check(lib().vkx_poly_overlap_counts_dev(ctx.handle, records.ctypes.data if len(records) else None, len(records),
+                                            points_xy.ctypes.data, pairs.ctypes.data if len(pairs) else None, len(pairs),
+                                            c_void_p(out.ptr)))
+    return out
+
+
+def mask_overlap_counts(records, ctx=None):
+    """vkx_mask_overlap_counts_dev on MASK_OVERLAP_REC_DTYPE ``records`` -> DevArray int64 (n, 3): the byte sum of
+    anchor & candidate over the intersection of the boxes, the nonzero bytes of the anchor, those of the candidate.  ONE
+    launch, asynchronous."""
+    ctx = ctx or default_ctx()
+    records = _records(records, MASK_OVERLAP_REC_DTYPE)
+    out = ctx.dev_empty((max(len(records), 1), 3), np.int64)
+    check(lib().vkx_mask_overlap_counts_dev(ctx.handle, records.ctypes.data if len(records) else None, len(records),
+                                            c_void_p(out.ptr)))
     return out
 
 

@@ -128,6 +128,8 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->collate_tables);
     scratch_release(&ctx->contour_tables);
     scratch_release(&ctx->contour_planes);
+    scratch_release(&ctx->ov_tables);
+    scratch_release(&ctx->ov_bits);
     scratch_release(&ctx->glass_win);
     scratch_release(&ctx->jpeg_planes);
     scratch_release(&ctx->pz_tabs);

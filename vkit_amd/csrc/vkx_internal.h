@@ -177,6 +177,7 @@ struct vkx_ctx {
     vkx_scratch collate_tables;               // batch collate (collate.hip): the staged image and plane records of the last call
     vkx_scratch contour_tables, contour_planes;   // mask contours (contours.hip): the staged mask records; the label planes, start bitmaps, starts and
                                                   // contour lengths of the last call, sized to its batch and kept until the context is destroyed
+    vkx_scratch ov_tables, ov_bits;           // char binding (polygon_overlap.hip): the overflow flag + staged tables (or the mask records); the polygons' bit planes of the last call
     vkx_scratch glass_win;                 // glass shuffle: the winner plane of a round's scatter (uint64 [h, w], zero between rounds)
     vkx_scratch pz_tabs, pz_work, pz_draws;   // rng.poisson on the device (poisson.hip): per-lam constants; block plan; raw draws + E rows
     bool pz_tabs_ready = false;

@@ -41,10 +41,16 @@ from .page_text_line_label import (  # noqa: F401
 from .page_text_region import (  # noqa: F401
     ColumnPacker,
     FlattenedTextRegion,
+    PageTextRegionInfo,
     PageTextRegionStep,
     PageTextRegionStepOutput,
     TextRegionFlattener,
     build_background_image_for_stacking,
+    calculate_boxed_masks_intersected_ratio,
+    calculate_boxed_masks_intersected_ratios,
+    envelope_pairs,
+    intersected_polygon_ratios,
+    polygon_overlap_tables,
     post_rotate_flattened_text_regions,
     resize_flattened_text_regions,
     stack_flattened_text_regions,

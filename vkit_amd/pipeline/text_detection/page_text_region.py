@@ -2,13 +2,19 @@
 output container.
 
 ``PageTextRegionStepOutput`` (:177-186) is the input of PageTextRegionLabelStep and PageTextRegionCroppingStep.  The step as
-a whole needs shapely, rectpack and pyclipper and stays outside the accelerated path; what is here is
+a whole needs rectpack and pyclipper and stays outside the accelerated path; what is here is
 everything of it that is pixel work, batched over all text regions of a page (csrc/region_masks.hip,
-csrc/region_flatten.hip, csrc/contours.hip):
+csrc/region_flatten.hip, csrc/contours.hip, csrc/polygon_overlap.hip):
 
 * ``PageTextRegionStep.generate_precise_text_region_candidate_polygons`` (:868-897) and its plural form: the AND of a precise
   mask and a disconnected text-region mask over their common box, then the outer contours (``Mask.to_disconnected_polygons``,
   cv.findContours on the device) -- eight launches and one synchronisation for all pairs of a list;
+* ``calculate_boxed_masks_intersected_ratio`` (:189-227), ``PageTextRegionStep.strtree_query_intersected_polygons`` (:899-925)
+  and the binding of the page's chars to its precise text regions (:1160-1216: ``intersected_polygon_ratios``,
+  ``bind_char_polygons``, ``build_page_text_region_infos``), with ``find_precise_text_region_candidate_polygons`` (:1115-1149)
+  composed on top: the STR-tree query is the closed integer envelope test (``envelope_pairs``, no shapely), every polygon
+  is rasterised once into a bit plane and every pair is counted -- three launches, one copy-out and one synchronisation
+  whatever the numbers of chars and regions; the ratios are formed on the host from the integer counts;
 * ``TextRegionFlattener.get_bounding_extended_text_region_masks`` (:477-558): the page's text mask by the fresh mask paint,
   then the three rasters and the mask algebra of every region -- three launches, no synchronisation while no polygon has
   more than 64 vertices;
@@ -23,6 +29,7 @@ The polygon geometry that decides the polygons and the angles (shapely, pyclippe
 (the host's); the masks built from them flow into the flattening on the device.  Results are device resident inside
 ``_native.resident(True)`` or when an input was; otherwise they come back as numpy arrays, by one copy a call.
 """
+import logging
 import math
 import statistics
 from typing import Any, List, Optional, Sequence, Tuple
@@ -33,6 +40,8 @@ import numpy as np
 from vkit_amd import _native
 from vkit_amd.element import Box, Image, Mask, Polygon
 from vkit_amd.mechanism.distortion.geometric.affine import RotateConfig, RotateState, rotate
+
+logger = logging.getLogger(__name__)
 
 
 @attrs.define
@@ -437,10 +446,257 @@ def post_rotate_flattened_text_regions(flattened_text_regions: Sequence[Flattene
     return regions
 
 
+# ---- char binding: mask-overlap ratios (:189-227, :899-925, :1160-1216) ---------------------------------------------------
+@attrs.define
+class PageTextRegionInfo:
+    precise_text_region_polygon: Polygon
+    char_polygons: Sequence[Polygon]
+
+
+def _boxes_meet(anchor_box: Box, candidate_box: Box):
+    return (max(anchor_box.up, candidate_box.up) <= min(anchor_box.down, candidate_box.down)
+            and max(anchor_box.left, candidate_box.left) <= min(anchor_box.right, candidate_box.right))
+
+
+def calculate_boxed_masks_intersected_ratios(pairs, use_candidate_as_base: bool = False):
+    """``calculate_boxed_masks_intersected_ratio(anchor_mask, candidate_mask, use_candidate_as_base)`` for every
+    (anchor_mask, candidate_mask) pair of ``pairs`` -> a list of floats.  The masks are box attached, host or device
+    resident; host planes are uploaded by one copy.  All pairs whose boxes meet go through ONE launch, one copy-out and one
+    synchronisation; pairs whose boxes do not meet are 0.0 and, when no boxes meet, the device is not touched.  A zero base
+    raises ZeroDivisionError, as the reference's division does."""
+    pairs = list(pairs)
+    for anchor_mask, candidate_mask in pairs:
+        assert anchor_mask.box and candidate_mask.box
+    met = [k for k, (anchor_mask, candidate_mask) in enumerate(pairs) if _boxes_meet(anchor_mask.box, candidate_mask.box)]
+    ratios = [0.0] * len(pairs)
+    if not met:
+        return ratios
+    src = _Sources([_arr(mask) for k in met for mask in pairs[k]])
+    records = np.zeros(len(met), _native.MASK_OVERLAP_REC_DTYPE)
+    for rec, n, k in zip(records, range(len(met)), met):
+        for name, mask, ptr in (('anchor', pairs[k][0], src.ptr[2 * n]), ('candidate', pairs[k][1], src.ptr[2 * n + 1])):
+            box = mask.box
+            rec[name], rec[name + '_step'] = ptr, box.width
+            rec[name + '_up'], rec[name + '_left'], rec[name + '_h'], rec[name + '_w'] = box.up, box.left, box.height, box.width
+    counts_dev = _native.mask_overlap_counts(records, ctx=src.ctx)
+    counts = src.ctx.pinned_empty((len(met), 3), np.int64)
+    src.ctx.copy_out(counts_dev.ptr, counts)
+    src.ctx.sync()
+    for k, (intersected_area, anchor_area, candidate_area) in zip(met, counts.tolist()):
+        base_area = candidate_area if use_candidate_as_base else anchor_area + candidate_area - intersected_area
+        ratios[k] = intersected_area / base_area
+    return ratios
+
+
+def calculate_boxed_masks_intersected_ratio(anchor_mask: Mask, candidate_mask: Mask, use_candidate_as_base: bool = False):
+    return calculate_boxed_masks_intersected_ratios([(anchor_mask, candidate_mask)], use_candidate_as_base)[0]
+
+
+def polygon_overlap_tables(polygons: Sequence[Polygon]):
+    """The tables of a batch of polygons, vectorised: (``records`` POLY_OVERLAP_REC_DTYPE with ``Polygon.bounding_box`` and the
+    point range of every polygon, ``points`` int32 (N, 2) holding ``Polygon.self_relative_polygon.to_np_array()`` of every
+    polygon at its range, ``envelopes`` int64 (n, 4) as (xmin, xmax, ymin, ymax) of the integer ``to_xy_pairs()``)."""
+    n = len(polygons)
+    records = np.zeros(n, _native.POLY_OVERLAP_REC_DTYPE)
+    if n == 0:
+        return records, np.zeros((0, 2), np.int32), np.zeros((0, 4), np.int64)
+    tables = [polygon.to_np_array() for polygon in polygons]
+    count = np.array([len(table) for table in tables], np.int64)
+    first = np.concatenate([[0], np.cumsum(count)[:-1]])
+    if int(count.sum()) > 0x7fffffff:
+        raise ValueError('more than 2^31 - 1 points in one batch')
+    xy = np.concatenate(tables, axis=0).astype(np.int32).reshape(-1, 2)
+    envelopes = np.empty((n, 4), np.int64)
+    envelopes[:, 0::2] = np.minimum.reduceat(xy, first, axis=0)
+    envelopes[:, 1::2] = np.maximum.reduceat(xy, first, axis=0)
+    # Polygon.bounding_box / self_relative_polygon: the integer positions as float32 (the PointTuple quirk), the box from
+    # round() of their minima and maxima, the points rounded after the float minimum is subtracted
+    smooth = xy.astype(np.float32)
+    low = np.minimum.reduceat(smooth, first, axis=0)
+    high = np.maximum.reduceat(smooth, first, axis=0)
+    relative = np.rint(smooth - np.repeat(low, count, axis=0)).astype(np.int32)
+    low, high = np.rint(low).astype(np.int64), np.rint(high).astype(np.int64)
+    if (np.abs(low) > 1 << 30).any() or (high - low >= 1 << 31).any():
+        raise ValueError('a polygon beyond the int32 range of the tables')
+    records['up'], records['left'] = low[:, 1], low[:, 0]
+    records['h'], records['w'] = high[:, 1] - low[:, 1] + 1, high[:, 0] - low[:, 0] + 1
+    # PointList.from_np_array drops a closing duplicate of the first point
+    last = first + count - 1
+    closed = (count > 2) & (relative[first] == relative[last]).all(axis=1)
+    records['pts_off'], records['pts_cnt'] = first, count - closed
+    return records, relative, envelopes
+
+
+def envelope_pairs(anchor_envelopes: np.ndarray, candidate_envelopes: np.ndarray):
+    """What ``sorted(STRtree(anchors).query(candidate))`` answers for every candidate, without shapely: the anchors whose
+    envelope (the closed integer rectangle (xmin, xmax, ymin, ymax) of its points) meets the candidate's; touching envelopes
+    count.  -> int32 (k, 2) as (candidate, anchor), candidate-major, anchors ascending."""
+    a, c = np.asarray(anchor_envelopes, np.int64).reshape(-1, 4), np.asarray(candidate_envelopes, np.int64).reshape(-1, 4)
+    out = []
+    # (blocks of candidates: the boolean matrix of a block stays below 16 MB)
+    step = max(1, (16 << 20) // max(len(a), 1))
+    for at in range(0, len(c), step):
+        b = c[at:at + step, None, :]
+        meet = (a[None, :, 0] <= b[:, :, 1]) & (b[:, :, 0] <= a[None, :, 1]) & (a[None, :, 2] <= b[:, :, 3]) & (b[:, :, 2] <= a[None, :, 3])
+        ci, ai = np.nonzero(meet)
+        out.append(np.stack([ci + at, ai], axis=1))
+    return np.concatenate(out, axis=0).astype(np.int32) if out else np.zeros((0, 2), np.int32)
+
+
+def plan_overlap_calls(pairs: np.ndarray, anchor_bytes: np.ndarray, candidate_bytes: np.ndarray, bound: int):
+    """The calls of one batch: runs [begin, end) of the candidate-major ``pairs`` such that the bit planes of a run's candidates
+    and of the anchors they meet stay within ``bound`` bytes (a run of a single candidate may exceed it: the library decides).
+    Candidates are taken in order and never split."""
+    k = len(pairs)
+    if int(anchor_bytes[np.unique(pairs[:, 1])].sum() + candidate_bytes[np.unique(pairs[:, 0])].sum()) <= bound:
+        return [(0, k)]
+    starts = np.flatnonzero(np.concatenate([[True], pairs[1:, 0] != pairs[:-1, 0]]))
+    ends = np.concatenate([starts[1:], [k]])
+    calls, begin, anchors, need = [], 0, set(), 0
+    for s, e in zip(starts.tolist(), ends.tolist()):
+        met = set(pairs[s:e, 1].tolist())
+        own = int(candidate_bytes[pairs[s, 0]])
+        more = own + sum(int(anchor_bytes[a]) for a in met - anchors)
+        if need and need + more > bound:
+            calls.append((begin, s))
+            begin, anchors, need = s, set(), 0
+            more = own + sum(int(anchor_bytes[a]) for a in met)
+        anchors |= met
+        need += more
+    calls.append((begin, k))
+    return calls
+
+
+def intersected_polygon_ratios(anchor_polygons: Sequence[Polygon], candidate_polygons: Sequence[Polygon],
+                               use_candidate_as_base: bool = True, max_scratch_bytes: Optional[int] = None):
+    """The batch form of ``PageTextRegionStep.strtree_query_intersected_polygons``: every (candidate, anchor) pair whose
+    envelopes meet, with the integer areas and the ratio of ``calculate_boxed_masks_intersected_ratio(anchor.mask,
+    candidate.mask, use_candidate_as_base)`` -> (``pairs`` int32 (k, 2) as (candidate, anchor), candidate-major with anchors
+    ascending, ``intersected_area`` int64 (k,), ``base_area`` int64 (k,), ``ratio`` float64 (k,)).
+
+    The envelope pairs and the self-relative point tables are built on the host with numpy; the device rasterises every
+    polygon that is in a pair once and counts (three launches, one copy-out, one ``Context.sync``; zero pairs: no device call);
+    the ratios are ``int64 / int64`` on the host, the correctly rounded float64 of the reference's division.  The bit planes of
+    one call are bounded by ``max_scratch_bytes`` (default: VKX_POLY_OVERLAP_MAX_SCRATCH, 1 GiB): a batch that needs more is
+    split by candidates into several calls, each rasterising the anchors its candidates meet, still with one synchronisation;
+    the result does not depend on the split.  A single candidate whose planes and anchors exceed the bound is refused by the
+    library."""
+    anchor_polygons, candidate_polygons = list(anchor_polygons), list(candidate_polygons)
+    n_anchors = len(anchor_polygons)
+    records, points, envelopes = polygon_overlap_tables(anchor_polygons + candidate_polygons)
+    pairs = envelope_pairs(envelopes[:n_anchors], envelopes[n_anchors:])
+    k = len(pairs)
+    intersected_area, base_area = np.zeros(k, np.int64), np.zeros(k, np.int64)
+    if k == 0:
+        return pairs, intersected_area, base_area, np.zeros(0, np.float64)
+    bound = _native.POLY_OVERLAP_MAX_SCRATCH if max_scratch_bytes is None else int(max_scratch_bytes)
+    plane_bytes = _native.poly_overlap_plane_bytes(records)
+    ctx = _native.default_ctx()
+    # the calls: runs of candidates (pairs are candidate-major) whose planes, with those of the anchors they meet, fit the bound
+    calls = plan_overlap_calls(pairs, plane_bytes[:n_anchors], plane_bytes[n_anchors:], bound)
+    area = np.zeros(len(records), np.int64)
+    pending = []
+    for s, e in calls:
+        part = pairs[s:e].astype(np.int64)
+        part[:, 0] += n_anchors
+        used, local = np.unique(part, return_inverse=True)
+        counts_dev = _native.poly_overlap_counts(records[used], points, local.reshape(-1, 2).astype(np.int32), ctx=ctx)
+        counts = ctx.pinned_empty((len(used) + e - s,), np.int32)
+        ctx.copy_out(counts_dev.ptr, counts)
+        pending.append((s, e, used, counts, counts_dev))
+    ctx.sync()
+    for s, e, used, counts, _ in pending:
+        area[used] = counts[:len(used)]
+        intersected_area[s:e] = counts[len(used):]
+    if use_candidate_as_base:
+        base_area[:] = area[n_anchors + pairs[:, 0]]
+    else:
+        base_area[:] = area[pairs[:, 1]] + area[n_anchors + pairs[:, 0]] - intersected_area
+    if (base_area == 0).any():
+        raise ZeroDivisionError('division by zero')
+    return pairs, intersected_area, base_area, intersected_area / base_area
+
+
 # ---- candidate polygons ----------------------------------------------------------------------------------------------
 class PageTextRegionStep:
-    """What of the reference's step class is pixel work on masks (:868-897); its host geometry (pyclipper, the STR-tree, the
-    KD-tree, the minimum-area rectangle) stays outside."""
+    """What of the reference's step class is pixel work on masks (:868-925, :1115-1216); its host geometry (pyclipper, the
+    KD-tree, the minimum-area rectangle) stays outside.  The STR-tree is not needed: the step only asks it which envelopes
+    meet (``envelope_pairs``)."""
+
+    @classmethod
+    def strtree_query_intersected_polygons(cls, strtree, anchor_polygons: Sequence[Polygon], candidate_polygon: Polygon):
+        """The reference's generator (:899-925) of (anchor_idx, anchor_polygon, anchor_mask, candidate_mask,
+        intersected_ratio), anchors ascending.  ``strtree`` may be ``None`` and is not consulted: what
+        ``sorted(strtree.query(candidate))`` answers is computed from the envelopes of ``anchor_polygons``.  The ratios of all
+        answers come from one ``intersected_polygon_ratios`` call; the masks are ``Polygon.mask``."""
+        pairs, _, _, ratios = intersected_polygon_ratios(anchor_polygons, [candidate_polygon], use_candidate_as_base=True)
+        if len(pairs) == 0:
+            return
+        candidate_mask = candidate_polygon.mask
+        for anchor_idx, intersected_ratio in zip(pairs[:, 1].tolist(), ratios.tolist()):
+            anchor_polygon = anchor_polygons[anchor_idx]
+            yield anchor_idx, anchor_polygon, anchor_polygon.mask, candidate_mask, intersected_ratio
+
+    @classmethod
+    def bind_char_polygons(cls, precise_text_region_polygons: Sequence[Polygon], char_polygons: Sequence[Polygon],
+                           max_scratch_bytes: Optional[int] = None):
+        """The binding of :1176-1205 for all chars at once -> int32 (len(char_polygons),): the index of the precise text
+        region that covers most of the char's mask (the first of equal ratios; a ratio of 0.0 does not bind), -1 for none."""
+        bound = np.full(len(char_polygons), -1, np.int32)
+        pairs, _, _, ratios = intersected_polygon_ratios(precise_text_region_polygons, char_polygons, use_candidate_as_base=True,
+                                                         max_scratch_bytes=max_scratch_bytes)
+        if len(pairs) == 0:
+            return bound
+        # per char (a run of the candidate-major pairs): the first anchor whose ratio is strictly above every earlier one
+        # and above 0, i.e. the first position of the run's maximum where that is positive
+        starts = np.flatnonzero(np.concatenate([[True], pairs[1:, 0] != pairs[:-1, 0]]))
+        lengths = np.diff(np.concatenate([starts, [len(pairs)]]))
+        best = np.repeat(np.maximum.reduceat(ratios, starts), lengths)
+        position = np.where((ratios == best) & (ratios > 0), np.arange(len(pairs)), len(pairs))
+        first = np.minimum.reduceat(position, starts)
+        found = first < len(pairs)
+        bound[pairs[starts[found], 0]] = pairs[first[found], 1]
+        return bound
+
+    @classmethod
+    def build_page_text_region_infos(cls, precise_text_region_polygons: Sequence[Polygon], char_polygons: Sequence[Polygon],
+                                     max_scratch_bytes: Optional[int] = None):
+        """:1160-1216: the precise text regions that received at least one char, in region order, each with its chars in char
+        order; a char that no region binds logs the reference's warning and is dropped."""
+        bound = cls.bind_char_polygons(precise_text_region_polygons, char_polygons, max_scratch_bytes=max_scratch_bytes)
+        ptrp_idx_to_char_polygons = {}
+        for char_polygon, ptrp_idx in zip(char_polygons, bound.tolist()):
+            if ptrp_idx >= 0:
+                ptrp_idx_to_char_polygons.setdefault(ptrp_idx, []).append(char_polygon)
+            else:
+                logger.warning(f'Cannot assign a text region for char_polygon={char_polygon}')
+        return [PageTextRegionInfo(precise_text_region_polygon=precise_text_region_polygon,
+                                   char_polygons=ptrp_idx_to_char_polygons[ptrp_idx])
+                for ptrp_idx, precise_text_region_polygon in enumerate(precise_text_region_polygons)
+                if ptrp_idx in ptrp_idx_to_char_polygons]
+
+    @classmethod
+    def find_precise_text_region_candidate_polygons(cls, page_shape: Tuple[int, int],
+                                                    disconnected_text_region_polygons: Sequence[Polygon],
+                                                    page_resized_text_line_mask: Mask):
+        """:1115-1149: the precise polygons of the resized text-line mask, resized back to ``page_shape``, each cut by every
+        disconnected text region whose envelope it meets (precise polygons in contour order, regions ascending) -> the flat
+        list of candidate polygons.  Composed of ``Mask.to_disconnected_polygons``, ``to_conducted_resized_polygon``,
+        ``envelope_pairs`` and ``generate_precise_text_region_candidate_polygons_of_pairs``."""
+        page_height, page_width = (int(v) for v in page_shape)
+        disconnected_text_region_polygons = list(disconnected_text_region_polygons)
+        precise_polygons = [
+            resized_precise_polygon.to_conducted_resized_polygon(page_resized_text_line_mask, resized_height=page_height,
+                                                                 resized_width=page_width)
+            for resized_precise_polygon in page_resized_text_line_mask.to_disconnected_polygons()]
+        n_regions = len(disconnected_text_region_polygons)
+        _, _, envelopes = polygon_overlap_tables(disconnected_text_region_polygons + precise_polygons)
+        pairs = envelope_pairs(envelopes[:n_regions], envelopes[n_regions:])
+        if len(pairs) == 0:
+            return []
+        candidates = cls.generate_precise_text_region_candidate_polygons_of_pairs(
+            [(precise_polygons[c].mask, disconnected_text_region_polygons[a].mask) for c, a in pairs.tolist()])
+        return [polygon for polygons in candidates for polygon in polygons]
 
     @classmethod
     def _intersected_mask(cls, precise_mask: Mask, disconnected_text_region_mask: Mask):
