@@ -1439,6 +1439,31 @@ typedef struct vkx_collate_norm {
 int vkx_collate_dev(vkx_ctx *ctx, const vkx_collate_image *images_host, int n_images, const vkx_collate_plane *planes_host,
                     int n_planes, const vkx_collate_norm *norm);
 
+/* ---- JPEG encode (vkit_amd/element/image.py: Image.to_file, to_jpeg_bytes, encode_jpeg_images) ------------------------------
+ * Image.to_file of the reference (image.py:351-359: to_rgb_image, to_pil_image, PIL's save) for a path Pillow writes as JPEG, for
+ * a whole batch: every image becomes the file `PIL.Image.fromarray(mat).save(f, format='JPEG', quality=quality)` writes with
+ * Pillow 12.2.0 / libjpeg-turbo 3.1.4.1 -- SOI, APP0 (JFIF 1.1, density 1 x 1, unit 0), one DQT per table, SOF0 (baseline; three
+ * channels: sampling 2x2, 1x1, 1x1), one DHT per table (the Annex K tables), SOS, the scan without restart markers, EOI --
+ * byte for byte (tests/jpeg_encode_restate.py, tests/golden/jpeg_encode.npz).
+ * images_host is a HOST table of n records; every src is a DEVICE pointer to a DENSE uint8 [h][w][cn] block, cn 1 (one
+ * component) or 3.  quality 0 .. 100 as in vkx_jpeg_roundtrip_u8 (0 scales the tables as 1).  bgr 1: channel 2 carries the red
+ * weight (cv.imencode, vkx_jpeg_roundtrip_u8); bgr 0: channel 0 does (Pillow's mode RGB, Image in RGB mode).
+ * out (device, `capacity` bytes) takes the files packed back to back: image i is out[offsets[i] .. offsets[i + 1]), offsets
+ * (device, int64 [n + 1], 8-byte aligned) is written completely and offsets[n] is the total.  When the total exceeds capacity
+ * nothing is written at or past out + capacity, offsets is complete all the same and the call returns VKX_OK: the caller reads
+ * offsets[n] and calls again with a buffer of that size.
+ * Eight launches and one memset whatever n is, no synchronisation; the scratch (140 bytes of coefficients, bit counts and offsets
+ * plus 208 bytes of unstuffed stream per 8 x 8 block, dummy blocks included) belongs to the context.
+ * Refused (VKX_ERR_INVALID, nothing launched, nothing written): a NULL argument or src, n outside 1 .. 65535, h or w outside
+ * 1 .. 32768, cn other than 1 / 3, quality outside 0 .. 100, bgr other than 0 / 1, a negative capacity, offsets not aligned, out
+ * or offsets overlapping a source or each other, more than 2^26 blocks in one call. */
+typedef struct vkx_jpeg_image {
+    const uint8_t *src;   /* device, uint8 [h][w][cn], dense */
+    int32_t h, w, cn;
+} vkx_jpeg_image;
+int vkx_jpeg_encode_u8_dev(vkx_ctx *ctx, const vkx_jpeg_image *images_host, int n, int quality, int bgr, uint8_t *out,
+                           long long capacity, int64_t *offsets);
+
 /* ---- per-kernel timing -----------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair recorded on the ctx
  * stream; vkx_ctx_collect_timings synchronises and folds them into per-kernel totals.

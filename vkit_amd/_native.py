@@ -262,6 +262,10 @@ class VkxCollateNorm(ctypes.Structure):
                 ('channels_first', ctypes.c_int32), ('mean', ctypes.c_float * 3), ('scale', ctypes.c_float * 3)]
 
 
+class VkxJpegImage(ctypes.Structure):
+    _fields_ = [('src', c_void_p), ('h', ctypes.c_int32), ('w', ctypes.c_int32), ('cn', ctypes.c_int32)]
+
+
 class VkxCombineTile(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in ('up', 'down', 'left', 'right', 'source')]
 
@@ -427,6 +431,8 @@ _SIGNATURES['vkx_ctx_wait_external'] = [c_void_p, c_void_p]
 _SIGNATURES['vkx_ctx_signal_external'] = [c_void_p, c_void_p]
 _SIGNATURES['vkx_collate_dev'] = [c_void_p, ctypes.POINTER(VkxCollateImage), c_int, ctypes.POINTER(VkxCollatePlane), c_int,
                                   ctypes.POINTER(VkxCollateNorm)]
+_SIGNATURES['vkx_jpeg_encode_u8_dev'] = [c_void_p, ctypes.POINTER(VkxJpegImage), c_int, c_int, c_int, c_void_p, ctypes.c_longlong,
+                                         c_void_p]
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['vkx_version', 'vkx_last_error', 'vkx_ctx_stream'])
 
 _lib = None
@@ -1975,6 +1981,70 @@ def jpeg_roundtrip(img, quality, ctx=None):
     dst, dptr = call.out(img.shape, np.uint8)
     check(call.fn('vkx_jpeg_roundtrip_u8')(call.ctx.handle, call.src(img), h, w, cn, stride, dptr, stride, int(quality)))
     return dst
+
+
+JPEG_ENCODE_MAX_IMAGES = 65535
+# the scans of csrc/jpeg_encode.hip (an image's blocks, its chunks, the images of a call): entries a round of the shape a range of up
+# to JPEG_SCAN_SMALL_MAX entries takes, and of the shape a longer one takes
+JPEG_SCAN_SMALL_MAX, JPEG_SCAN_SMALL_ROUND, JPEG_SCAN_LARGE_ROUND = 2048, 128, 8192
+
+
+def jpeg_encode_raw(records, n, quality, bgr, capacity, ctx):
+    """ONE vkx_jpeg_encode_u8_dev call on a ``VkxJpegImage`` table into a fresh device buffer of ``capacity`` bytes: eight launches,
+    the copy-out of ``offsets`` and ONE Context.sync -> (the buffer, offsets as int64 [n + 1] on the host).  ``offsets[n]`` above
+    ``capacity``: the buffer holds the first ``capacity`` bytes only."""
+    out = ctx.dev_empty((max(int(capacity), 1),), np.uint8)
+    offsets = ctx.dev_empty((n + 1,), np.int64)
+    check(lib().vkx_jpeg_encode_u8_dev(ctx.handle, records, n, int(quality), int(bool(bgr)), c_void_p(out.ptr), int(capacity),
+                                       c_void_p(offsets.ptr)))
+    host = ctx.pinned_empty((n + 1,), np.int64)
+    ctx.copy_out(offsets.ptr, host)
+    ctx.sync()
+    return out, host
+
+
+def jpeg_encode(images, quality=75, bgr=False, ctx=None, capacity=None):
+    """The JPEG files ``PIL.Image.fromarray(mat).save(f, format='JPEG', quality=quality)`` writes (Pillow's defaults: baseline,
+    4:2:0, Annex K tables), byte for byte, for a batch of uint8 ``H x W`` or ``H x W x 3`` numpy arrays or DevArrays of any mix of
+    shapes, encoded on the device in one call (include/vkx.h vkx_jpeg_encode_u8_dev) -> a list of ``bytes``.  ``bgr``: channel 2
+    carries the red weight (what ``cv.imencode`` reads); otherwise channel 0 does.  One synchronisation to read the sizes, then one
+    copy of exactly the files' bytes.  ``capacity``: the bytes of the first call's buffer (default: the raw bytes of the batch plus
+    1024 an image); a batch that compresses to more is encoded once more at the size the first call reported."""
+    images = list(images)
+    if not images:
+        return []
+    if len(images) > JPEG_ENCODE_MAX_IMAGES:
+        return [data for k in range(0, len(images), JPEG_ENCODE_MAX_IMAGES)
+                for data in jpeg_encode(images[k:k + JPEG_ENCODE_MAX_IMAGES], quality, bgr, ctx, capacity)]
+    if not 0 <= int(quality) <= 100:
+        raise ValueError(f'quality {quality} outside 0 .. 100')
+    for img in images:
+        h, w, cn, _ = _shape_u8(img)
+        if cn not in (1, 3) or not (1 <= h <= 32768 and 1 <= w <= 32768):
+            raise ValueError(f'jpeg_encode takes HxW or HxWx3 with sides of 1 .. 32768, got shape {tuple(img.shape)}')
+    call = _Call(ctx, *images)
+    ctx = call.ctx
+    n = len(images)
+    keep = [img if isinstance(img, DevArray) else ctx.to_device(np.ascontiguousarray(img)) for img in images]
+    records = (VkxJpegImage * n)()
+    raw = 0
+    for rec, arr in zip(records, keep):
+        if arr._viewed:
+            arr.after_views(ctx)
+        h, w, cn, _ = _shape_u8(arr)
+        rec.src, rec.h, rec.w, rec.cn = arr.ptr, h, w, cn
+        raw += arr.nbytes
+    capacity = raw + 1024 * n if capacity is None else int(capacity)
+    out, offsets = jpeg_encode_raw(records, n, quality, bgr, capacity, ctx)
+    total = int(offsets[n])
+    if total > capacity:
+        out, offsets = jpeg_encode_raw(records, n, quality, bgr, total, ctx)
+        if int(offsets[n]) != total:
+            raise VkxError('jpeg_encode: the images changed between the two calls')
+    host = ctx.pinned_empty((total,), np.uint8)
+    ctx.download(out.ptr, host)
+    view = memoryview(host)         # one host copy a file: out of the page-locked block
+    return [bytes(view[int(offsets[i]):int(offsets[i + 1])]) for i in range(n)]
 
 
 def zoom_in_blur(img, sizes_hw, alpha, ctx=None):

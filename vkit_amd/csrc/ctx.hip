@@ -132,6 +132,8 @@ VKX_EXPORT int vkx_ctx_destroy(vkx_ctx *ctx)
     scratch_release(&ctx->ov_bits);
     scratch_release(&ctx->glass_win);
     scratch_release(&ctx->jpeg_planes);
+    scratch_release(&ctx->jpeg_encode_tables);
+    scratch_release(&ctx->jpeg_encode_work);
     scratch_release(&ctx->pz_tabs);
     scratch_release(&ctx->pz_work);
     scratch_release(&ctx->pz_draws);

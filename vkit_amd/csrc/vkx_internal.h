@@ -154,6 +154,8 @@ struct vkx_ctx {
     vkx_scratch camera_work;                  // camera states (camera.hip): descriptors, results, the depth values of the cubic curve
     vkx_scratch fog_work;                     // fog field (fog.hip): raw draws + the float64 centres of a level; a glass round's temporaries
     vkx_scratch jpeg_planes;                  // jpeg round trip (jpeg.hip): the decoded Y, Cb, Cr planes at their padded sizes
+    vkx_scratch jpeg_encode_tables, jpeg_encode_work;   // jpeg encoder (jpeg_encode.hip): the staged records, Huffman codes and headers of the last call;
+                                                        // its coefficients, bit and stuffing offsets and unstuffed streams
     vkx_scratch crop_windows, crop_planes;      // page cropping (crop.hip): the window and plane tables of the last call
     vkx_scratch combine_tables;               // combiner image engine (image_combine.hip): block bins + tile records of the last call
     vkx_scratch char_table, char_geo, char_layout, char_host;   // char masks (char_mask.hip): chars, setup results, tile layout,

@@ -5,4 +5,4 @@ from .polygon import Polygon
 from .soup import PointArray, PolygonSoup
 from .mask import Mask, MaskSetItemConfig
 from .score_map import ScoreMap, ScoreMapSetItemConfig, quad_u, quad_v
-from .image import Image, ImageMode, ImageSetItemConfig
+from .image import Image, ImageMode, ImageSetItemConfig, encode_jpeg_images

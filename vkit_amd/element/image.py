@@ -153,6 +153,35 @@ class Image(LazyMat, Shapable):
                 pil_image = PilImageOps.exif_transpose(pil_image)
         return cls.from_pil_image(pil_image)
 
+    def to_pil_image(self):
+        from PIL import Image as PilImage
+        return PilImage.fromarray(self.mat)
+
+    def to_jpeg_bytes(self, quality: int = 75):
+        """The file ``to_pil_image().save(f, format='JPEG', quality=quality)`` writes, encoded on the device (csrc/jpeg_encode.hip):
+        a 2-D mat as one component, a 3-channel mat with channel 0 as red."""
+        return encode_jpeg_images([self], quality=quality)[0]
+
+    def to_file(self, path, disable_to_rgb_image: bool = False):
+        """The image written to ``path`` (reference image.py:351-359): converted to RGB unless disabled, then saved as Pillow saves
+        it by the path's extension.  A uint8 image of 1 or 3 channels under an extension Pillow writes as JPEG
+        (``JPEG_EXTENSIONS``) is encoded on the device, at Pillow's default quality 75 and to the byte the file Pillow writes;
+        every other file is Pillow's ``save`` of the host copy."""
+        import os
+        image = self
+        if not disable_to_rgb_image:
+            image = image.to_rgb_image()
+        # PilImage.save cannot handle `~`
+        path = os.path.expanduser(os.fspath(path))
+        if os.path.splitext(path)[1].lower() in JPEG_EXTENSIONS and image.arr.dtype == np.uint8:
+            if image.num_channels not in (0, 3):
+                raise OSError(f'cannot write mode {image.mode.name} as JPEG')        # as Pillow's JPEG plugin answers
+            data = image.to_jpeg_bytes()
+            with open(path, 'wb') as f:
+                f.write(data)
+            return
+        image.to_pil_image().save(path)
+
     # ---- properties
     @property
     def height(self):
@@ -376,6 +405,21 @@ class Image(LazyMat, Shapable):
 
     def to_rgba_image(self):
         return self.to_target_mode_image(ImageMode.RGBA)
+
+
+# the extensions Pillow maps to its JPEG plugin, lower case
+JPEG_EXTENSIONS = ('.jpg', '.jpeg', '.jpe', '.jfif')
+
+
+def encode_jpeg_images(images, quality: int = 75):
+    """``image.to_jpeg_bytes(quality)`` for every image of ``images`` (uint8, 1 or 3 channels, any mix of shapes: the crops of a
+    page) in ONE device call -> a list of ``bytes``."""
+    from vkit_amd import _native
+    images = list(images)
+    for image in images:
+        if image.arr.dtype != np.uint8 or image.num_channels not in (0, 3):
+            raise OSError(f'cannot write mode {image.mode.name} as JPEG')
+    return _native.jpeg_encode([image.arr for image in images], quality=quality)
 
 
 from .box import Box  # noqa: E402
